@@ -8,27 +8,32 @@ subdivision surface at the reference's bomberman.ecs settings (subdivision level
 `--compress.leaf` = subdiv_accel=bvh4.compressed.leaf: 46 528 cBVH blobs under a quantized BVH8) — traced with
 1 M random incoherent rays per step (the viewer's makeRandomRay generator, drand48 LCG).  `--workload tri`
 selects BASELINE configs[1] (same rays vs the BVH8 of bomberman's 1454 fan triangles), `eager` the default
-GridSOA-style subdiv accel, `cbvh.box` / `cbvh.grid` the other fork modes.  The JSON line of the default run also
-carries the tri and eager rates under config.other_workloads (short runs of the same loop).
+GridSOA-style subdiv accel, `cbvh.box` / `cbvh.grid` the other fork modes.  With --full, the JSON line of the default
+run also carries the tri and eager rates under config.other_workloads (short runs of the same loop).
 
 One "step" = one rtcIntersect1M call over one batch of device-resident RTCRayHit records.  Every step traces a
-DIFFERENT, freshly generated batch (a trace modifies rays in place, so re-tracing a batch would shrink the work).
-Rank r owns its own batches (weak scaling, no data-path collective: SURVEY.md 8e); the accel is replicated per
-GPU.  Timing: barrier + synchronize on both sides of exactly K steps, MAX over ranks; `value` = all rays of all
-ranks / that time.
+freshly restored batch (a trace modifies rays in place, so re-tracing a batch would shrink the work); the batches of
+one timed region are distinct buffers (contents drawn from up to SRC_DISTINCT differently seeded batches).  Rank r owns
+its own batches (weak scaling, no data-path collective: SURVEY.md 8e); the accel is replicated per GPU.  Timing:
+barrier + synchronize on both sides of every timed region, MAX over ranks; `value` = all rays of all ranks / the
+time of K steps.
 
-The timed region of K steps is REPEATED (`--repeats`, default: as many as make the timed regions add up to >= 60 ms, 5..40): every
-repeat restores the K batches from pristine device copies (untimed), is bracketed by barrier + synchronize like the single region
-of the contract, and `value` / `ms_per_step` are those of the MEDIAN repeat (min / max next to them): a 2-4 ms region alone was
-what round 2's headline hung on.
+A plain run (`--steps K --warmup W`) does only what `value` needs: build the scene, W warm-up steps, EXACTLY K timed steps,
+the result line.  The K steps run in regions of at most REGION_STEPS steps (each step needs a working batch of its own in
+device memory): before every region, its batches are restored from pristine device copies (untimed), and
+`ms_per_step` = the summed region times / K (after the warm-up, the region's steps first run untimed for SETTLE_S).
+`--repeats R` times the K steps R times and reports the MEDIAN repeat (min / max next to it).  `--dump-outputs DIR` writes
+the records the last timed step returned (bench.py dump_outputs).
 
-The JSON line also carries
+--full adds the side measurements below, each in passes of its own.  Its default is --repeats 0: as many repeats as make the
+timed steps add up to >= 60 ms, 5..40 (a 2-4 ms region alone was what round 2's headline hung on).  The line then also carries
   one_stream       the same K steps strictly back-to-back on ONE stream (what a caller sees that does not pipeline batches)
   roofline         algorithmic bytes per launch / mean kernel time (HIP events on the launch stream) vs 8 TB/s; `bytes_per_ray_addressed`
                    prices a blob visit at the fields it actually reads instead of the whole record
   roofline_scaled  the same measurement on the scaled scene (--scaled-levels, default 8,3: 381 MB of blobs, larger than L2 + Infinity
                    Cache), with the PMC traffic of the committed profile of that scene
   cpu_baseline     the oracle (a scalar C port of the reference's AVX2 path) on the host cores, bounded sample
+  config.pcie_inclusive_Mrays   the same workload through host pointers
 """
 import argparse
 import glob
@@ -45,6 +50,18 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec peak
 IO_BYTES_PER_RAY = 84  # 48 B RTCRay read + 36 B (tfar, Ng, u, v, primID, geomID, instID) written
+# timed steps per region at most: every step of a region traces a working batch of its own (80 MB at 1 M rays, plus the pristine
+# copies), so device memory and setup stay bounded whatever --steps is; the first steps of a region fill the pipeline of batches in
+# flight (regions of 5 / 10 steps read 20-25 % / ~15 % low: about 1.5 steps lost per region), which 128 steps amortise to ~1 %
+REGION_STEPS = 128
+# differently seeded batches generated on the host at most (about 0.2 s each at 1 M rays): working batch b of a region is restored
+# from pristine batch b % SRC_DISTINCT.  The working batches are distinct buffers, so no step reads another's records from a cache.
+SRC_DISTINCT = 32
+# untimed settle before the first timed region: the region's own steps, restored each time, for this long.  After the idle set-up the
+# GPU needs tens of milliseconds of work to reach the state the later repeats of a region run in (a single region of 20 steps read
+# 3 % below the median of 36 repeats without it)
+SETTLE_S = 0.1
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: at most this much in all (a fixed, seeded sample of the rays beyond it)
 
 # name -> (device config, geometry kind, oracle mode, dominant-kernel tag in rocprof output, description)
 WORKLOADS = {
@@ -66,11 +83,20 @@ def parse():
     ap.add_argument("--rays", type=int, default=1_000_000, help="rays per step per GPU")
     ap.add_argument("--workload", default="cbvh.leaf", choices=list(WORKLOADS))
     ap.add_argument("--levels", default="6,3", help="subdivision level, compression level")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the cpu_baseline sample (0 = skip)")
-    ap.add_argument("--no-others", action="store_true", help="skip the short tri / eager side runs")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of K steps each (0 = auto: >= 60 ms of timed regions in total, 5..40)")
-    ap.add_argument("--scaled-levels", default="8,3", help="levels of the scaled scene measured for roofline_scaled on the default workload ('none' = skip)")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-record (PCIe-inclusive) side measurement: under a profiler its chunk launches would mix into the kernel statistics")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure one_stream, roofline (+ work counters, committed profiles), the PCIe-inclusive rate, cpu_baseline, the tri / "
+                         "eager side runs and roofline_scaled; without it the run does only what `value` needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records the last timed step returned as DIR/<field>.npy (float32 / float64, "
+                         "all finite: hit.npy / occluded.npy flag the rays whose tfar is infinite; <= 64 MB in all: a fixed, seeded sample "
+                         "of the rays beyond that, with its ray indices in ray_index.npy)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: budget of the cpu_baseline sample (0 = skip)")
+    ap.add_argument("--no-others", action="store_true", help="--full: skip the short tri / eager side runs")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="times the K timed steps are measured, value = median (0 = auto: >= 60 ms of timed steps in total, 5..40); "
+                         "default 1, with --full 0")
+    ap.add_argument("--scaled-levels", default="8,3", help="--full: levels of the scaled scene measured for roofline_scaled on the default workload ('none' = skip)")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the host-record (PCIe-inclusive) side measurement: under a profiler its chunk launches would mix into the kernel statistics")
     ap.add_argument("--inflight", type=int, default=4,
                     help="ray batches in flight: step s is enqueued on HIP stream s %% inflight (1 = one stream, strictly back-to-back)")
     ap.add_argument("--query", default="intersect", choices=["intersect", "occluded"],
@@ -78,7 +104,12 @@ def parse():
                          "for --rays-kind secondary (shadow rays)")
     ap.add_argument("--rays-kind", default="random", choices=["random", "primary", "secondary"],
                     help="random: the metric's incoherent bbox rays; primary: BASELINE config 4, 1920x1080 camera rays of bomberman.ecs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 0 if args.full else 1
+    return args
 
 
 def build_hash():
@@ -213,10 +244,12 @@ def pcie_inclusive(sc, raygen, D, m, lo, hi, rank, reps=3):
 
 def run_loop(torch, dist, sc, dev, streams, bufs, src, K, W, world, occluded=False, repeats=0):
     """W untimed + R x K timed steps; step s goes to streams[s % len(streams)] (the library keeps per-launch scratch, so
-    batches on different streams overlap: the drain of one batch runs under the start of the next).  Every repeat first
-    restores bufs[W .. W+K) from the pristine copies src[...] (untimed; a trace modifies rays in place), then times EXACTLY K
-    steps bracketed by barrier + synchronize on both sides.  Returns the host-clock times of the repeats and, for ONE stream,
-    the HIP-event times per launch on that stream."""
+    batches on different streams overlap: the drain of one batch runs under the start of the next).  bufs = W warm-up batches,
+    P = len(bufs) - W - 1 working batches of the timed steps and a spare.  A repeat times EXACTLY K steps in regions of at most
+    P steps, each bracketed by barrier + synchronize on both sides; every region first restores its batches from the pristine
+    copies src[...] (untimed; a trace modifies rays in place).  Returns the host-clock times of the repeats
+    (sum of their regions) and, for ONE stream, the HIP-event times per launch on that stream.  Between the warm-up and the first
+    region, the steps of a region run untimed for SETTLE_S."""
     def barrier():
         torch.cuda.synchronize()
         if world > 1:
@@ -231,34 +264,49 @@ def run_loop(torch, dist, sc, dev, streams, bufs, src, K, W, world, occluded=Fal
         trace(bufs[s], ctx=ctx, check=False)
 
     # every stream (and every per-launch context of the library) is exercised before the clock starts: first use of a
-    # HIP stream costs milliseconds.  The extra untimed steps re-trace warm-up batches, never timed ones.
+    # HIP stream costs milliseconds.  The extra untimed steps re-trace warm-up batches (the spare without any), never timed ones.
     for s in range(W):
         step(s)
     for s in range(W, 2 * len(streams) if len(streams) > 1 else 0):
         st = streams[s % len(streams)]
         dev.set_stream(st.cuda_stream)
-        trace(bufs[s % max(W, 1)], ctx=ctx, check=False)
+        trace(bufs[s % W] if W else bufs[-1], ctx=ctx, check=False)
+    P = len(bufs) - W - 1
+    t_end = time.perf_counter() + SETTLE_S
+    while time.perf_counter() < t_end:
+        with torch.cuda.stream(streams[0]):
+            for s in range(W, W + min(K, P)):
+                bufs[s].copy_(src[s])
+        for s in range(W, W + min(K, P)):
+            step(s)
+        torch.cuda.synchronize()
     barrier()
     times, ev_ms = [], []
     target_s, done = 0.060, 0
     while True:
-        if done:  # fresh records for the next repeat
-            with torch.cuda.stream(streams[0]):
-                for s in range(W, W + K):
+        t_rep, ev_rep, left = 0.0, 0.0, K
+        while left:
+            n = min(left, P)
+            with torch.cuda.stream(streams[0]):  # fresh records for the region (every region alike: just written by the copy)
+                for s in range(W, W + n):
                     bufs[s].copy_(src[s])
-        barrier()
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        ev0.record(streams[0])
-        for s in range(W, W + K):
-            step(s)
-        ev1.record(streams[0])
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        barrier()
-        times.append(t1 - t0)
+            barrier()
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            ev0.record(streams[0])
+            for s in range(W, W + n):
+                step(s)
+            ev1.record(streams[0])
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            barrier()
+            t_rep += t1 - t0
+            if len(streams) == 1:
+                ev_rep += ev0.elapsed_time(ev1)
+            left -= n
+        times.append(t_rep)
         if len(streams) == 1:
-            ev_ms.append(ev0.elapsed_time(ev1) / K)
+            ev_ms.append(ev_rep / K)
         done += 1
         if repeats == 0:  # auto: from the first region's length (same on every rank: MAX over ranks)
             first = times[0]
@@ -272,6 +320,37 @@ def run_loop(torch, dist, sc, dev, streams, bufs, src, K, W, world, occluded=Fal
     dev.check("timed region")
     dev.set_stream(streams[0].cuda_stream)
     return times, ev_ms
+
+
+def dump_outputs(out_dir, last, occluded, rank, world):
+    """--dump-outputs: the fields rtcIntersect1M / rtcOccluded1M return in the records of the last timed step (`last`, a device tensor
+    of RTCRayHit[80B] / RTCRay[48B] rows), as <out_dir>/<field>.npy: float fields as float32, the uint32 IDs as float64 (exact).
+    Every array is finite: a ray that misses keeps its input tfar (+inf for the random rays) and an occluded ray reports -inf, so
+    hit.npy / occluded.npy (1 / 0) say which rays those are and tfar.npy holds 0 in them.  Beyond DUMP_BUDGET_BYTES / world per rank,
+    a fixed, seeded sample of the rays (sorted indices in ray_index.npy).  Rank r > 0 prefixes its files with rank<r>_."""
+    rec = last.cpu().numpy().view(np.uint32).reshape(last.shape[0], -1)
+    f32 = rec.view(np.float32)
+    if occluded:
+        flag = np.isneginf(f32[:, 8])
+        out = {"occluded": flag.astype(np.float32), "tfar": np.where(flag | ~np.isfinite(f32[:, 8]), np.float32(0), f32[:, 8])}
+    else:
+        flag = rec[:, 18] != 0xFFFFFFFF
+        out = {"hit": flag.astype(np.float32), "tfar": np.where(flag, f32[:, 8], np.float32(0))}
+        out.update({name: f32[:, col] for name, col in (("Ng_x", 12), ("Ng_y", 13), ("Ng_z", 14), ("u", 15), ("v", 16))})
+        out.update({name: rec[:, col].astype(np.float64) for name, col in (("primID", 17), ("geomID", 18), ("instID", 19))})
+    per_ray = sum(a.itemsize for a in out.values())
+    budget = DUMP_BUDGET_BYTES // world - 4096  # (the .npy headers)
+    if rec.shape[0] * per_ray > budget:
+        idx = np.sort(np.random.default_rng(20240607).choice(rec.shape[0], budget // (per_ray + 8), replace=False))
+        out = {name: a[idx] for name, a in out.items()}
+        out["ray_index"] = idx.astype(np.float64)
+    bad = [name for name, a in out.items() if not np.isfinite(a).all()]
+    if bad:
+        raise RuntimeError(f"--dump-outputs: non-finite values in {bad} (records of the last timed step)")
+    os.makedirs(out_dir, exist_ok=True)
+    pre = f"rank{rank}_" if rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, pre + name + ".npy"), np.ascontiguousarray(a))
 
 
 def median(v):
@@ -355,17 +434,19 @@ def main():
     occluded = args.query == "occluded"
     red_dev = "cpu" if rehearse else "cuda"
 
-    def measure(workload, K, W, lv=levels, repeats=args.repeats):
-        """One scene, two timed passes.  Returns a dict of everything the JSON line needs about it."""
+    def measure(workload, K, W, lv=levels, repeats=args.repeats, full=args.full):
+        """One scene; the timed pass of `value` (with --full also the one-stream pass and the work counters).  Returns a dict of
+        everything the JSON line needs about it."""
         nonlocal m
         t_build = time.perf_counter()
         dev, sc = build_scene(rtc, local_rank, workload, mesh, lv)
         t_build = time.perf_counter() - t_build
         dev.set_stream(stream.cuda_stream)
         sc.bench_ctx = rtc.make_context(coherent=True) if args.rays_kind == "primary" else None
-        # distinct batches per step and per rank, generated on the host, resident in HBM before timing starts: pristine copies
-        # `src` and the working records `bufs` the traces modify in place
-        nb = K + W + 1
+        # batches per rank, generated on the host, resident in HBM before timing starts: pristine copies `src` and the working
+        # records `bufs` the traces modify in place (W warm-up, P timed, 1 spare)
+        P = min(K, REGION_STEPS)
+        nb = P + W + 1
         if args.rays_kind == "secondary":
             # config 5, wavefront style: trace the camera frame once on THIS scene, record one bounce ray and one shadow ray
             # per hit (raygen.make_secondary_rays); every step traces a fresh copy of the recorded batch
@@ -381,42 +462,51 @@ def main():
             one = torch.from_numpy(primary[:, :48].copy() if occluded else primary).to("cuda")
             src = [one for s in range(nb)]
         else:
-            src = [torch.from_numpy(np.ascontiguousarray(raygen.make_random_rays(m, lo, hi, seed=D.batch_seed(rank, s))[:, :48 if occluded else 80])).to("cuda")
-                   for s in range(nb)]
+            distinct = [torch.from_numpy(np.ascontiguousarray(raygen.make_random_rays(m, lo, hi, seed=D.batch_seed(rank, s))[:, :48 if occluded else 80])).to("cuda")
+                        for s in range(min(nb, SRC_DISTINCT))]
+            src = [distinct[s % len(distinct)] for s in range(nb)]
         bufs = [t.clone() for t in src]
         torch.cuda.synchronize()
-        cnt = (sc.occluded1M_counted if occluded else sc.intersect1M_counted)(bufs[nb - 1], ctx=sc.bench_ctx)  # extra batch: work counters -> algorithmic bytes per ray
-        # pass 1, one stream: the kernel alone, HIP-event time per launch (the roofline figure; agrees with rocprofv3
-        # --kernel-trace of `bench.py --inflight 1`)
-        t1, ev1 = run_loop(torch, dist, sc, dev, streams[:1], bufs, src, K, W, world, occluded, repeats)
+        R = {"dev": dev, "sc": sc, "st": sc.stats(), "m": m, "K": K, "build_s": t_build}
+        # the records the last timed step returned (its working batch is not touched again after the pass of `value`)
+        last = bufs[W + (K - 1) % P]
+        t1 = ev1 = None
+        if full:
+            cnt = (sc.occluded1M_counted if occluded else sc.intersect1M_counted)(bufs[nb - 1], ctx=sc.bench_ctx)  # extra batch: work counters -> algorithmic bytes per ray
+        if full or nfl == 1:
+            # pass 1, one stream: the kernel alone, HIP-event time per launch (the roofline figure; agrees with rocprofv3
+            # --kernel-trace of `bench.py --inflight 1`)
+            t1, ev1 = run_loop(torch, dist, sc, dev, streams[:1], bufs, src, K, W, world, occluded, repeats)
+        # pass 2 (the reported value), fresh records: `inflight` batches in flight on as many streams
+        tN = t1
+        if nfl > 1:
+            if t1 is not None:
+                for s in range(nb):
+                    bufs[s].copy_(src[s])
+                torch.cuda.synchronize()
+            tN, _ = run_loop(torch, dist, sc, dev, streams, bufs, src, K, W, world, occluded, repeats)
+        # bufs[W] holds the trace of the first timed batch (restored and re-traced by every region, the same records each time)
         if occluded:
             hits = int(torch.isneginf(bufs[W].view(torch.float32)[:, 8]).sum().item())
         else:
             hits = int((bufs[W].view(torch.int32)[:, 18] != -1).sum().item())
-        # pass 2 (the reported value), fresh records: `inflight` batches in flight on as many streams
-        tN = t1
-        if nfl > 1:
-            for s in range(nb):
-                bufs[s].copy_(src[s])
-            torch.cuda.synchronize()
-            tN, _ = run_loop(torch, dist, sc, dev, streams, bufs, src, K, W, world, occluded, repeats)
-        # per repeat: MAX over ranks of the region, then the median / min / max of the repeats
-        worstN = [D.max_over_ranks(t, world, red_dev) for t in tN]
-        worst1 = [D.max_over_ranks(t, world, red_dev) for t in t1]
-        total_rays = D.sum_over_ranks(m * K, world, red_dev)
-        st = sc.stats()
+        # per repeat: MAX over ranks of the repeat's timed steps, then the median / min / max of the repeats
+        R.update(hits=hits, last=last, regionN=[D.max_over_ranks(t, world, red_dev) for t in tN], total_rays=D.sum_over_ranks(m * K, world, red_dev))
+        if not full:
+            return R
+        st = R["st"]
         rays = max(cnt["rays"], 1)
         n_node = cnt["nodeVisits"] / rays
         # leaf records visited per ray: triangle records tested, or subdivision leaves entered (grid cells / cBVH blobs)
         n_leaf = (cnt["primTests"] if st["accelKind"] in (1, 2) else cnt["leafVisits"]) / rays
         io_bytes = 48 + 4 if occluded else IO_BYTES_PER_RAY  # any hit: RTCRay read, tfar written
-        return {"dev": dev, "sc": sc, "cnt": cnt, "st": st, "hits": hits, "m": m, "K": K, "build_s": t_build,
-                "regionN": worstN, "region1": worst1, "kernel_ms": median(ev1), "kernel_ms_minmax": (min(ev1), max(ev1)),
-                "total_rays": total_rays, "n_node": n_node, "n_leaf": n_leaf, "n_inner": cnt["innerVisits"] / rays,
-                # implementation's own visits x record sizes; a subdiv leaf visit is priced at its whole record
-                "leaf_bytes": leaf_record_bytes(st, lv),
-                "bytes_per_ray": io_bytes + n_node * st["nodeBytes"] + n_leaf * leaf_record_bytes(st, lv),
-                "bytes_per_ray_addressed": addressed_bytes_per_ray(cnt, st, occluded, lv)}
+        R.update({"cnt": cnt, "region1": [D.max_over_ranks(t, world, red_dev) for t in t1], "kernel_ms": median(ev1), "kernel_ms_minmax": (min(ev1), max(ev1)),
+                  "n_node": n_node, "n_leaf": n_leaf, "n_inner": cnt["innerVisits"] / rays,
+                  # implementation's own visits x record sizes; a subdiv leaf visit is priced at its whole record
+                  "leaf_bytes": leaf_record_bytes(st, lv),
+                  "bytes_per_ray": io_bytes + n_node * st["nodeBytes"] + n_leaf * leaf_record_bytes(st, lv),
+                  "bytes_per_ray_addressed": addressed_bytes_per_ray(cnt, st, occluded, lv)})
+        return R
 
     def roofline_of(R, tag, traffic, traffic_src, with_profiles):
         kernel_ms = R["kernel_ms"]
@@ -438,13 +528,14 @@ def main():
 
     R = measure(args.workload, K, W)
     dev, sc, st, m = R["dev"], R["sc"], R["st"], R["m"]
-    medN, med1 = median(R["regionN"]), median(R["region1"])
+    medN = median(R["regionN"])
     rate = R["total_rays"] / medN
     metric_cfg = m == 1_000_000 and levels == (6, 3) and args.rays_kind == "random" and not occluded  # the committed profiles were taken on this exact workload
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, R["last"], occluded, rank, world)
 
     if rank == 0:
         _, _, _, tag, desc = WORKLOADS[args.workload]
-        traffic, traffic_src = pmc_traffic(tag, args.workload) if metric_cfg else (None, None)
         out = {
             "metric": "Mrays/s (incoherent) on bomberman displaced-subdiv scene, device-resident ray batches",
             "value": rate / 1e6,
@@ -461,10 +552,8 @@ def main():
             "repeats": len(R["regionN"]),
             "timed_ms_total": sum(R["regionN"]) * 1e3,
             "value_min_max": [R["total_rays"] / max(R["regionN"]) / 1e6, R["total_rays"] / min(R["regionN"]) / 1e6],
-            "value_note": f"median of {len(R['regionN'])} timed regions of exactly {K} steps each (barrier + synchronize on both sides of every region, MAX over ranks per region)",
-            "one_stream": {"value": R["total_rays"] / med1 / 1e6, "unit": "Mrays/s", "ms_per_step": med1 / K * 1e3, "repeats": len(R["region1"]),
-                           "value_min_max": [R["total_rays"] / max(R["region1"]) / 1e6, R["total_rays"] / min(R["region1"]) / 1e6],
-                           "note": "the same K steps strictly back-to-back on ONE stream: what a caller gets that does not keep several batches in flight"},
+            "value_note": f"median of {len(R['regionN'])} timed repeats of exactly {K} steps each, in regions of at most {REGION_STEPS} steps (barrier + "
+                          "synchronize on both sides of every region, MAX over ranks per repeat)",
             "config": {"workload": f"{args.workload}: {desc}; {m} "
                                    + {"random": "random incoherent rays per step (drand48 LCG, bbox-uniform endpoints), ",
                                       "primary": "coherent primary rays per step (config 4: 1920x1080, bomberman.ecs camera, 8x8 tile order), ",
@@ -475,25 +564,31 @@ def main():
                        "leaf_record_bytes": st["primBytes"], "accel_bytes": st["totalBytes"], "commit_seconds": R["build_s"], "hits_first_timed_batch": R["hits"],
                        "batches_in_flight": nfl,
                        "in_flight_note": (f"step s is enqueued on HIP stream s % {nfl}; value = K steps / wall time of the region; "
-                                          "see one_stream for the strictly back-to-back rate") if nfl > 1 else "one stream, strictly back-to-back",
+                                          "see one_stream (--full) for the strictly back-to-back rate") if nfl > 1 else "one stream, strictly back-to-back",
                        "sharding": f"replicated accel, {world} independent ray shards, no collective"
                                    + ("; device-resident, process-per-GPU batches are the only path that can scale near-linearly: ONE host-pointer call "
                                       "through rtcNewDevice(\"gpus=...\") is bound by the caller's gather / scatter (345 Mrays/s per process, DESIGN.md)" if world > 1 else "")},
-            "roofline": roofline_of(R, tag, traffic, traffic_src, metric_cfg),
         }
-        out["roofline"]["in_flight_profile"] = inflight_profile(args.workload) if metric_cfg else None
-        if world == 1 and args.rays_kind == "random" and not occluded and not args.no_pcie:
-            out["config"]["pcie_inclusive_Mrays"] = pcie_inclusive(sc, raygen, D, m, lo, hi, rank)
-            out["config"]["pcie_inclusive_note"] = ("one rtcIntersect1M call on pageable HOST records, best of 3: chunked pipeline of gather into pinned memory "
-                                                    "(host thread pool) / H2D / traversal / D2H on two alternating streams / scatter of tfar + hit "
-                                                    "(rt_trace.cpp trace_host_pipelined); `value` is the device-resident rate")
-    if world == 1 and args.cpu_seconds > 0:
+        if args.full:
+            med1 = median(R["region1"])
+            traffic, traffic_src = pmc_traffic(tag, args.workload) if metric_cfg else (None, None)
+            out["one_stream"] = {"value": R["total_rays"] / med1 / 1e6, "unit": "Mrays/s", "ms_per_step": med1 / K * 1e3, "repeats": len(R["region1"]),
+                                 "value_min_max": [R["total_rays"] / max(R["region1"]) / 1e6, R["total_rays"] / min(R["region1"]) / 1e6],
+                                 "note": "the same K steps strictly back-to-back on ONE stream: what a caller gets that does not keep several batches in flight"}
+            out["roofline"] = roofline_of(R, tag, traffic, traffic_src, metric_cfg)
+            out["roofline"]["in_flight_profile"] = inflight_profile(args.workload) if metric_cfg else None
+            if world == 1 and args.rays_kind == "random" and not occluded and not args.no_pcie:
+                out["config"]["pcie_inclusive_Mrays"] = pcie_inclusive(sc, raygen, D, m, lo, hi, rank)
+                out["config"]["pcie_inclusive_note"] = ("one rtcIntersect1M call on pageable HOST records, best of 3: chunked pipeline of gather into pinned memory "
+                                                        "(host thread pool) / H2D / traversal / D2H on two alternating streams / scatter of tfar + hit "
+                                                        "(rt_trace.cpp trace_host_pipelined); `value` is the device-resident rate")
+    if args.full and world == 1 and args.cpu_seconds > 0:
         out["cpu_baseline"] = cpu_baseline(sc, rtc, args.workload, mesh, levels, lo, hi, m, args.cpu_seconds)
     sc.release()
     dev.release()
     del R
 
-    default_line = world == 1 and args.workload == "cbvh.leaf" and metric_cfg
+    default_line = args.full and world == 1 and args.workload == "cbvh.leaf" and metric_cfg
     if default_line and not args.no_others:
         others = {}
         for w2 in ("tri", "eager"):

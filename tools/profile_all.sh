@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 for w in ${PROF_WORKLOADS:-cbvh.leaf tri}; do
   O=$R/gpurun_out/prof_$w${PROF_SUFFIX}
   rm -rf $O && mkdir -p $O
-  A="--workload $w --inflight 1 --cpu-seconds 0 --no-others --no-pcie --scaled-levels none --repeats 1 --steps 20 --warmup 3 $PROF_ARGS"
+  A="--workload $w --inflight 1 --full --cpu-seconds 0 --no-others --no-pcie --scaled-levels none --repeats 1 --steps 20 --warmup 3 $PROF_ARGS"
   echo "== $w: kernel trace"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py $A > $O/bench_trace.json 2> $O/trace.err
   echo "== $w: FETCH_SIZE"
@@ -29,7 +29,7 @@ for w in ${PROF_WORKLOADS:-cbvh.leaf tri}; do
     # the mode `value` is measured in: four batches in flight on four streams (kernel trace only: counter collection would
     # serialise the dispatches)
     echo "== $w: kernel trace, 4 batches in flight"
-    timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_if4 -- python3 $R/bench.py --workload $w --inflight 4 --cpu-seconds 0 --no-others --no-pcie --scaled-levels none --repeats 1 --steps 40 --warmup 4 $PROF_ARGS > $O/bench_if4.json 2> $O/if4.err
+    timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_if4 -- python3 $R/bench.py --workload $w --inflight 4 --full --cpu-seconds 0 --no-others --no-pcie --scaled-levels none --repeats 1 --steps 40 --warmup 4 $PROF_ARGS > $O/bench_if4.json 2> $O/if4.err
     python3 $R/tools/summarize_inflight.py $O/trace_if4 ${P}_inflight.json 40
     cp $O/bench_if4.json ${P}_inflight_bench.json
   fi

@@ -35,7 +35,7 @@ fi
 for set in "${SETS[@]}"; do
   i=$((i+1))
   echo "== pass $i: $set" >> $O/summary.txt
-  if timeout -k 10 150 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/p$i -- python3 $R/bench.py --workload $W "$@" --inflight 1 --steps 6 --warmup 2 --repeats 1 --cpu-seconds 0 --no-others --no-pcie --scaled-levels none > $O/log_$i.txt 2>&1; then
+  if timeout -k 10 150 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/p$i -- python3 $R/bench.py --workload $W "$@" --inflight 1 --steps 6 --warmup 2 --repeats 1 --full --cpu-seconds 0 --no-others --no-pcie --scaled-levels none > $O/log_$i.txt 2>&1; then
     python3 $R/tools/sq_summary.py $O/p$i >> $O/summary.txt
   else
     echo "pass failed (rc $?); end of its log (kept whole as log_$i.txt next to this file):" >> $O/summary.txt

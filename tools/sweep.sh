@@ -8,7 +8,7 @@
 #   tools/sweep.sh workloads                                            cbvh.leaf / eager / tri on the default build
 # BENCH_ARGS adds bench.py arguments to every run (e.g. BENCH_ARGS="--levels 8,3" or "--inflight 2").
 mode=$1; shift
-COMMON="--cpu-seconds 0 --no-others --no-pcie --scaled-levels none ${BENCH_ARGS}"
+COMMON="--full --cpu-seconds 0 --no-others --no-pcie --scaled-levels none ${BENCH_ARGS}"
 fmt='import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print("in flight %8.0f Mrays/s [%.0f..%.0f] | one stream %8.0f | alone %.4f ms (frac %.3f) | nodes/ray %.2f leaves/ray %.3f" % (d["value"], d["value_min_max"][0], d["value_min_max"][1], d["one_stream"]["value"], r["kernel_ms"], r["frac"], r["nodes_per_ray"], r["leaf_visits_per_ray"]))'
 run() { python3 bench.py "$@" $COMMON 2>/dev/null | python3 -c "$fmt"; }
 case $mode in

@@ -3,7 +3,8 @@
 // Everything the kernels read lives in four flat HBM arrays per committed scene:
 //   nodes   : QNode8[]       96-byte quantized BVH8 nodes, index 0 = root (if the root is inner)
 //   prims   : TriRecord[]    48-byte triangle records (v0,v1,v2 or v0,e1,e2 + ids), leaf-contiguous
-//   blobs   : bytes          cBVH / GridSOA leaf blobs for subdivision geometry (16-byte aligned each)
+//   blobs   : bytes          cBVH / GridSOA leaf blobs for subdivision geometry (16-byte aligned each),
+//                            or QuadRecord[] (64-byte quad records, leaf-contiguous) for quad geometry
 // The reference keeps the same information behind 64-bit tagged pointers (kernels/bvh/bvh.h:150-396,
 // AlignedNode :433-594, QuantizedNode :1150-1324, Triangle4v kernels/geometry/trianglev.h:24-162).
 #pragma once
@@ -19,6 +20,7 @@ namespace rtamd {
 // bit 31      : leaf flag
 // inner       : bits 0..30 = node index
 // triangle leaf: bits 26..30 = triangle count (1..28, i.e. up to 7 blocks of 4 like bvh.h:140), bits 0..25 = first record
+// quad leaf   : the same form, counting quads
 // subdiv leaf : bits 0..30 = blob index (one blob per leaf, like encodeTypedLeaf(ptr,1) bvh_builder_subdiv.cpp:728)
 static const uint32_t REF_EMPTY = 0xFFFFFFFFu; // no child (reference: BVH::emptyNode, bvh.h:117-132)
 static const uint32_t REF_LEAF = 0x80000000u;
@@ -60,6 +62,23 @@ struct alignas(16) TriRecord
   uint32_t pad;
 };
 static_assert(sizeof(TriRecord) == 48, "TriRecord must be 48 bytes");
+
+// ---- quad record, 64 bytes = 4 x dwordx4 ---------------------------------------------------------------------
+// The four vertices as given (QuadMv, quadv.h); both accels (Pluecker / Moeller) read the same record and split the quad into
+// triangle A = (v0, v1, v3) and B = (v2, v1, v3) at run time.  Every group of 4 records from the leaf start is one block of 4 quads =
+// one 8-wide block of triangles (the reference's AVX form, quad_intersector_pluecker.h:264-299).
+struct alignas(16) QuadRecord
+{
+  float v0x, v0y, v0z;
+  uint32_t geomID;
+  float v1x, v1y, v1z;
+  uint32_t primID;
+  float v2x, v2y, v2z;
+  uint32_t pad0;
+  float v3x, v3y, v3z;
+  uint32_t pad1;
+};
+static_assert(sizeof(QuadRecord) == 64, "QuadRecord must be 64 bytes");
 
 // ---- eager subdivision leaf: one 3x3-vertex cell (2x2 quads = 8 triangles), 160 bytes = 10 x dwordx4 ------
 // Replaces the inner leaves of GridSOA (kernels/geometry/grid_soa.h:267-286, :85-90): the reference stores whole
@@ -138,7 +157,9 @@ enum AccelKind : uint32_t
   ACCEL_CBVH_LEAF = 4,    // subdiv_accel=bvh4.compressed.leaf
   ACCEL_CBVH_GRID = 5,    // subdiv_accel=bvh4.compressed.grid
   ACCEL_GRIDSOA = 6,      // eager subdiv (default subdiv accel)
-  ACCEL_CBVH_FULL = 7     // subdiv_accel=bvh4.compressed.full: the fork's box mode over UNcompressed quadtree nodes (compressed.h:40,774)
+  ACCEL_CBVH_FULL = 7,    // subdiv_accel=bvh4.compressed.full: the fork's box mode over UNcompressed quadtree nodes (compressed.h:40,774)
+  ACCEL_QUAD_PLUECKER = 8, // quad_accel=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:251-330): QuadMv + Pluecker, robust traversal
+  ACCEL_QUAD_MOELLER = 9   // quad_accel=default / bvh8.quad4v / bvh4.quad4v / *.quad4i: QuadMv + Moeller, fast traversal
 };
 
 // What a kernel launch needs to know about one committed scene.
@@ -146,7 +167,7 @@ struct AccelDesc
 {
   const QNode8* nodes;
   const TriRecord* prims;
-  const uint8_t* blobs;
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind
@@ -165,7 +186,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (two launches per batch: triangles, subdiv)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (up to three launches per batch: triangles, quads, subdiv)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

@@ -37,6 +37,7 @@ void Device::parse(const std::string& cfg)
     if (key.empty()) continue;
     if (key == "tri_accel" || key == "accel") tri_accel = val;
     else if (key == "subdiv_accel") subdiv_accel = val;
+    else if (key == "quad_accel") { quad_accel = val; quadAccelNamed = true; }
     else if (key == "verbose") verbose = atoi(val.c_str());
     else if (key == "gpu" || key == "device") { gpu = (val == "none") ? -1 : atoi(val.c_str()); gpuList.clear(); }
     else if (key == "gpus") {
@@ -118,7 +119,7 @@ Device::Device(const char* cfg)
     sh->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     HIP_CHECK(hipStreamCreateWithFlags(&sh->stream, hipStreamNonBlocking));
     sh->ownsStream = true;
-    HIP_CHECK(hipMalloc(&sh->countersDev, 2 * (size_t)WAVE_LOG_CAPACITY * sizeof(WaveRecord)));
+    HIP_CHECK(hipMalloc(&sh->countersDev, 3 * (size_t)WAVE_LOG_CAPACITY * sizeof(WaveRecord))); // triangle, subdiv, quad launches
     HIP_CHECK(hipHostMalloc((void**)&sh->overflowHost, 64, hipHostMallocMapped));
     *sh->overflowHost = 0u;
     HIP_CHECK(hipHostGetDevicePointer((void**)&sh->overflowDev, sh->overflowHost, 0));
@@ -127,8 +128,8 @@ Device::Device(const char* cfg)
       HIP_CHECK(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
     }
     if (verbose >= 1)
-      fprintf(stderr, "embree3-amd: shard %zu on device %d (%s, %d CUs), tri_accel=%s subdiv_accel=%s\n", shards.size(), g, prop.name, sh->numCUs,
-              tri_accel.c_str(), subdiv_accel.c_str());
+      fprintf(stderr, "embree3-amd: shard %zu on device %d (%s, %d CUs), tri_accel=%s subdiv_accel=%s quad_accel=%s\n", shards.size(), g, prop.name, sh->numCUs,
+              tri_accel.c_str(), subdiv_accel.c_str(), quad_accel.c_str());
     shards.push_back(std::move(sh));
   }
   HIP_CHECK(hipSetDevice(gpu));

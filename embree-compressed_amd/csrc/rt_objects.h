@@ -26,6 +26,8 @@ struct Device : RefCounted
   // config (reference: State::parse, kernels/common/state.cpp:241-430)
   std::string tri_accel = "default";
   std::string subdiv_accel = "default";
+  std::string quad_accel = "default";
+  bool quadAccelNamed = false; // "quad_accel=" given (a host-only device takes quad geometry only then, quads_enabled())
   int verbose = 0;
   int gpu = 0;            // HIP device ordinal ("gpu=" key; falls back to env RTAMD_GPU, LOCAL_RANK is NOT read here)
   int numThreads = 0;     // accepted, used only for host-side builders
@@ -191,6 +193,10 @@ struct Device : RefCounted
   RTCError takeError();
   void useDevice() const; // hipSetDevice(first shard) for the calling thread; throws on a gpu=none device
   void synchronize();     // all shards' streams; raises a pending stack-overflow report
+  // Quad meshes are traced by the GPU kernels (trace_quad.hip): every device with a GPU takes them.  A host-only device (gpu=none) keeps
+  // the geometry set of the host object model as it was - RTC_GEOMETRY_TYPE_QUAD raises INVALID_OPERATION there, as in a build without
+  // the feature - unless its config names a quad accel (quad_accel=...), which builds quad scenes for inspection.
+  bool quads_enabled() const { return gpu >= 0 || quadAccelNamed; }
   bool tuneBlocksAuto = true; // no RTAMD_BLOCKS_PER_CU given: 2 workgroups per CU, 1 when >= 2 batches run on other streams
   void memoryMonitor(ssize_t bytes, bool post);
 };
@@ -267,6 +273,10 @@ struct Geometry : RefCounted
   void triangle(size_t i, unsigned idx[3]) const;
   V3 vertex(size_t i) const;
   bool validTriangle(size_t i) const;
+  // quad mesh accessors (reference: QuadMesh, kernels/common/scene_quad_mesh.h)
+  size_t numQuads() const { return numTriangles(); } // index buffer records (UINT4 for quads)
+  void quad(size_t i, unsigned idx[4]) const;
+  bool validQuad(size_t i) const;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -314,7 +324,7 @@ struct Scene : RefCounted
   void* progressUser = nullptr;
   bool modified = true; // "scene got not committed" until the first commit (scene.cpp:25,54)
   // filter callbacks present at commit time (Scene::hasGeometryFilterFunction, scene.h): they route a batch through the
-  // host filter loop of rt_trace.cpp
+  // host filter loop of rt_trace.cpp (the tri* flags cover quad meshes too)
   bool triIntersectFilter = false, triOccludedFilter = false, subdivFilter = false;
   std::mutex buildMutex;
   Box3 bounds;
@@ -322,6 +332,7 @@ struct Scene : RefCounted
   std::vector<uint8_t> debugGrids; // keep_grids=1: per patch {geomID,primID,n} + x[],y[],z[] of the (n+1)^2 grid
 
   Accel triAccel;    // triangles
+  Accel quadAccel;   // quads (QuadRecord[] in `blobs`); traced after the triangles, before the subdivision patches (scene.cpp:650-654)
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
 
   explicit Scene(Device* d);

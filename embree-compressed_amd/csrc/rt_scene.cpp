@@ -58,6 +58,15 @@ void Geometry::bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size
     } else if (t != RTC_BUFFER_TYPE_VERTEX_ATTRIBUTE)
       RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown buffer type");
     break;
+  case RTC_GEOMETRY_TYPE_QUAD: // QuadMesh::setBuffer (scene_quad_mesh.cpp)
+    if (t == RTC_BUFFER_TYPE_VERTEX) {
+      if (f != RTC_FORMAT_FLOAT3) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid vertex buffer format");
+    } else if (t == RTC_BUFFER_TYPE_INDEX) {
+      if (slot != 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid buffer slot");
+      if (f != RTC_FORMAT_UINT4) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid index buffer format");
+    } else if (t != RTC_BUFFER_TYPE_VERTEX_ATTRIBUTE)
+      RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown buffer type");
+    break;
   case RTC_GEOMETRY_TYPE_SUBDIVISION:
     if (t == RTC_BUFFER_TYPE_VERTEX && f != RTC_FORMAT_FLOAT3) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid vertex buffer format");
     if ((t == RTC_BUFFER_TYPE_INDEX || t == RTC_BUFFER_TYPE_FACE) && f != RTC_FORMAT_UINT)
@@ -102,6 +111,27 @@ bool Geometry::validTriangle(size_t i) const
   const size_t nv = numVertices();
   if (idx[0] >= nv || idx[1] >= nv || idx[2] >= nv) return false;
   for (int k = 0; k < 3; k++) {
+    V3 p = vertex(idx[k]);
+    if (!(std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z))) return false;
+    if (fabsf(p.x) > 1.844e18f || fabsf(p.y) > 1.844e18f || fabsf(p.z) > 1.844e18f) return false; // FLT_LARGE
+  }
+  return true;
+}
+
+void Geometry::quad(size_t i, unsigned idx[4]) const
+{
+  const unsigned* p = (const unsigned*)view(RTC_BUFFER_TYPE_INDEX, 0)->at(i);
+  idx[0] = p[0]; idx[1] = p[1]; idx[2] = p[2]; idx[3] = p[3];
+}
+
+// QuadMesh::valid (scene_quad_mesh.h:121-138): all four indices in range and finite vertices
+bool Geometry::validQuad(size_t i) const
+{
+  unsigned idx[4];
+  quad(i, idx);
+  const size_t nv = numVertices();
+  for (int k = 0; k < 4; k++) {
+    if (idx[k] >= nv) return false;
     V3 p = vertex(idx[k]);
     if (!(std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z))) return false;
     if (fabsf(p.x) > 1.844e18f || fabsf(p.y) > 1.844e18f || fabsf(p.z) > 1.844e18f) return false; // FLT_LARGE
@@ -198,6 +228,7 @@ Scene::~Scene()
 {
   service_quiesce(device); // freeing device memory synchronises the device: do not wait for the resident service kernel's idle exit
   triAccel.freeDevice();
+  quadAccel.freeDevice();
   subdivAccel.freeDevice();
   if (device->gpu >= 0) hipSetDevice(device->gpu);
   for (Geometry* g : geometries)
@@ -309,6 +340,77 @@ static void build_triangle_accel(Scene* s)
   for (const BuildPrim& p : bp) s->bounds.extend(p.box);
 }
 
+// Quad meshes: one BVH8 over whole quads with the triangle settings; the records keep the four vertices (QuadMv) and go to the
+// accel's byte array.  Accel choice (scene.cpp:251-330, bvh8_factory.h:43): default = Pluecker + robust traversal for a robust scene,
+// Moeller + fast traversal otherwise; an explicit quad4v / quad4i accel is the fast (Moeller) variant.
+static void build_quad_accel(Scene* s)
+{
+  Device* dev = s->device;
+  Accel& A = s->quadAccel;
+  A.clear();
+  const std::string& name = dev->quad_accel;
+  bool pluecker;
+  if (name == "default") pluecker = s->isRobust();
+  else if (name == "bvh8.quad4v" || name == "bvh4.quad4v" || name == "bvh8.quad4i" || name == "bvh4.quad4i" || name == "qbvh8.quad4i") pluecker = false;
+  else RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown quad acceleration structure " + name);
+
+  struct Src { unsigned geomID, primID; };
+  std::vector<Src> src;
+  std::vector<BuildPrim> bp;
+  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
+    Geometry* g = s->geometries[gid];
+    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_QUAD) continue;
+    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry is not supported by the device path");
+    const size_t nq = g->numQuads();
+    for (size_t i = 0; i < nq; i++) {
+      if (!g->validQuad(i)) continue;
+      unsigned idx[4];
+      g->quad(i, idx);
+      BuildPrim p;
+      for (int k = 0; k < 4; k++) p.box.extend(g->vertex(idx[k]));
+      p.id = (uint32_t)src.size();
+      src.push_back({gid, (unsigned)i});
+      bp.push_back(p);
+    }
+  }
+  if (bp.empty()) return;
+  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many quads for the 26-bit leaf reference");
+  A.kind = pluecker ? ACCEL_QUAD_PLUECKER : ACCEL_QUAD_MOELLER;
+  A.robust = pluecker ? 1 : 0;
+  A.blobStride = sizeof(QuadRecord);
+
+  std::vector<QuadRecord> recs;
+  recs.reserve(bp.size());
+  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
+    const uint32_t first = (uint32_t)recs.size();
+    for (size_t i = begin; i < end; i++) {
+      const Src& sr = src[prims[i].id];
+      Geometry* g = s->geometries[sr.geomID];
+      unsigned idx[4];
+      g->quad(sr.primID, idx);
+      const V3 v0 = g->vertex(idx[0]), v1 = g->vertex(idx[1]), v2 = g->vertex(idx[2]), v3 = g->vertex(idx[3]);
+      QuadRecord q;
+      memset(&q, 0, sizeof(q));
+      q.v0x = v0.x; q.v0y = v0.y; q.v0z = v0.z; q.geomID = sr.geomID;
+      q.v1x = v1.x; q.v1y = v1.y; q.v1z = v1.z; q.primID = sr.primID;
+      q.v2x = v2.x; q.v2y = v2.y; q.v2z = v2.z;
+      q.v3x = v3.x; q.v3y = v3.y; q.v3z = v3.z;
+      recs.push_back(q);
+    }
+    return make_tri_leaf(first, (uint32_t)(end - begin));
+  };
+  BuildSettings cfg; // the triangle settings: block 4, min leaf 4, max leaf 28
+  cfg.threads = host_threads(s->device);
+  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
+  A.nodes = std::move(r.nodes);
+  A.root = r.root;
+  A.maxDepth = r.maxDepth;
+  A.leafCount = r.leafCount;
+  A.blobs.resize(recs.size() * sizeof(QuadRecord));
+  memcpy(A.blobs.data(), recs.data(), A.blobs.size());
+  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+}
+
 void Scene::commit()
 {
   std::lock_guard<std::mutex> g(buildMutex);
@@ -317,6 +419,7 @@ void Scene::commit()
     if (!geo || !geo->enabled) continue;
     switch (geo->type) {
     case RTC_GEOMETRY_TYPE_TRIANGLE:
+    case RTC_GEOMETRY_TYPE_QUAD:
     case RTC_GEOMETRY_TYPE_SUBDIVISION: break;
     default: // scene.cpp:25-30: geometry types compiled out raise INVALID_OPERATION
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry type not supported by the MI355X traversal path");
@@ -325,7 +428,7 @@ void Scene::commit()
   triIntersectFilter = triOccludedFilter = subdivFilter = false;
   for (Geometry* geo : geometries) {
     if (!geo || !geo->enabled) continue;
-    if (geo->type == RTC_GEOMETRY_TYPE_TRIANGLE) {
+    if (geo->type == RTC_GEOMETRY_TYPE_TRIANGLE || geo->type == RTC_GEOMETRY_TYPE_QUAD) {
       triIntersectFilter |= geo->intersectFilter != nullptr;
       triOccludedFilter |= geo->occludedFilter != nullptr;
     } else
@@ -334,14 +437,19 @@ void Scene::commit()
   if (progressFn && !progressFn(progressUser, 0.0)) RT_THROW(RTC_ERROR_CANCELLED, "progress monitor forced termination");
   bounds = Box3();
   build_triangle_accel(this);
+  build_quad_accel(this);
   build_subdiv_accel(this);
   triAccel.upload(device);
+  quadAccel.upload(device);
   subdivAccel.upload(device);
   if (progressFn) progressFn(progressUser, 1.0);
   if (device->verbose >= 2) {
     fprintf(stderr, "embree3-amd: tri accel kind %u: %zu nodes (%zu B), %zu tris, depth %u; subdiv accel kind %u: %zu nodes, %zu blobs (%zu B)\n",
             triAccel.kind, triAccel.nodes.size(), triAccel.nodes.size() * sizeof(QNode8), triAccel.prims.size(), triAccel.maxDepth,
             subdivAccel.kind, subdivAccel.nodes.size(), subdivAccel.blobOffsets.size(), subdivAccel.blobs.size());
+    if (quadAccel.kind != ACCEL_NONE)
+      fprintf(stderr, "embree3-amd: quad accel kind %u: %zu nodes (%zu B), %zu quads (%zu B), depth %u\n", quadAccel.kind, quadAccel.nodes.size(),
+              quadAccel.nodes.size() * sizeof(QNode8), quadAccel.blobs.size() / sizeof(QuadRecord), quadAccel.blobs.size(), quadAccel.maxDepth);
   }
   modified = false;
 }

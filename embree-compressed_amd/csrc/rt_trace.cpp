@@ -72,6 +72,7 @@ static void launch_on(Scene* s, const Accel& A, size_t si, void* dRays, uint32_t
   // Ray-pool skeleton for very large batches - where it still pays.  Since the two-stage blob visits and the batched leaf passes of round 3 the lane
   // kernel is the faster one at EVERY size for grid cells and the cBVH box / leaf / full modes (4 M rays, one stream: cbvh.leaf 12.0 vs 10.2 Grays/s,
   // eager 6 M 14.5 vs 10.7); the pool keeps triangles (6 M: 16.8 vs 14.8) and the cBVH grid mode (11.0 vs 8.3).  profiles/r03_lane_pool_ab.txt
+  // (quad leaves stay on the lane kernel unless RTAMD_KERNEL=pool: not measured)
   const bool poolPays = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER || A.kind == ACCEL_CBVH_GRID;
   p.poolKernel = dev->tunePoolKernel == 2u ? (poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel;
   // worst-case stack: 7 siblings per level plus the entry being expanded.  The overflow area is sized for it, so a push
@@ -179,6 +180,8 @@ static void launch_on(Scene* s, const Accel& A, size_t si, void* dRays, uint32_t
 //    a candidate is identified by (geomID, primID, bits of t) - kernels are deterministic, the same triangle gives the same t
 //    when the ray is traced again.  Two triangles of one patch hit at a bit-identical distance (a ray through their shared edge)
 //    are rejected together, where the reference would offer both.
+//  * quads (QuadMvIntersector1*<4,true>, filter = true) offer each triangle with the QUAD's geomID / primID: identified like grid cells
+//    by (geomID, primID, bits of t); a ray through the diagonal v1-v3 hits both triangles at one t, and rejecting one rejects both.
 //  * the fork's compressed modes never call a filter: CompressedBVHIntersector1::intersect writes the hit itself and occluded()
 //    is a stub (compressed.h:454-756, no runIntersectionFilter1 anywhere in compressed*.h).  Hits on such an accel are accepted
 //    without a callback, geometry and context filter alike; for any-hit queries the stub pass runs first, unfiltered.
@@ -240,9 +243,10 @@ static void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, 
     act.swap(rest);
   }
   struct Rejected { uint32_t geomID, primID, tbits; };
-  std::vector<std::vector<Rejected>> exclTri(M), exclSub(M);
-  std::vector<uint32_t> offT, offS, tS, next;
-  std::vector<uint2> pairsT, pairsS;
+  std::vector<std::vector<Rejected>> exclTri(M), exclSub(M), exclQuad(M);
+  std::vector<uint32_t> offT, offS, tS, offQ, tQ, next;
+  std::vector<uint2> pairsT, pairsS, pairsQ;
+  const bool haveQuads = s->quadAccel.kind != ACCEL_NONE && s->quadAccel.root != REF_EMPTY;
   void* dExcl = nullptr;
   size_t dExclBytes = 0;
   auto freeExcl = [&]() { if (dExcl) hipFree(dExcl); dExcl = nullptr; };
@@ -256,21 +260,30 @@ static void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, 
       offT.assign(K + 1, 0);
       offS.assign(K + 1, 0);
       pairsT.clear(); pairsS.clear(); tS.clear();
+      if (haveQuads) { offQ.assign(K + 1, 0); pairsQ.clear(); tQ.clear(); }
       for (uint32_t k = 0; k < K; k++) {
         h[k] = W[act[k]];
         offT[k] = (uint32_t)pairsT.size();
         offS[k] = (uint32_t)pairsS.size();
         for (const Rejected& e : exclTri[act[k]]) pairsT.push_back(make_uint2(e.geomID, e.primID));
         for (const Rejected& e : exclSub[act[k]]) { pairsS.push_back(make_uint2(e.geomID, e.primID)); tS.push_back(e.tbits); }
+        if (haveQuads) {
+          offQ[k] = (uint32_t)pairsQ.size();
+          for (const Rejected& e : exclQuad[act[k]]) { pairsQ.push_back(make_uint2(e.geomID, e.primID)); tQ.push_back(e.tbits); }
+        }
       }
       offT[K] = (uint32_t)pairsT.size();
       offS[K] = (uint32_t)pairsS.size();
+      if (haveQuads) offQ[K] = (uint32_t)pairsQ.size();
       const uint32_t *dOffT = nullptr, *dOffS = nullptr, *dTS = nullptr;
       const uint2 *dPairsT = nullptr, *dPairsS = nullptr;
-      if (!pairsT.empty() || !pairsS.empty()) {
+      const uint32_t *dOffQ = nullptr, *dTQ = nullptr;
+      const uint2* dPairsQ = nullptr;
+      if (!pairsT.empty() || !pairsS.empty() || !pairsQ.empty()) {
         const size_t offBytes = a16((size_t)(K + 1) * 4);
-        const size_t oPT = 2 * offBytes, oPS = oPT + a16(pairsT.size() * sizeof(uint2)), oTS = oPS + a16(pairsS.size() * sizeof(uint2));
-        const size_t need = oTS + a16(tS.size() * 4);
+        const size_t oPT = 3 * offBytes, oPS = oPT + a16(pairsT.size() * sizeof(uint2)), oTS = oPS + a16(pairsS.size() * sizeof(uint2));
+        const size_t oPQ = oTS + a16(tS.size() * 4), oTQ = oPQ + a16(pairsQ.size() * sizeof(uint2));
+        const size_t need = oTQ + a16(tQ.size() * 4);
         if (need > dExclBytes) {
           HIP_CHECK(hipStreamSynchronize(sh.stream));
           freeExcl();
@@ -292,9 +305,18 @@ static void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, 
           dPairsS = (const uint2*)(D + oPS);
           dTS = (const uint32_t*)(D + oTS);
         }
+        if (!pairsQ.empty()) {
+          HIP_CHECK(hipMemcpyAsync(D + 2 * offBytes, offQ.data(), (size_t)(K + 1) * 4, hipMemcpyHostToDevice, sh.stream));
+          HIP_CHECK(hipMemcpyAsync(D + oPQ, pairsQ.data(), pairsQ.size() * sizeof(uint2), hipMemcpyHostToDevice, sh.stream));
+          HIP_CHECK(hipMemcpyAsync(D + oTQ, tQ.data(), tQ.size() * 4, hipMemcpyHostToDevice, sh.stream));
+          dOffQ = (const uint32_t*)(D + 2 * offBytes);
+          dPairsQ = (const uint2*)(D + oPQ);
+          dTQ = (const uint32_t*)(D + oTQ);
+        }
       }
       HIP_CHECK(hipMemcpyAsync(sh.stageDev, h, bytes, hipMemcpyHostToDevice, sh.stream));
       launch_on(s, s->triAccel, 0, sh.stageDev, K, (uint32_t)sizeof(RTCRayHit), false, instID, nullptr, dOffT, dPairsT);
+      launch_on(s, s->quadAccel, 0, sh.stageDev, K, (uint32_t)sizeof(RTCRayHit), false, instID, nullptr, dOffQ, dPairsQ, nullptr, false, dTQ);
       if (!(occluded && forkAccel))
         launch_on(s, s->subdivAccel, 0, sh.stageDev, K, (uint32_t)sizeof(RTCRayHit), false, instID, nullptr, dOffS, dPairsS, nullptr, false, dTS);
       HIP_CHECK(hipMemcpyAsync(h, sh.stageDev, bytes, hipMemcpyDeviceToHost, sh.stream));
@@ -335,7 +357,8 @@ static void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, 
         } else {
           uint32_t tb;
           memcpy(&tb, &got.ray.tfar, 4);
-          (onSubdiv ? exclSub : exclTri)[i].push_back(Rejected{got.hit.geomID, got.hit.primID, tb});
+          const bool onQuad = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD;
+          (onSubdiv ? exclSub : (onQuad ? exclQuad : exclTri))[i].push_back(Rejected{got.hit.geomID, got.hit.primID, tb});
           next.push_back(i);
         }
       }
@@ -435,6 +458,7 @@ static void trace_host_pipelined(Scene* s, char* rays, uint32_t M, size_t byteSt
       const size_t bytes = (size_t)(b - a) * rec;
       HIP_CHECK(hipMemcpyAsync(d, h + (size_t)a * rec, bytes, hipMemcpyHostToDevice, st));
       launch_on(s, s->triAccel, L.g, d, b - a, rec, occluded, instID, nullptr, nullptr, nullptr, nullptr, coherent, nullptr, st);
+      launch_on(s, s->quadAccel, L.g, d, b - a, rec, occluded, instID, nullptr, nullptr, nullptr, nullptr, coherent, nullptr, st);
       launch_on(s, s->subdivAccel, L.g, d, b - a, rec, occluded, instID, nullptr, nullptr, nullptr, nullptr, coherent, nullptr, st);
       HIP_CHECK(hipMemcpyAsync(h + (size_t)a * rec, d, bytes, hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipEventRecord(L.sh->pipeEvents[k], st));
@@ -487,19 +511,23 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
   const bool coherent = ctx && (ctx->flags & RTC_INTERSECT_CONTEXT_FLAG_COHERENT);
   const uint32_t rec = occluded ? (uint32_t)sizeof(RTCRay) : (uint32_t)sizeof(RTCRayHit);
 
-  // instrumented twin: every wavefront stores one WaveRecord; first half of the log = triangle launch, second = subdiv.
-  // Counted batches run on ONE shard (the first, or the one the device pointer lives on) and one at a time.
+  // instrumented twin: every wavefront stores one WaveRecord; first slice of the log = triangle launch, second = subdiv, third = quads
+  // (present only for scenes with quads). Counted batches run on ONE shard (the first, or the one the device pointer lives on) and one at a time.
   WaveRecord* dCounters = nullptr;
   WaveRecord* dCounters2 = nullptr;
-  const size_t logBytes = 2 * (size_t)WAVE_LOG_CAPACITY * sizeof(WaveRecord);
+  WaveRecord* dCounters3 = nullptr;
+  const bool haveQuads = s->quadAccel.kind != ACCEL_NONE && s->quadAccel.root != REF_EMPTY;
+  const size_t logSlices = haveQuads ? 3 : 2;
+  const size_t logBytes = logSlices * (size_t)WAVE_LOG_CAPACITY * sizeof(WaveRecord);
   std::unique_lock<std::mutex> countLock(dev->launchMutex, std::defer_lock);
   size_t countShard = 0;
-  std::vector<uint32_t> cullWords; // counted batches: queue words of the triangle launch, then of the subdivision launch
-  uint32_t *cull1 = nullptr, *cull2 = nullptr;
+  std::vector<uint32_t> cullWords; // counted batches: queue words of the triangle launch, then of the subdivision launch, then of the quad launch
+  uint32_t *cull1 = nullptr, *cull2 = nullptr, *cull3 = nullptr;
   if (countersOut) {
-    cullWords.assign(2 * (size_t)TRACE_QUEUES * TRACE_QUEUE_STRIDE, 0u);
+    cullWords.assign(3 * (size_t)TRACE_QUEUES * TRACE_QUEUE_STRIDE, 0u);
     cull1 = cullWords.data();
     cull2 = cull1 + (size_t)TRACE_QUEUES * TRACE_QUEUE_STRIDE;
+    cull3 = cull2 + (size_t)TRACE_QUEUES * TRACE_QUEUE_STRIDE;
   }
 
   const int ptrDev = pointer_device(rays);
@@ -517,9 +545,11 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
       countShard = si;
       dCounters = (WaveRecord*)sh.countersDev;
       dCounters2 = dCounters + WAVE_LOG_CAPACITY;
+      dCounters3 = haveQuads ? dCounters2 + WAVE_LOG_CAPACITY : nullptr;
       HIP_CHECK(hipMemsetAsync(dCounters, 0, logBytes, sh.stream));
     }
     launch_on(s, s->triAccel, si, rays, M, (uint32_t)byteStride, occluded, instID, dCounters, nullptr, nullptr, cull1, coherent);
+    launch_on(s, s->quadAccel, si, rays, M, (uint32_t)byteStride, occluded, instID, dCounters3, nullptr, nullptr, cull3, coherent);
     launch_on(s, s->subdivAccel, si, rays, M, (uint32_t)byteStride, occluded, instID, dCounters2, nullptr, nullptr, cull2, coherent);
   } else {
     // Host records: staged through pinned memory.  With several shards the M rays are split into contiguous ranges
@@ -555,9 +585,11 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
         countShard = g;
         dCounters = (WaveRecord*)sh.countersDev;
         dCounters2 = dCounters + WAVE_LOG_CAPACITY;
+        dCounters3 = haveQuads ? dCounters2 + WAVE_LOG_CAPACITY : nullptr;
         HIP_CHECK(hipMemsetAsync(dCounters, 0, logBytes, sh.stream));
       }
       launch_on(s, s->triAccel, g, dRays, n, rec, occluded, instID, dCounters, nullptr, nullptr, cull1, coherent);
+      launch_on(s, s->quadAccel, g, dRays, n, rec, occluded, instID, dCounters3, nullptr, nullptr, cull3, coherent);
       launch_on(s, s->subdivAccel, g, dRays, n, rec, occluded, instID, dCounters2, nullptr, nullptr, cull2, coherent);
       if (!zeroCopy) HIP_CHECK(hipMemcpyAsync(h, sh.stageDev, bytes, hipMemcpyDeviceToHost, sh.stream));
     }
@@ -580,7 +612,7 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
   }
 
   if (countersOut) {
-    std::vector<WaveRecord> log(2 * (size_t)WAVE_LOG_CAPACITY);
+    std::vector<WaveRecord> log(logSlices * (size_t)WAVE_LOG_CAPACITY);
     Device::GpuShard& csh = *dev->shards[countShard];
     csh.use();
     HIP_CHECK(hipMemcpyAsync(log.data(), dCounters, logBytes, hipMemcpyDeviceToHost, csh.stream));
@@ -606,7 +638,7 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
       c.waveIterHist[std::min<unsigned long long>(w.iterations / 2ull, 63ull)] += 1;
     }
     // root cull pre-pass: it visited the root once for every valid ray; the traversal kernel saw (and counted) the survivors only
-    for (int l = 0; l < 2; l++) {
+    for (int l = 0; l < 3; l++) {
       unsigned long long survivors = 0, valid = 0;
       for (int q = 0; q < TRACE_QUEUES; q++) {
         survivors += cullWords[((size_t)l * TRACE_QUEUES + q) * TRACE_QUEUE_STRIDE + 1];
@@ -727,8 +759,9 @@ static bool service_trace(Scene* s, char* rays, uint32_t M, size_t byteStride, b
   Device* dev = s->device;
   if (!dev->tuneService || dev->gpu < 0 || dev->shards.size() != 1 || M > (uint32_t)SERVICE_SLOT_RAYS) return false;
   const bool tri = s->triAccel.kind != ACCEL_NONE && s->triAccel.root != REF_EMPTY, sub = s->subdivAccel.kind != ACCEL_NONE && s->subdivAccel.root != REF_EMPTY;
-  if (tri == sub) return false; // two accels (AccelN) or none: the general path
-  const Accel& A = tri ? s->triAccel : s->subdivAccel;
+  const bool quad = s->quadAccel.kind != ACCEL_NONE && s->quadAccel.root != REF_EMPTY;
+  if ((int)tri + (int)sub + (int)quad != 1) return false; // several accels (AccelN) or none: the general path
+  const Accel& A = tri ? s->triAccel : (quad ? s->quadAccel : s->subdivAccel);
   const uint32_t worst = 7u * (A.maxDepth + 1u) + 2u;
   const uint32_t need = worst > (uint32_t)TRACE_LDS_STACK ? worst - TRACE_LDS_STACK : 0u;
   if (need > Device::Service::SPILL_DEPTH) return false;
@@ -779,7 +812,8 @@ static bool service_trace(Scene* s, char* rays, uint32_t M, size_t byteStride, b
     }
     sv = dev->service;
   }
-  if (sv->failed || sv->kind != A.kind || (sv->levels != s->compressionLevel && A.kind != ACCEL_TRI_PLUECKER && A.kind != ACCEL_TRI_MOELLER && A.kind != ACCEL_GRIDSOA)) return false;
+  const bool levelFree = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER || A.kind == ACCEL_QUAD_PLUECKER || A.kind == ACCEL_QUAD_MOELLER || A.kind == ACCEL_GRIDSOA;
+  if (sv->failed || sv->kind != A.kind || (sv->levels != s->compressionLevel && !levelFree)) return false;
 
   // a slot: threads are dealt slots round-robin once; a shared slot is taken in turns
   static thread_local uint32_t mySlot = 0xFFFFFFFFu;

@@ -85,7 +85,7 @@ API ssize_t rtcGetDeviceProperty(RTCDevice h, enum RTCDeviceProperty prop)
   case RTC_DEVICE_PROPERTY_FILTER_FUNCTION_SUPPORTED: return 1;   // host callbacks, two-phase (rt_trace.cpp, triangle geometry)
   case RTC_DEVICE_PROPERTY_IGNORE_INVALID_RAYS_ENABLED: return 0; // CMakeLists.txt:117
   case RTC_DEVICE_PROPERTY_TRIANGLE_GEOMETRY_SUPPORTED: return 1;
-  case RTC_DEVICE_PROPERTY_QUAD_GEOMETRY_SUPPORTED: return 0;
+  case RTC_DEVICE_PROPERTY_QUAD_GEOMETRY_SUPPORTED: return D(h)->quads_enabled() ? 1 : 0;
   case RTC_DEVICE_PROPERTY_SUBDIVISION_GEOMETRY_SUPPORTED: return 1;
   case RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED: return 0;
   case RTC_DEVICE_PROPERTY_USER_GEOMETRY_SUPPORTED: return 0;
@@ -155,7 +155,9 @@ API RTCGeometry rtcNewGeometry(RTCDevice h, enum RTCGeometryType type)
   switch (type) {
   case RTC_GEOMETRY_TYPE_TRIANGLE:
   case RTC_GEOMETRY_TYPE_SUBDIVISION: return (RTCGeometry) new Geometry(D(h), type);
-  case RTC_GEOMETRY_TYPE_QUAD: unsupported("RTC_GEOMETRY_TYPE_QUAD");
+  case RTC_GEOMETRY_TYPE_QUAD:
+    if (!D(h)->quads_enabled()) unsupported("RTC_GEOMETRY_TYPE_QUAD on a host-only device without quad_accel=");
+    return (RTCGeometry) new Geometry(D(h), type);
   case RTC_GEOMETRY_TYPE_USER: unsupported("RTC_GEOMETRY_TYPE_USER");
   case RTC_GEOMETRY_TYPE_INSTANCE: unsupported("RTC_GEOMETRY_TYPE_INSTANCE");
   case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE:
@@ -356,6 +358,7 @@ API void rtcInterpolate(const struct RTCInterpolateArguments* args)
   VERIFY(args->geometry);
   Geometry* g = G(args->geometry);
   if (g->type == RTC_GEOMETRY_TYPE_TRIANGLE) interpolate_triangles(g, args);
+  else if (g->type == RTC_GEOMETRY_TYPE_QUAD) interpolate_quads(g, args);
   else if (g->type == RTC_GEOMETRY_TYPE_SUBDIVISION) interpolate_subdiv(g, args);
   else unsupported("rtcInterpolate on this geometry type");
   CATCH_END(args && args->geometry ? devOf(args->geometry) : nullptr)
@@ -747,6 +750,14 @@ API void rtcamdSynchronizeDevice(RTCDevice h)
 
 API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 
+// the accel the inspection calls describe: the subdivision accel if there is one, else the triangle accel, else (quad-only scene) the quad accel
+static const Accel& exported_accel(const Scene* s)
+{
+  if (s->subdivAccel.kind != ACCEL_NONE) return s->subdivAccel;
+  if (s->triAccel.kind == ACCEL_NONE && s->quadAccel.kind != ACCEL_NONE) return s->quadAccel;
+  return s->triAccel;
+}
+
 API void rtcamdGetSceneStats(RTCScene h, struct RTCAMDSceneStats* st)
 {
   CATCH_BEGIN
@@ -754,7 +765,7 @@ API void rtcamdGetSceneStats(RTCScene h, struct RTCAMDSceneStats* st)
   VERIFY(st);
   if (st->byteSize != sizeof(RTCAMDSceneStats)) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "RTCAMDSceneStats::byteSize mismatch");
   if (S(h)->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "scene got not committed");
-  const Accel& A = S(h)->subdivAccel.kind != ACCEL_NONE ? S(h)->subdivAccel : S(h)->triAccel;
+  const Accel& A = exported_accel(S(h));
   st->accelKind = A.kind;
   st->branching = 8;
   st->nodeCount = A.nodes.size();
@@ -763,7 +774,7 @@ API void rtcamdGetSceneStats(RTCScene h, struct RTCAMDSceneStats* st)
   st->primCount = tri ? A.prims.size() : (A.blobStride ? A.blobs.size() / A.blobStride : 0);
   st->primBytes = tri ? sizeof(TriRecord) : A.blobStride;
   st->leafCount = A.leafCount;
-  st->totalBytes = S(h)->triAccel.deviceBytes() + S(h)->subdivAccel.deviceBytes();
+  st->totalBytes = S(h)->triAccel.deviceBytes() + S(h)->quadAccel.deviceBytes() + S(h)->subdivAccel.deviceBytes();
   st->maxDepth = A.maxDepth;
   st->reserved = 0;
   CATCH_END(devOf(h))
@@ -795,7 +806,7 @@ API const void* rtcamdGetAccelData(RTCScene h, unsigned int kind, size_t* byteSi
   CATCH_BEGIN
   VERIFY(h);
   if (S(h)->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "scene got not committed");
-  const Accel& A = S(h)->subdivAccel.kind != ACCEL_NONE ? S(h)->subdivAccel : S(h)->triAccel;
+  const Accel& A = exported_accel(S(h));
   const void* p = nullptr;
   size_t n = 0;
   switch (kind) {
@@ -867,7 +878,7 @@ API unsigned int rtcamdGetAccelRoot(RTCScene h)
 {
   CATCH_BEGIN
   VERIFY(h);
-  const Accel& A = S(h)->subdivAccel.kind != ACCEL_NONE ? S(h)->subdivAccel : S(h)->triAccel;
+  const Accel& A = exported_accel(S(h));
   return A.root;
   CATCH_END(devOf(h))
   return REF_EMPTY;

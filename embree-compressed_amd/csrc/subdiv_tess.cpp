@@ -979,6 +979,26 @@ void interpolate_triangles(const Geometry* geom, const RTCInterpolateArguments* 
   }
 }
 
+// Quad meshes: the reference's arithmetic (QuadMesh::interpolate, scene_quad_mesh.cpp:210-270): the triangle (p0, p1, p3) for
+// u+v <= 1, else (p2, p3, p1) at (1-u, 1-v); signed edge differences as derivatives, second derivatives 0.
+void interpolate_quads(const Geometry* geom, const RTCInterpolateArguments* args)
+{
+  const BufferView* src = geom->view(args->bufferType, args->bufferSlot);
+  if (!src || !src->valid()) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: buffer slot is not bound");
+  if (args->primID >= geom->numQuads()) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: invalid primID");
+  unsigned idx[4];
+  geom->quad(args->primID, idx);
+  const bool left = args->u + args->v <= 1.0f;
+  const unsigned i0 = left ? idx[0] : idx[2], i1 = left ? idx[1] : idx[3], i2 = left ? idx[3] : idx[1];
+  const float u = left ? args->u : 1.0f - args->u, v = left ? args->v : 1.0f - args->v, w = 1.0f - u - v;
+  for (unsigned i = 0; i < args->valueCount; i++) {
+    const float q0 = ((const float*)src->at(i0))[i], q1 = ((const float*)src->at(i1))[i], q2 = ((const float*)src->at(i2))[i];
+    if (args->P) args->P[i] = fmaf(w, q0, fmaf(u, q1, v * q2));
+    if (args->dPdu) { args->dPdu[i] = left ? q1 - q0 : q0 - q1; args->dPdv[i] = left ? q2 - q0 : q0 - q2; }
+    if (args->ddPdudu) { args->ddPdudu[i] = 0.f; args->ddPdvdv[i] = 0.f; args->ddPdudv[i] = 0.f; }
+  }
+}
+
 // Subdivision meshes: Catmull-Clark limit surface of any vertex / vertex-attribute buffer at (primID, u, v).
 // The reference evaluates through patch classification, bicubic B-spline patches, feature-adaptive subdivision and
 // Gregory patches (scene_subdiv_mesh.cpp:757-864, patch_eval.h).  Here the buffer is refined K = 3 times with the

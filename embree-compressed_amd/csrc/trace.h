@@ -37,6 +37,7 @@ struct LaunchParams
   // nullptr for ordinary launches.
   // Grid cells (eager subdivision path): the triangles of a patch share (geomID, primID), so an entry also carries the candidate's
   // distance, exclT[e] = bits of t - the kernels are deterministic, the same triangle yields the same t on the re-trace.
+  // Quads use the same scheme (their two triangles share the quad's ids).
   const uint32_t* exclOffsets;
   const uint2* exclPairs;
   const uint32_t* exclT;
@@ -85,6 +86,7 @@ struct ServiceParams
 // start the service kernel for base.accel.kind (and base.cbvhLevels); hipErrorInvalidValue: no service kernel for this accel kind / level
 hipError_t launch_service_tri(const ServiceParams& s, hipStream_t stream);    // trace_tri.hip
 hipError_t launch_service_subdiv(const ServiceParams& s, hipStream_t stream); // trace_subdiv.hip
+hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream);   // trace_quad.hip
 
 static const int TRACE_QUEUES = 64;       // work queues per launch (must equal the wavefront width: one lane scans one head)
 static const int TRACE_QUEUE_STRIDE = 32; // u32 words between two work-queue heads (128 B: one L2 line each)
@@ -113,11 +115,14 @@ uint32_t trace_grid_blocks(uint32_t count, int numCUs, uint32_t rayChunk);
 hipError_t launch_trace_tri(const LaunchParams& p, hipStream_t stream);    // trace_tri.hip
 hipError_t launch_cull(const LaunchParams& p, hipStream_t stream);         // trace_tri.hip (trace_cull.hip.h): root cull pre-pass
 hipError_t launch_trace_subdiv(const LaunchParams& p, hipStream_t stream); // trace_subdiv.hip
+hipError_t launch_trace_quad(const LaunchParams& p, hipStream_t stream);   // trace_quad.hip
 inline hipError_t launch_service(const ServiceParams& s, hipStream_t stream)
 {
   switch (s.base.accel.kind) {
   case ACCEL_TRI_PLUECKER:
   case ACCEL_TRI_MOELLER: return launch_service_tri(s, stream);
+  case ACCEL_QUAD_PLUECKER:
+  case ACCEL_QUAD_MOELLER: return launch_service_quad(s, stream);
   case ACCEL_CBVH_BOX:
   case ACCEL_CBVH_LEAF:
   case ACCEL_CBVH_GRID:
@@ -131,6 +136,8 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   switch (p.accel.kind) {
   case ACCEL_TRI_PLUECKER:
   case ACCEL_TRI_MOELLER: return launch_trace_tri(p, stream);
+  case ACCEL_QUAD_PLUECKER:
+  case ACCEL_QUAD_MOELLER: return launch_trace_quad(p, stream);
   case ACCEL_CBVH_BOX:
   case ACCEL_CBVH_LEAF:
   case ACCEL_CBVH_GRID:

@@ -1,0 +1,231 @@
+// Quad leaves of the quantized BVH8: Quad4v with Pluecker (robust) or Moeller-Trumbore (fast) arithmetic.
+// 64-byte records (QuadRecord, accel.h) fetched as four dwordx4; every group of 4 records from the leaf start is one block of the
+// reference's AVX form, which tests the 4 quads as ONE 8-wide block of triangles:
+//   lanes 0-3 = triangle A (v0, v1, v3) of quads 0-3, lanes 4-7 = triangle B (v2, v1, v3) of quads 0-3
+//   (quad_intersector_pluecker.h:264-299, quad_intersector_moeller.h:251-290), all 8 tested against the tfar at block entry,
+//   one select_min over the 8 lanes (Intersect1EpilogM<8,8,filter>): the lowest lane wins ties, so A beats B at equal t.
+// Hits on a B triangle report the quad's parametrisation and the negated triangle normal; the u / v mapping differs per variant:
+//   Pluecker  u = 1 - v_tri, v = 1 - u_tri after the division (QuadHitPlueckerM::finalize, the AVX branch, pluecker.h:45-66)
+//   Moeller   U' = absDen - V, V' = absDen - U before the division by absDen (quad_intersector_moeller.h:268-282)
+#include "trace_loop.hip.h"
+#include "trace_pool.hip.h"
+#include "trace_service.hip.h"
+
+namespace rtamd {
+namespace dev {
+
+// Records requested per memory round trip inside a block of 4 quads in the lane-per-ray form (1, 2 or 4).  Pluecker fetches two at
+// a time: with four (16 dwordx4 in flight) its closest-hit lane kernel needs 32-40 bytes of scratch at the 3-waves register limit.
+#ifndef QUAD_FETCH_PLUECKER
+#define QUAD_FETCH_PLUECKER 2
+#endif
+#ifndef QUAD_FETCH_MOELLER
+#define QUAD_FETCH_MOELLER 4
+#endif
+
+// Moeller-Trumbore on the triangle (a, b, c) of a quad, edges formed as the reference's vertex form does (e1 = a - b, e2 = c - a,
+// MoellerTrumboreIntersector1::intersect(ray, v0, v1, v2), triangle_intersector_moeller.h); the test itself is moeller()'s.
+// flip: triangle B of the quad - U / V are mapped before the division and the normal is negated.
+__device__ __forceinline__ bool moeller_quad(const RayState& r, const float4 a, const float4 b, const float4 c, float tfarBlock, bool flip, TriHit& h)
+{
+  const float e1x = a.x - b.x, e1y = a.y - b.y, e1z = a.z - b.z;
+  const float e2x = c.x - a.x, e2y = c.y - a.y, e2z = c.z - a.z;
+  const float ngx = msub(e2y, e1z, e2z * e1y), ngy = msub(e2z, e1x, e2x * e1z), ngz = msub(e2x, e1y, e2y * e1x);
+  const float cx = a.x - r.ox, cy = a.y - r.oy, cz = a.z - r.oz;
+  const float rx = msub(cy, r.dz, cz * r.dy), ry = msub(cz, r.dx, cx * r.dz), rz = msub(cx, r.dy, cy * r.dx);
+  const float den = dot3(ngx, ngy, ngz, r.dx, r.dy, r.dz);
+  const float absDen = fabsf(den);
+  const uint32_t sgnDen = __float_as_uint(den) & 0x80000000u;
+  const float U = xorf(dot3(rx, ry, rz, e2x, e2y, e2z), sgnDen);
+  const float V = xorf(dot3(rx, ry, rz, e1x, e1y, e1z), sgnDen);
+  if (!((den != 0.0f) & (U >= 0.0f) & (V >= 0.0f) & (U + V <= absDen))) return false;
+  const float T = xorf(dot3(ngx, ngy, ngz, cx, cy, cz), sgnDen);
+  h.Ts = T; h.absDen = absDen;
+  if (!((absDen * r.tnear < T) & (T <= absDen * tfarBlock))) return false;
+  const float rcpAbsDen = 1.0f / absDen;
+  h.t = T * rcpAbsDen;
+  h.u = (flip ? absDen - V : U) * rcpAbsDen;
+  h.v = (flip ? absDen - U : V) * rcpAbsDen;
+  const uint32_t s = flip ? 0x80000000u : 0u;
+  h.ngx = xorf(ngx, s); h.ngy = xorf(ngy, s); h.ngz = xorf(ngz, s);
+  return true;
+}
+
+// Pluecker on the triangle (a, b, c) of a quad: pluecker() unchanged, then the B mapping after the division.
+__device__ __forceinline__ bool pluecker_quad(const RayState& r, const float4 a, const float4 b, const float4 c, float tfarBlock, bool flip, TriHit& h)
+{
+  if (!pluecker(r, a, b, c, tfarBlock, h)) return false;
+  const float u = h.u, v = h.v;
+  h.u = flip ? 1.0f - v : u;
+  h.v = flip ? 1.0f - u : v;
+  const uint32_t s = flip ? 0x80000000u : 0u;
+  h.ngx = xorf(h.ngx, s); h.ngy = xorf(h.ngy, s); h.ngz = xorf(h.ngz, s);
+  return true;
+}
+
+// Filter re-trace (LaunchParams::exclOffsets): both triangles of a quad carry the quad's (geomID, primID), so a rejected candidate
+// is identified by its distance as well (exclT, the scheme of the grid cells).  A ray through the diagonal v1-v3 hits A and B at a
+// bit-identical t: rejecting one rejects both, where the reference would offer B after A.
+__device__ __forceinline__ bool quad_candidate_excluded(const LaunchParams& P, uint32_t rayIdx, uint32_t geomID, uint32_t primID, float t)
+{
+  const uint32_t e1 = P.exclOffsets[rayIdx + 1];
+  for (uint32_t e = P.exclOffsets[rayIdx]; e < e1; e++) {
+    const uint2 q = P.exclPairs[e];
+    if (q.x == geomID && q.y == primID && P.exclT[e] == __float_as_uint(t)) return true;
+  }
+  return false;
+}
+
+template <bool PLUECKER> struct QuadLeaf
+{
+  static constexpr bool OCTET = true;
+  static constexpr bool CONST_NG = false;
+  static constexpr int GROUP = 8;
+  static constexpr bool HIT_IN_MEMORY = false;
+  static constexpr bool OCTET_ONLY = false; // both forms, as for triangle leaves (trace_tri.hip)
+  static constexpr int MIN_WAVES = TRACE_MIN_WAVES_PER_SIMD;
+  static constexpr uint32_t FETCH = PLUECKER ? QUAD_FETCH_PLUECKER : QUAD_FETCH_MOELLER;
+  static __device__ __forceinline__ bool octet_ok(const LaunchParams&) { return true; }
+  static __device__ __forceinline__ void prepare() {}
+
+  static __device__ __forceinline__ bool test(const RayState& r, const float4 a, const float4 b, const float4 c, float tfar, bool flip, TriHit& h)
+  {
+    return PLUECKER ? pluecker_quad(r, a, b, c, tfar, flip, h) : moeller_quad(r, a, b, c, tfar, flip, h);
+  }
+
+  // Child-parallel form (trace_loop.hip.h): lane k of the octet of the ray in exchange row `x` tests triangle A (k < 4) or B (k >= 4)
+  // of quad b + (k & 3) - exactly one of the reference's 8-wide blocks per pass.  One 8-lane minimum; the lowest lane with that t
+  // writes the hit into the row (words 0..7 = t, Ng, u, v, geomID, primID; word 9 = 1).
+  template <bool OCCLUDED, bool COUNT>
+  static __device__ __forceinline__ void octet_pass(const LaunchParams& P, float* x, bool valid, uint32_t lid, WorkCounters& wc)
+  {
+    const QuadRecord* __restrict__ quads = (const QuadRecord*)P.accel.blobs;
+    const uint32_t k = lid & 7u, sh = lid & 56u;
+    const bool isB = k >= 4u;
+    RayState r;
+    r.ox = x[0]; r.oy = x[1]; r.oz = x[2]; r.tnear = x[3];
+    r.dx = x[4]; r.dy = x[5]; r.dz = x[6]; r.tfar = x[7];
+    const uint32_t ref = __float_as_uint(x[8]);
+    const uint32_t first = ref & ((1u << TRI_START_BITS) - 1u);
+    uint32_t cnt = valid ? (ref >> TRI_START_BITS) & 31u : 0u;
+    float tfar = r.tfar;
+    for (uint32_t b = 0; __ballot(b < cnt) != 0ull; b += 4u) {
+      const bool present = b + (k & 3u) < cnt;
+      const float4* qp = (const float4*)(quads + first + (present ? b + (k & 3u) : 0u));
+      const float4 V0 = qp[isB ? 2 : 0], V1 = qp[1], V3 = qp[3];
+      // geomID lives in v0.w: lane k+4 takes it from lane k (same quad; half mirror, then xor 3 = lane k^4)
+      const uint32_t geomID = dpp_u32<DPP_XOR3>(dpp_u32<DPP_HALF_MIRROR>(__float_as_uint(V0.w)));
+      const uint32_t primID = __float_as_uint(V1.w);
+      if (COUNT && present && !isB) wc.prims++;
+      TriHit h;
+      h.t = RT_INF; h.Ts = 0.f; h.absDen = 0.f;
+      bool ok = test(r, V0, V1, V3, tfar, isB, h) && present;
+      if (ok && P.exclOffsets) ok = !quad_candidate_excluded(P, __float_as_uint(x[10]), isB ? geomID : __float_as_uint(V0.w), primID, h.t);
+      const uint32_t m8 = (uint32_t)(__ballot(ok) >> sh) & 0xffu;
+      if (OCCLUDED) { // Occluded1EpilogM: any valid lane
+        if (m8 != 0u) {
+          if (k == 0u) x[9] = __uint_as_float(1u);
+          cnt = 0u;
+        }
+        continue;
+      }
+      float tm = ok ? h.t : RT_INF;
+      tm = fminf(tm, __uint_as_float(dpp_u32<DPP_XOR1>(__float_as_uint(tm))));
+      tm = fminf(tm, __uint_as_float(dpp_u32<DPP_XOR2>(__float_as_uint(tm))));
+      tm = fminf(tm, __uint_as_float(dpp_u32<DPP_HALF_MIRROR>(__float_as_uint(tm)))); // minimum of the 8 lanes, in all 8
+      const uint32_t w = (uint32_t)(__ballot(ok && h.t == tm) >> sh) & 0xffu;
+      const uint32_t winner = w != 0u ? (uint32_t)__ffs(w) - 1u : 8u;
+      if (k == winner) { // Intersect1EpilogM, intersector_epilog.h:293-305
+        x[0] = h.t; x[1] = h.ngx; x[2] = h.ngy; x[3] = h.ngz; x[4] = h.u; x[5] = h.v;
+        x[6] = __uint_as_float(isB ? geomID : __float_as_uint(V0.w)); x[7] = __uint_as_float(primID);
+        x[9] = __uint_as_float(1u);
+      }
+      tfar = w != 0u ? tm : tfar;
+    }
+  }
+
+  // Lane-per-ray form: the 8 candidates of a block (A of quads 0-3 = lanes 0-3, B = lanes 4-7), all against the tfar at block
+  // entry, tested quad by quad (A, B) so that a quad's registers die early; the lane number decides between equal t, so the
+  // lowest lane wins ties as in the octet form.
+  template <bool OCCLUDED, bool COUNT>
+  static __device__ __forceinline__ bool intersect(const LaunchParams& P, uint32_t ref, RayState& r, WorkCounters& wc, uint32_t rayIdx)
+  {
+    const QuadRecord* __restrict__ quads = (const QuadRecord*)P.accel.blobs;
+    const uint32_t first = ref & ((1u << TRI_START_BITS) - 1u);
+    const uint32_t count = (ref >> TRI_START_BITS) & 31u;
+    for (uint32_t b = 0; b < count; b += 4) {
+      const float tfarBlock = r.tfar;
+      const uint32_t nb = min(4u, count - b);
+      bool found = false;
+      TriHit best;
+      uint32_t bestLane = 8u, bestPrim = 0, bestGeom = 0;
+      best.t = RT_INF;
+      for (uint32_t g = 0; g < nb; g += FETCH) {
+        // all records of the fetch group are requested before the first one is used; slots past the leaf end re-read the last record
+        float4 V0[FETCH], V1[FETCH], V2[FETCH], V3[FETCH];
+#pragma unroll
+        for (uint32_t k = 0; k < FETCH; k++) {
+          const float4* qp = (const float4*)(quads + first + b + min(g + k, nb - 1u));
+          V0[k] = qp[0]; V1[k] = qp[1]; V2[k] = qp[2]; V3[k] = qp[3];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < FETCH; k++) {
+          if (g + k >= nb) break;
+          if (COUNT) wc.prims++;
+          const uint32_t gid = __float_as_uint(V0[k].w), pid = __float_as_uint(V1[k].w);
+#pragma unroll
+          for (uint32_t half = 0; half < 2; half++) { // A then B of this quad (lanes g+k and 4+g+k)
+            TriHit h;
+            bool ok = test(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h);
+            if (ok && P.exclOffsets) ok = !quad_candidate_excluded(P, rayIdx, gid, pid, h.t);
+            if (ok) {
+              if (OCCLUDED) return true; // Occluded1EpilogM: any valid lane
+              // select_min over the 8 lanes, lowest lane wins ties
+              const uint32_t lane = half * 4u + g + k;
+              if (!found || h.t < best.t || (h.t == best.t && lane < bestLane)) {
+                best = h;
+                bestLane = lane;
+                bestGeom = gid;
+                bestPrim = pid;
+                found = true;
+              }
+            }
+          }
+        }
+      }
+      if (found) { // Intersect1EpilogM, intersector_epilog.h:293-305
+        r.tfar = best.t;
+        r.ngx = best.ngx; r.ngy = best.ngy; r.ngz = best.ngz;
+        r.u = best.u; r.v = best.v;
+        r.primID = bestPrim; r.geomID = bestGeom;
+        r.hit = 1u;
+      }
+    }
+    return false;
+  }
+};
+
+} // namespace dev
+
+hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream)
+{
+#ifdef TRACE_DEV_METRIC_ONLY
+  return hipErrorInvalidValue;
+#else
+  if (s.base.accel.kind == ACCEL_QUAD_PLUECKER) return dev::launch_service_kernel<dev::QuadLeaf<true>, true>(s, stream);
+  return dev::launch_service_kernel<dev::QuadLeaf<false>, false>(s, stream);
+#endif
+}
+
+hipError_t launch_trace_quad(const LaunchParams& p, hipStream_t stream)
+{
+  // Quad4v: Pluecker <-> robust traversal, Moeller <-> fast traversal (bvh_intersector1_bvh8.cpp:37-39)
+  if (p.poolKernel) {
+    if (p.accel.kind == ACCEL_QUAD_PLUECKER) return dev::launch_leaf_pool<dev::QuadLeaf<true>, true>(p, stream);
+    return dev::launch_leaf_pool<dev::QuadLeaf<false>, false>(p, stream);
+  }
+  if (p.accel.kind == ACCEL_QUAD_PLUECKER) return dev::launch_leaf<dev::QuadLeaf<true>, true>(p, stream);
+  return dev::launch_leaf<dev::QuadLeaf<false>, false>(p, stream);
+}
+
+} // namespace rtamd

@@ -29,6 +29,7 @@ RTC_BUFFER_TYPE_VERTEX_CREASE_INDEX = 20
 RTC_BUFFER_TYPE_VERTEX_CREASE_WEIGHT = 21
 RTC_FORMAT_UINT = 0x5001
 RTC_FORMAT_UINT3 = 0x5003
+RTC_FORMAT_UINT4 = 0x5004
 RTC_FORMAT_FLOAT = 0x9001
 RTC_FORMAT_FLOAT3 = 0x9003
 RTC_SCENE_FLAG_NONE = 0
@@ -298,6 +299,28 @@ class Scene:
         L.rtcReleaseGeometry(g)
         self._keep += [vpad, t]
         self.device.check("add_triangles")
+        return gid
+
+    def add_quads(self, verts, quads, geom_id=None):
+        """verts float32 [nv,3], quads uint32 [nq,4] (RTC_GEOMETRY_TYPE_QUAD, UINT4 index buffer); shared buffers like add_triangles."""
+        L = self.lib
+        v = np.ascontiguousarray(verts, dtype=np.float32)
+        vpad = np.zeros((v.shape[0] + 2, 3), dtype=np.float32)
+        vpad[: v.shape[0]] = v
+        q = np.ascontiguousarray(quads, dtype=np.uint32).reshape(-1, 4)
+        g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_QUAD)
+        self.device.check("rtcNewGeometry(QUAD)")
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_VERTEX, 0, RTC_FORMAT_FLOAT3, vpad.ctypes.data, 0, 12, v.shape[0])
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_INDEX, 0, RTC_FORMAT_UINT4, q.ctypes.data, 0, 16, q.shape[0])
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self._keep += [vpad, q]
+        self.device.check("add_quads")
         return gid
 
     def add_subdiv(self, verts, face_sizes, face_index, level=1.0, geom_id=None, displacement=None, user_data=None,

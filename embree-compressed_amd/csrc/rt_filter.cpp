@@ -1,0 +1,220 @@
+// Batches with filter callbacks: the host filter loop over exclusion-list re-traces.
+#include "rt_trace.h"
+
+namespace rtamd {
+
+// ---- filter callbacks (row f3) -----------------------------------------------------------------------------------------
+// Filter functions are host function pointers (intersector_epilog.h:251-291, filter.h:27-130): the device cannot call
+// them.  Two-phase scheme: the kernel finds the closest candidate of every ray; the host runs the geometry's filter and
+// then the context filter on it with the reference's argument protocol (ray.tfar = candidate distance, N = 1); an
+// accepted candidate is the ray's result; a rejected one is put on the ray's exclusion list and the ray is traced again
+// (only those rays, compacted), the kernel skipping listed candidates, until every ray has an accepted hit or none.
+// For pure accept/reject filters this is the reference's result: rejected candidates never shorten the ray there either,
+// so the closest accepted candidate wins.  The callbacks see the candidates of a ray in order of distance instead of
+// traversal order, each at most once.  Occlusion filters run the same loop on closest candidates (any accepted candidate
+// = occluded).
+// Subdivision geometry (round 2):
+//  * eager grid cells (GridSOAIntersector1 -> Intersect1EpilogMU / Occluded1EpilogMU, grid_soa_intersector1.h:61,83,
+//    intersector_epilog.h:460-600: every triangle of a patch is offered to the filter on its own, with the PATCH's geomID / primID):
+//    a candidate is identified by (geomID, primID, bits of t) - kernels are deterministic, the same triangle gives the same t
+//    when the ray is traced again.  Two triangles of one patch hit at a bit-identical distance (a ray through their shared edge)
+//    are rejected together, where the reference would offer both.
+//  * quads (QuadMvIntersector1*<4,true>, filter = true) offer each triangle with the QUAD's geomID / primID: identified like grid cells
+//    by (geomID, primID, bits of t); a ray through the diagonal v1-v3 hits both triangles at one t, and rejecting one rejects both.
+//  * the fork's compressed modes never call a filter: CompressedBVHIntersector1::intersect writes the hit itself and occluded()
+//    is a stub (compressed.h:454-756, no runIntersectionFilter1 anywhere in compressed*.h).  Hits on such an accel are accepted
+//    without a callback, geometry and context filter alike; for any-hit queries the stub pass runs first, unfiltered.
+static const unsigned FILTER_MAX_ROUNDS = 256;
+
+// The candidates the callbacks rejected on one accel, and their flattened form for the active rays of a round.
+struct ExclList
+{
+  struct Rejected { uint32_t geomID, primID, tbits; };
+  bool keyedByT = false; // grid cells and quads: a candidate is (geomID, primID, bits of t); triangles: (geomID, primID)
+  std::vector<std::vector<Rejected>> perRay; // by ray of the batch
+  std::vector<uint32_t> off, tbits;
+  std::vector<uint2> pairs;
+  static size_t a16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+  void flatten(const std::vector<uint32_t>& act)
+  {
+    off.assign(act.size() + 1, 0);
+    pairs.clear();
+    tbits.clear();
+    for (size_t k = 0; k < act.size(); k++) {
+      off[k] = (uint32_t)pairs.size();
+      for (const Rejected& e : perRay[act[k]]) {
+        pairs.push_back(make_uint2(e.geomID, e.primID));
+        if (keyedByT) tbits.push_back(e.tbits);
+      }
+    }
+    off[act.size()] = (uint32_t)pairs.size();
+  }
+  size_t deviceBytes() const { return a16(off.size() * 4) + a16(pairs.size() * sizeof(uint2)) + a16(tbits.size() * 4); }
+  // into deviceBytes() bytes at D; an empty list is not uploaded and its launch gets no exclusion pointers
+  LaunchExtras upload(char* D, hipStream_t stream) const
+  {
+    LaunchExtras x;
+    if (pairs.empty()) return x;
+    char* dPairs = D + a16(off.size() * 4);
+    char* dT = dPairs + a16(pairs.size() * sizeof(uint2));
+    HIP_CHECK(hipMemcpyAsync(D, off.data(), off.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(dPairs, pairs.data(), pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
+    if (keyedByT) HIP_CHECK(hipMemcpyAsync(dT, tbits.data(), tbits.size() * 4, hipMemcpyHostToDevice, stream));
+    x.exclOffsets = (const uint32_t*)D;
+    x.exclPairs = (const uint2*)dPairs;
+    x.exclT = keyedByT ? (const uint32_t*)dT : nullptr;
+    return x;
+  }
+};
+
+void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occluded, const RTCIntersectContext* ctx)
+{
+  Device* dev = s->device;
+  RTCIntersectContext localCtx;
+  if (!ctx) { memset(&localCtx, 0, sizeof(localCtx)); localCtx.instID[0] = RTC_INVALID_GEOMETRY_ID; ctx = &localCtx; }
+  const uint32_t instID = ctx->instID[0];
+  const uint32_t recIn = occluded ? (uint32_t)sizeof(RTCRay) : (uint32_t)sizeof(RTCRayHit);
+  const bool forkAccel = s->subdivAccel.traceable() && s->subdivAccel.kind != ACCEL_GRIDSOA; // no filter calls on these (see above)
+  std::lock_guard<std::mutex> lock(dev->launchMutex);
+  // the host filter loop runs on the first shard (its rounds are latency bound, not throughput bound)
+  Device::GpuShard& sh = dev->primary();
+  sh.use();
+
+  // the caller's records, on the host
+  const bool devPtr = is_device_pointer(rays);
+  const size_t span = (size_t)(M - 1) * byteStride + recIn;
+  std::vector<char> mirror;
+  char* src = (char*)rays;
+  if (devPtr) {
+    mirror.resize(span);
+    HIP_CHECK(hipMemcpyAsync(mirror.data(), rays, span, hipMemcpyDeviceToHost, sh.stream));
+    HIP_CHECK(hipStreamSynchronize(sh.stream));
+    src = mirror.data();
+  }
+  std::vector<RTCRayHit> W(M);
+  std::vector<uint32_t> act;
+  act.reserve(M);
+  for (uint32_t i = 0; i < M; i++) {
+    memcpy(&W[i].ray, src + (size_t)i * byteStride, sizeof(RTCRay));
+    if (occluded) {
+      memset(&W[i].hit, 0, sizeof(RTCHit));
+      W[i].hit.geomID = W[i].hit.primID = W[i].hit.instID[0] = RTC_INVALID_GEOMETRY_ID;
+    } else
+      memcpy(&W[i].hit, src + (size_t)i * byteStride + sizeof(RTCRay), sizeof(RTCHit));
+    if (W[i].ray.tnear <= W[i].ray.tfar && !(occluded && W[i].ray.tfar < 0.0f)) act.push_back(i);
+  }
+  if (occluded && forkAccel && !act.empty()) {
+    // the stub any-hit pass of the fork's accel, unfiltered; the filter loop below then only sees the triangle accel
+    const uint32_t K = (uint32_t)act.size();
+    const size_t bytes = (size_t)K * sizeof(RTCRay);
+    sh.ensureStaging(bytes);
+    RTCRay* h = (RTCRay*)sh.stageHost;
+    for (uint32_t k = 0; k < K; k++) h[k] = W[act[k]].ray;
+    HIP_CHECK(hipMemcpyAsync(sh.stageDev, h, bytes, hipMemcpyHostToDevice, sh.stream));
+    launch_on(s, s->subdivAccel, 0, Batch{sh.stageDev, K, (uint32_t)sizeof(RTCRay), true, false, instID, nullptr});
+    HIP_CHECK(hipMemcpyAsync(h, sh.stageDev, bytes, hipMemcpyDeviceToHost, sh.stream));
+    HIP_CHECK(hipStreamSynchronize(sh.stream));
+    std::vector<uint32_t> rest;
+    for (uint32_t k = 0; k < K; k++) {
+      if (h[k].tfar < 0.0f) W[act[k]].ray.tfar = -std::numeric_limits<float>::infinity();
+      else rest.push_back(act[k]);
+    }
+    act.swap(rest);
+  }
+  ExclList excl[Scene::NUM_ACCELS];
+  for (ExclList& e : excl) e.perRay.resize(M);
+  excl[Scene::QUAD].keyedByT = excl[Scene::SUBDIV].keyedByT = true;
+  std::vector<uint32_t> next;
+  void* dExcl = nullptr;
+  size_t dExclBytes = 0;
+  auto freeExcl = [&]() { if (dExcl) hipFree(dExcl); dExcl = nullptr; };
+  try {
+    for (unsigned round = 0; !act.empty() && round < FILTER_MAX_ROUNDS; round++) {
+      const uint32_t K = (uint32_t)act.size();
+      const size_t bytes = (size_t)K * sizeof(RTCRayHit);
+      sh.ensureStaging(bytes);
+      RTCRayHit* h = (RTCRayHit*)sh.stageHost;
+      for (uint32_t k = 0; k < K; k++) h[k] = W[act[k]];
+      size_t need = 0, listed = 0;
+      for (ExclList& e : excl) {
+        e.flatten(act);
+        need += e.deviceBytes();
+        listed += e.pairs.size();
+      }
+      LaunchExtras extras[Scene::NUM_ACCELS];
+      if (listed) {
+        if (need > dExclBytes) {
+          HIP_CHECK(hipStreamSynchronize(sh.stream));
+          freeExcl();
+          dExclBytes = need * 2;
+          HIP_CHECK(hipMalloc(&dExcl, dExclBytes));
+        }
+        char* D = (char*)dExcl;
+        for (size_t i = 0; i < Scene::NUM_ACCELS; i++) {
+          extras[i] = excl[i].upload(D, sh.stream);
+          D += excl[i].deviceBytes();
+        }
+      }
+      HIP_CHECK(hipMemcpyAsync(sh.stageDev, h, bytes, hipMemcpyHostToDevice, sh.stream));
+      // (any-hit queries on a fork accel: its stub pass above was the subdivision launch)
+      trace_accels(s, 0, Batch{sh.stageDev, K, (uint32_t)sizeof(RTCRayHit), false, false, instID, nullptr}, extras, occluded && forkAccel ? &s->subdivAccel : nullptr);
+      HIP_CHECK(hipMemcpyAsync(h, sh.stageDev, bytes, hipMemcpyDeviceToHost, sh.stream));
+      HIP_CHECK(hipStreamSynchronize(sh.stream));
+      next.clear();
+      for (uint32_t k = 0; k < K; k++) {
+        const uint32_t i = act[k];
+        const RTCRayHit& got = h[k];
+        const bool found = got.hit.geomID != RTC_INVALID_GEOMETRY_ID &&
+                           (got.ray.tfar != W[i].ray.tfar || got.hit.primID != W[i].hit.primID || got.hit.geomID != W[i].hit.geomID);
+        if (!found) continue; // miss: the caller's record stays as it is
+        // the hit reports instID in geomID when instanced; instancing is not on this path, so geomID is the geometry
+        Geometry* geo = got.hit.geomID < s->geometries.size() ? s->geometries[got.hit.geomID] : nullptr;
+        const bool onSubdiv = geo && geo->type == RTC_GEOMETRY_TYPE_SUBDIVISION;
+        const bool unfiltered = onSubdiv && forkAccel;
+        RTCFilterFunctionN fn = geo && !unfiltered ? (occluded ? geo->occludedFilter : geo->intersectFilter) : nullptr;
+        RTCFilterFunctionN cfn = unfiltered ? nullptr : ctx->filter;
+        bool accepted = true;
+        RTCRayHit cand = W[i];
+        cand.ray.tfar = got.ray.tfar; // filter.h / intersector_epilog.h:277-279: the callback sees tfar = candidate distance
+        RTCHit hit = got.hit;
+        if (fn || cfn) {
+          int mask = -1;
+          RTCFilterFunctionNArguments a;
+          a.valid = &mask;
+          a.geometryUserPtr = geo ? geo->userPtr : nullptr;
+          a.context = ctx;
+          a.ray = (RTCRayN*)&cand.ray;
+          a.hit = (RTCHitN*)&hit;
+          a.N = 1;
+          if (fn) fn(&a);
+          if (mask != 0 && cfn) cfn(&a);
+          accepted = mask != 0;
+        }
+        if (accepted) {
+          if (occluded) W[i].ray.tfar = -std::numeric_limits<float>::infinity();
+          else { W[i].ray = cand.ray; W[i].hit = hit; } // copyHitToRay
+        } else {
+          uint32_t tb;
+          memcpy(&tb, &got.ray.tfar, 4);
+          const bool onQuad = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD;
+          excl[onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : Scene::TRI)].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb});
+          next.push_back(i);
+        }
+      }
+      act.swap(next);
+    }
+  } catch (...) {
+    freeExcl();
+    throw;
+  }
+  freeExcl();
+  // outputs: tfar, and the hit for rtcIntersect
+  scatter_outputs(src, byteStride, W.data(), (uint32_t)sizeof(RTCRayHit), M, occluded);
+  if (devPtr) {
+    HIP_CHECK(hipMemcpyAsync(rays, mirror.data(), span, hipMemcpyHostToDevice, sh.stream));
+    HIP_CHECK(hipStreamSynchronize(sh.stream));
+  }
+}
+
+} // namespace rtamd

@@ -4,6 +4,7 @@
 #pragma once
 #include <map>
 #include <memory>
+#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -143,7 +144,7 @@ struct Device : RefCounted
     RTCError error = RTC_ERROR_NONE;
     std::string message;
   };
-  // Persistent consumer for calls of up to 64 rays (trace_service.hip.h, rt_trace.cpp service_trace): env RTAMD_SERVICE / config key service=1
+  // Persistent consumer for calls of up to 64 rays (trace_service.hip.h, rt_service.cpp service_trace): env RTAMD_SERVICE / config key service=1
   struct Service;
   Service* service = nullptr;
   std::mutex serviceMutex; // creation / restart of the service kernel
@@ -306,6 +307,7 @@ struct Accel
   std::vector<DevCopy> dev;
   std::vector<int> devOrdinals; // ordinal each copy lives on (for freeDevice)
   AccelDesc desc(size_t shard = 0) const;
+  bool traceable() const { return kind != ACCEL_NONE && root != REF_EMPTY; } // a launch on anything else returns before it touches the GPU
   size_t deviceBytes() const;
   void upload(Device* dev);
   void freeDevice();
@@ -324,7 +326,7 @@ struct Scene : RefCounted
   void* progressUser = nullptr;
   bool modified = true; // "scene got not committed" until the first commit (scene.cpp:25,54)
   // filter callbacks present at commit time (Scene::hasGeometryFilterFunction, scene.h): they route a batch through the
-  // host filter loop of rt_trace.cpp (the tri* flags cover quad meshes too)
+  // host filter loop of rt_filter.cpp (the tri* flags cover quad meshes too)
   bool triIntersectFilter = false, triOccludedFilter = false, subdivFilter = false;
   std::mutex buildMutex;
   Box3 bounds;
@@ -334,6 +336,9 @@ struct Scene : RefCounted
   Accel triAccel;    // triangles
   Accel quadAccel;   // quads (QuadRecord[] in `blobs`); traced after the triangles, before the subdivision patches (scene.cpp:650-654)
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
+  // the accels in trace order; TRI / QUAD / SUBDIV index whatever a path keeps per accel
+  enum { TRI = 0, QUAD = 1, SUBDIV = 2, NUM_ACCELS = 3 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &quadAccel, &subdivAccel}; }
 
   explicit Scene(Device* d);
   ~Scene() override;

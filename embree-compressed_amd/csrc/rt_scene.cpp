@@ -50,20 +50,12 @@ void Geometry::bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size
     RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "buffer range out of bounds");
   switch (type) {
   case RTC_GEOMETRY_TYPE_TRIANGLE:
+  case RTC_GEOMETRY_TYPE_QUAD: // TriangleMesh::setBuffer / QuadMesh::setBuffer (scene_quad_mesh.cpp): the index format differs
     if (t == RTC_BUFFER_TYPE_VERTEX) {
       if (f != RTC_FORMAT_FLOAT3) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid vertex buffer format");
     } else if (t == RTC_BUFFER_TYPE_INDEX) {
       if (slot != 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid buffer slot");
-      if (f != RTC_FORMAT_UINT3) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid index buffer format");
-    } else if (t != RTC_BUFFER_TYPE_VERTEX_ATTRIBUTE)
-      RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown buffer type");
-    break;
-  case RTC_GEOMETRY_TYPE_QUAD: // QuadMesh::setBuffer (scene_quad_mesh.cpp)
-    if (t == RTC_BUFFER_TYPE_VERTEX) {
-      if (f != RTC_FORMAT_FLOAT3) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid vertex buffer format");
-    } else if (t == RTC_BUFFER_TYPE_INDEX) {
-      if (slot != 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid buffer slot");
-      if (f != RTC_FORMAT_UINT4) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid index buffer format");
+      if (f != (type == RTC_GEOMETRY_TYPE_QUAD ? RTC_FORMAT_UINT4 : RTC_FORMAT_UINT3)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid index buffer format");
     } else if (t != RTC_BUFFER_TYPE_VERTEX_ATTRIBUTE)
       RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown buffer type");
     break;
@@ -103,19 +95,25 @@ V3 Geometry::vertex(size_t i) const
   return V3(p[0], p[1], p[2]);
 }
 
-// TriangleMesh::valid (scene_triangle_mesh.h): indices in range and finite vertices
-bool Geometry::validTriangle(size_t i) const
+// the vertex test of TriangleMesh::valid / QuadMesh::valid: every index in range, every vertex finite and within FLT_LARGE
+static bool valid_vertices(const Geometry& g, const unsigned* idx, int n)
 {
-  unsigned idx[3];
-  triangle(i, idx);
-  const size_t nv = numVertices();
-  if (idx[0] >= nv || idx[1] >= nv || idx[2] >= nv) return false;
-  for (int k = 0; k < 3; k++) {
-    V3 p = vertex(idx[k]);
+  const size_t nv = g.numVertices();
+  for (int k = 0; k < n; k++) {
+    if (idx[k] >= nv) return false;
+    V3 p = g.vertex(idx[k]);
     if (!(std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z))) return false;
     if (fabsf(p.x) > 1.844e18f || fabsf(p.y) > 1.844e18f || fabsf(p.z) > 1.844e18f) return false; // FLT_LARGE
   }
   return true;
+}
+
+// TriangleMesh::valid (scene_triangle_mesh.h)
+bool Geometry::validTriangle(size_t i) const
+{
+  unsigned idx[3];
+  triangle(i, idx);
+  return valid_vertices(*this, idx, 3);
 }
 
 void Geometry::quad(size_t i, unsigned idx[4]) const
@@ -124,19 +122,12 @@ void Geometry::quad(size_t i, unsigned idx[4]) const
   idx[0] = p[0]; idx[1] = p[1]; idx[2] = p[2]; idx[3] = p[3];
 }
 
-// QuadMesh::valid (scene_quad_mesh.h:121-138): all four indices in range and finite vertices
+// QuadMesh::valid (scene_quad_mesh.h:121-138)
 bool Geometry::validQuad(size_t i) const
 {
   unsigned idx[4];
   quad(i, idx);
-  const size_t nv = numVertices();
-  for (int k = 0; k < 4; k++) {
-    if (idx[k] >= nv) return false;
-    V3 p = vertex(idx[k]);
-    if (!(std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z))) return false;
-    if (fabsf(p.x) > 1.844e18f || fabsf(p.y) > 1.844e18f || fabsf(p.z) > 1.844e18f) return false; // FLT_LARGE
-  }
-  return true;
+  return valid_vertices(*this, idx, 4);
 }
 
 // ---- Accel -------------------------------------------------------------------------------------------------
@@ -227,9 +218,7 @@ Scene::Scene(Device* d) : device(d) { device->retain(); }
 Scene::~Scene()
 {
   service_quiesce(device); // freeing device memory synchronises the device: do not wait for the resident service kernel's idle exit
-  triAccel.freeDevice();
-  quadAccel.freeDevice();
-  subdivAccel.freeDevice();
+  for (Accel* a : accels()) a->freeDevice();
   if (device->gpu >= 0) hipSetDevice(device->gpu);
   for (Geometry* g : geometries)
     if (g) g->release();
@@ -264,15 +253,74 @@ void Scene::detach(unsigned id)
 
 Geometry* Scene::get(unsigned id) const { return id < geometries.size() ? geometries[id] : nullptr; }
 
+// The frame of the triangle and quad builders: one BVH8 (block 4, min leaf 4, max leaf 28: bvh_builder_sah.cpp:651-658) over the valid
+// primitives, NV vertices each, of the scene's enabled geometries of `type`.  A leaf's records are appended to `recs` in leaf order:
+// fill(rec, v) writes the vertices into a zeroed record, geomID / primID are set here.  false (and `A` untouched): no primitive.
+template <int NV, class Rec, class Fill>
+static bool build_mesh_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* tooMany, std::vector<Rec>& recs, const Fill& fill)
+{
+  struct Src { unsigned geomID, primID; };
+  std::vector<Src> src;
+  std::vector<BuildPrim> bp;
+  // the index record of a primitive (UINT3 / UINT4), and its vertices
+  auto vertices = [](const Geometry* g, size_t i, V3* v) {
+    const unsigned* idx = (const unsigned*)g->view(RTC_BUFFER_TYPE_INDEX, 0)->at(i);
+    for (int k = 0; k < NV; k++) v[k] = g->vertex(idx[k]);
+  };
+  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
+    Geometry* g = s->geometries[gid];
+    if (!g || !g->enabled || g->type != type) continue;
+    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry is not supported by the device path");
+    const size_t n = g->numTriangles(); // index buffer records
+    for (size_t i = 0; i < n; i++) {
+      if (!(NV == 4 ? g->validQuad(i) : g->validTriangle(i))) continue;
+      V3 v[NV];
+      vertices(g, i, v);
+      BuildPrim p;
+      for (int k = 0; k < NV; k++) p.box.extend(v[k]);
+      p.id = (uint32_t)src.size();
+      src.push_back({gid, (unsigned)i});
+      bp.push_back(p);
+    }
+  }
+  if (bp.empty()) return false;
+  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, tooMany);
+
+  recs.reserve(bp.size());
+  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
+    const uint32_t first = (uint32_t)recs.size();
+    for (size_t i = begin; i < end; i++) {
+      const Src& sr = src[prims[i].id];
+      V3 v[NV];
+      vertices(s->geometries[sr.geomID], sr.primID, v);
+      Rec r;
+      memset(&r, 0, sizeof(r));
+      fill(r, v);
+      r.geomID = sr.geomID;
+      r.primID = sr.primID;
+      recs.push_back(r);
+    }
+    return make_tri_leaf(first, (uint32_t)(end - begin));
+  };
+  BuildSettings cfg;
+  cfg.threads = host_threads(s->device);
+  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
+  A.nodes = std::move(r.nodes);
+  A.root = r.root;
+  A.maxDepth = r.maxDepth;
+  A.leafCount = r.leafCount;
+  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  return true;
+}
+
 static void build_triangle_accel(Scene* s)
 {
-  Device* dev = s->device;
   Accel& A = s->triAccel;
   A.clear();
 
   // accel selection: scene.cpp:130-211.  Everything is served by the one BVH8 layout; the name only picks
   // the leaf arithmetic (Triangle4v/Pluecker/robust vs Triangle4/Moeller/fast).
-  const std::string& name = dev->tri_accel;
+  const std::string& name = s->device->tri_accel;
   bool pluecker;
   if (name == "default") pluecker = s->isRobust();
   else if (name == "bvh8.triangle4v" || name == "bvh4.triangle4v") pluecker = true;
@@ -281,63 +329,17 @@ static void build_triangle_accel(Scene* s)
   A.kind = pluecker ? ACCEL_TRI_PLUECKER : ACCEL_TRI_MOELLER;
   A.robust = pluecker ? 1 : 0;
 
-  struct Src { unsigned geomID, primID; };
-  std::vector<Src> src;
-  std::vector<BuildPrim> bp;
-  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
-    Geometry* g = s->geometries[gid];
-    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_TRIANGLE) continue;
-    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry is not supported by the device path");
-    const size_t nt = g->numTriangles();
-    for (size_t i = 0; i < nt; i++) {
-      if (!g->validTriangle(i)) continue;
-      unsigned idx[3];
-      g->triangle(i, idx);
-      BuildPrim p;
-      p.box.extend(g->vertex(idx[0]));
-      p.box.extend(g->vertex(idx[1]));
-      p.box.extend(g->vertex(idx[2]));
-      p.id = (uint32_t)src.size();
-      src.push_back({gid, (unsigned)i});
-      bp.push_back(p);
+  auto fill = [pluecker](TriRecord& t, const V3* v) {
+    t.ax = v[0].x; t.ay = v[0].y; t.az = v[0].z;
+    if (pluecker) {
+      t.bx = v[1].x; t.by = v[1].y; t.bz = v[1].z;
+      t.cx = v[2].x; t.cy = v[2].y; t.cz = v[2].z;
+    } else { // TriangleM ctor: e1 = v0-v1, e2 = v2-v0 (triangle.h:52-53)
+      t.bx = v[0].x - v[1].x; t.by = v[0].y - v[1].y; t.bz = v[0].z - v[1].z;
+      t.cx = v[2].x - v[0].x; t.cy = v[2].y - v[0].y; t.cz = v[2].z - v[0].z;
     }
-  }
-  if (bp.empty()) { A.kind = ACCEL_NONE; return; }
-  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many triangles for the 26-bit leaf reference");
-
-  A.prims.reserve(bp.size());
-  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
-    const uint32_t first = (uint32_t)A.prims.size();
-    for (size_t i = begin; i < end; i++) {
-      const Src& sr = src[prims[i].id];
-      Geometry* g = s->geometries[sr.geomID];
-      unsigned idx[3];
-      g->triangle(sr.primID, idx);
-      const V3 v0 = g->vertex(idx[0]), v1 = g->vertex(idx[1]), v2 = g->vertex(idx[2]);
-      TriRecord t;
-      memset(&t, 0, sizeof(t));
-      t.ax = v0.x; t.ay = v0.y; t.az = v0.z;
-      if (pluecker) {
-        t.bx = v1.x; t.by = v1.y; t.bz = v1.z;
-        t.cx = v2.x; t.cy = v2.y; t.cz = v2.z;
-      } else { // TriangleM ctor: e1 = v0-v1, e2 = v2-v0 (triangle.h:52-53)
-        t.bx = v0.x - v1.x; t.by = v0.y - v1.y; t.bz = v0.z - v1.z;
-        t.cx = v2.x - v0.x; t.cy = v2.y - v0.y; t.cz = v2.z - v0.z;
-      }
-      t.geomID = sr.geomID;
-      t.primID = sr.primID;
-      A.prims.push_back(t);
-    }
-    return make_tri_leaf(first, (uint32_t)(end - begin));
   };
-  BuildSettings cfg; // block 4, min leaf 4, max leaf 28 (bvh_builder_sah.cpp:651-658)
-  cfg.threads = host_threads(s->device);
-  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
-  A.nodes = std::move(r.nodes);
-  A.root = r.root;
-  A.maxDepth = r.maxDepth;
-  A.leafCount = r.leafCount;
-  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  if (!build_mesh_bvh8<3>(s, A, RTC_GEOMETRY_TYPE_TRIANGLE, "too many triangles for the 26-bit leaf reference", A.prims, fill)) A.kind = ACCEL_NONE;
 }
 
 // Quad meshes: one BVH8 over whole quads with the triangle settings; the records keep the four vertices (QuadMv) and go to the
@@ -345,70 +347,27 @@ static void build_triangle_accel(Scene* s)
 // Moeller + fast traversal otherwise; an explicit quad4v / quad4i accel is the fast (Moeller) variant.
 static void build_quad_accel(Scene* s)
 {
-  Device* dev = s->device;
   Accel& A = s->quadAccel;
   A.clear();
-  const std::string& name = dev->quad_accel;
+  const std::string& name = s->device->quad_accel;
   bool pluecker;
   if (name == "default") pluecker = s->isRobust();
   else if (name == "bvh8.quad4v" || name == "bvh4.quad4v" || name == "bvh8.quad4i" || name == "bvh4.quad4i" || name == "qbvh8.quad4i") pluecker = false;
   else RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown quad acceleration structure " + name);
 
-  struct Src { unsigned geomID, primID; };
-  std::vector<Src> src;
-  std::vector<BuildPrim> bp;
-  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
-    Geometry* g = s->geometries[gid];
-    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_QUAD) continue;
-    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry is not supported by the device path");
-    const size_t nq = g->numQuads();
-    for (size_t i = 0; i < nq; i++) {
-      if (!g->validQuad(i)) continue;
-      unsigned idx[4];
-      g->quad(i, idx);
-      BuildPrim p;
-      for (int k = 0; k < 4; k++) p.box.extend(g->vertex(idx[k]));
-      p.id = (uint32_t)src.size();
-      src.push_back({gid, (unsigned)i});
-      bp.push_back(p);
-    }
-  }
-  if (bp.empty()) return;
-  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many quads for the 26-bit leaf reference");
-  A.kind = pluecker ? ACCEL_QUAD_PLUECKER : ACCEL_QUAD_MOELLER;
+  std::vector<QuadRecord> recs;
+  auto fill = [](QuadRecord& q, const V3* v) {
+    q.v0x = v[0].x; q.v0y = v[0].y; q.v0z = v[0].z;
+    q.v1x = v[1].x; q.v1y = v[1].y; q.v1z = v[1].z;
+    q.v2x = v[2].x; q.v2y = v[2].y; q.v2z = v[2].z;
+    q.v3x = v[3].x; q.v3y = v[3].y; q.v3z = v[3].z;
+  };
+  if (!build_mesh_bvh8<4>(s, A, RTC_GEOMETRY_TYPE_QUAD, "too many quads for the 26-bit leaf reference", recs, fill)) return;
+  A.kind = pluecker ? ACCEL_QUAD_PLUECKER : ACCEL_QUAD_MOELLER; // only once there are quads
   A.robust = pluecker ? 1 : 0;
   A.blobStride = sizeof(QuadRecord);
-
-  std::vector<QuadRecord> recs;
-  recs.reserve(bp.size());
-  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
-    const uint32_t first = (uint32_t)recs.size();
-    for (size_t i = begin; i < end; i++) {
-      const Src& sr = src[prims[i].id];
-      Geometry* g = s->geometries[sr.geomID];
-      unsigned idx[4];
-      g->quad(sr.primID, idx);
-      const V3 v0 = g->vertex(idx[0]), v1 = g->vertex(idx[1]), v2 = g->vertex(idx[2]), v3 = g->vertex(idx[3]);
-      QuadRecord q;
-      memset(&q, 0, sizeof(q));
-      q.v0x = v0.x; q.v0y = v0.y; q.v0z = v0.z; q.geomID = sr.geomID;
-      q.v1x = v1.x; q.v1y = v1.y; q.v1z = v1.z; q.primID = sr.primID;
-      q.v2x = v2.x; q.v2y = v2.y; q.v2z = v2.z;
-      q.v3x = v3.x; q.v3y = v3.y; q.v3z = v3.z;
-      recs.push_back(q);
-    }
-    return make_tri_leaf(first, (uint32_t)(end - begin));
-  };
-  BuildSettings cfg; // the triangle settings: block 4, min leaf 4, max leaf 28
-  cfg.threads = host_threads(s->device);
-  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
-  A.nodes = std::move(r.nodes);
-  A.root = r.root;
-  A.maxDepth = r.maxDepth;
-  A.leafCount = r.leafCount;
   A.blobs.resize(recs.size() * sizeof(QuadRecord));
   memcpy(A.blobs.data(), recs.data(), A.blobs.size());
-  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
 }
 
 void Scene::commit()
@@ -439,9 +398,7 @@ void Scene::commit()
   build_triangle_accel(this);
   build_quad_accel(this);
   build_subdiv_accel(this);
-  triAccel.upload(device);
-  quadAccel.upload(device);
-  subdivAccel.upload(device);
+  for (Accel* a : accels()) a->upload(device);
   if (progressFn) progressFn(progressUser, 1.0);
   if (device->verbose >= 2) {
     fprintf(stderr, "embree3-amd: tri accel kind %u: %zu nodes (%zu B), %zu tris, depth %u; subdiv accel kind %u: %zu nodes, %zu blobs (%zu B)\n",

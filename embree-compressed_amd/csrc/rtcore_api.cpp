@@ -82,7 +82,7 @@ API ssize_t rtcGetDeviceProperty(RTCDevice h, enum RTCDeviceProperty prop)
   case RTC_DEVICE_PROPERTY_RAY_STREAM_SUPPORTED: return 1;
   case RTC_DEVICE_PROPERTY_RAY_MASK_SUPPORTED: return 0;          // EMBREE_RAY_MASK default OFF (CMakeLists.txt:114)
   case RTC_DEVICE_PROPERTY_BACKFACE_CULLING_ENABLED: return 0;    // CMakeLists.txt:115
-  case RTC_DEVICE_PROPERTY_FILTER_FUNCTION_SUPPORTED: return 1;   // host callbacks, two-phase (rt_trace.cpp, triangle geometry)
+  case RTC_DEVICE_PROPERTY_FILTER_FUNCTION_SUPPORTED: return 1;   // host callbacks, two-phase (rt_filter.cpp)
   case RTC_DEVICE_PROPERTY_IGNORE_INVALID_RAYS_ENABLED: return 0; // CMakeLists.txt:117
   case RTC_DEVICE_PROPERTY_TRIANGLE_GEOMETRY_SUPPORTED: return 1;
   case RTC_DEVICE_PROPERTY_QUAD_GEOMETRY_SUPPORTED: return D(h)->quads_enabled() ? 1 : 0;
@@ -774,7 +774,8 @@ API void rtcamdGetSceneStats(RTCScene h, struct RTCAMDSceneStats* st)
   st->primCount = tri ? A.prims.size() : (A.blobStride ? A.blobs.size() / A.blobStride : 0);
   st->primBytes = tri ? sizeof(TriRecord) : A.blobStride;
   st->leafCount = A.leafCount;
-  st->totalBytes = S(h)->triAccel.deviceBytes() + S(h)->quadAccel.deviceBytes() + S(h)->subdivAccel.deviceBytes();
+  st->totalBytes = 0;
+  for (const Accel* a : S(h)->accels()) st->totalBytes += a->deviceBytes();
   st->maxDepth = A.maxDepth;
   st->reserved = 0;
   CATCH_END(devOf(h))

@@ -7,7 +7,7 @@
 //   ComputeLinearEstimate/project kernels/geometry/compressed_help.h:54-90   (Eigen's 8x8 fullPivLu -> own full-pivot solve)
 //   Morton helpers                kernels/geometry/compressed_help.h:19-50
 // The codec functions below are shared with the unit tests through rtcamd test hooks; the DEVICE decode in
-// trace_subdiv.hip repeats cbvh_decode_child() operation for operation.
+// trace_cbvh.hip.h repeats cbvh_decode_child() operation for operation.
 #pragma once
 #include "accel.h"
 #include "subdiv_tess.h"

@@ -19,7 +19,7 @@ struct LaunchParams
   uint32_t spillDepth; // entries per lane available in `spill`
   uint32_t gridBlocks; // persistent grid size the spill area was sized for
   uint32_t cbvhLevels; // fork: depth C of every cBVH blob of the scene (rtcSetSceneLevels)
-  uint32_t cbvhLaneForm; // fork, lane kernel: 1 = walk blobs one ray per lane (coherent batches), 0 = quad form (trace_subdiv.hip)
+  uint32_t cbvhLaneForm; // fork, lane kernel: 1 = walk blobs one ray per lane (coherent batches), 0 = quad form (trace_cbvh.hip.h)
   WaveRecord* counters;    // non-null selects the instrumented kernel twin; one record per wavefront
   uint32_t numCUs;         // compute units of the device (persistent grid sizing)
   uint32_t rayChunk;       // rays per work-queue grab (tuning knob, env RTAMD_CHUNK)
@@ -84,9 +84,13 @@ struct ServiceParams
   uint32_t* activity;  // device word: jobs served by any wavefront
 };
 // start the service kernel for base.accel.kind (and base.cbvhLevels); hipErrorInvalidValue: no service kernel for this accel kind / level
-hipError_t launch_service_tri(const ServiceParams& s, hipStream_t stream);    // trace_tri.hip
-hipError_t launch_service_subdiv(const ServiceParams& s, hipStream_t stream); // trace_subdiv.hip
-hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream);   // trace_quad.hip
+hipError_t launch_service_tri(const ServiceParams& s, hipStream_t stream);       // trace_tri.hip
+hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream);      // trace_quad.hip
+hipError_t launch_service_grid(const ServiceParams& s, hipStream_t stream);      // trace_grid.hip
+hipError_t launch_service_cbvh_box(const ServiceParams& s, hipStream_t stream);  // trace_cbvh_box.hip  (one unit per cBVH mode:
+hipError_t launch_service_cbvh_leaf(const ServiceParams& s, hipStream_t stream); // trace_cbvh_leaf.hip  trace_cbvh.hip.h
+hipError_t launch_service_cbvh_grid(const ServiceParams& s, hipStream_t stream); // trace_cbvh_grid.hip  instantiated for
+hipError_t launch_service_cbvh_full(const ServiceParams& s, hipStream_t stream); // trace_cbvh_full.hip  that mode)
 
 static const int TRACE_QUEUES = 64;       // work queues per launch (must equal the wavefront width: one lane scans one head)
 static const int TRACE_QUEUE_STRIDE = 32; // u32 words between two work-queue heads (128 B: one L2 line each)
@@ -112,22 +116,30 @@ static const int TRACE_LDS_STACK = TRACE_LDS_STACK_ENTRIES; // stack entries per
 uint32_t trace_grid_blocks(uint32_t count, int numCUs, uint32_t rayChunk);
 
 // Enqueue traversal of one batch on `stream`.  Asynchronous; errors surface through the returned hipError_t.
-hipError_t launch_trace_tri(const LaunchParams& p, hipStream_t stream);    // trace_tri.hip
-hipError_t launch_cull(const LaunchParams& p, hipStream_t stream);         // trace_tri.hip (trace_cull.hip.h): root cull pre-pass
-hipError_t launch_trace_subdiv(const LaunchParams& p, hipStream_t stream); // trace_subdiv.hip
-hipError_t launch_trace_quad(const LaunchParams& p, hipStream_t stream);   // trace_quad.hip
+hipError_t launch_trace_tri(const LaunchParams& p, hipStream_t stream);       // trace_tri.hip
+hipError_t launch_cull(const LaunchParams& p, hipStream_t stream);            // trace_tri.hip (trace_cull.hip.h): root cull pre-pass
+hipError_t launch_trace_quad(const LaunchParams& p, hipStream_t stream);      // trace_quad.hip
+hipError_t launch_trace_grid(const LaunchParams& p, hipStream_t stream);      // trace_grid.hip
+hipError_t launch_trace_cbvh_box(const LaunchParams& p, hipStream_t stream);  // trace_cbvh_box.hip
+hipError_t launch_trace_cbvh_leaf(const LaunchParams& p, hipStream_t stream); // trace_cbvh_leaf.hip
+hipError_t launch_trace_cbvh_grid(const LaunchParams& p, hipStream_t stream); // trace_cbvh_grid.hip
+hipError_t launch_trace_cbvh_full(const LaunchParams& p, hipStream_t stream); // trace_cbvh_full.hip
+// Development builds (-DTRACE_DEV_METRIC_ONLY, tools/README.md): of the subdivision accels only the metric's kind is dispatched (the
+// others fail with hipErrorInvalidValue, so that only trace_cbvh_leaf.hip has to be rebuilt), and launch_service serves no other kind.
 inline hipError_t launch_service(const ServiceParams& s, hipStream_t stream)
 {
   switch (s.base.accel.kind) {
+#ifndef TRACE_DEV_METRIC_ONLY
   case ACCEL_TRI_PLUECKER:
   case ACCEL_TRI_MOELLER: return launch_service_tri(s, stream);
   case ACCEL_QUAD_PLUECKER:
   case ACCEL_QUAD_MOELLER: return launch_service_quad(s, stream);
-  case ACCEL_CBVH_BOX:
-  case ACCEL_CBVH_LEAF:
-  case ACCEL_CBVH_GRID:
-  case ACCEL_CBVH_FULL:
-  case ACCEL_GRIDSOA: return launch_service_subdiv(s, stream);
+  case ACCEL_GRIDSOA: return launch_service_grid(s, stream);
+  case ACCEL_CBVH_BOX: return launch_service_cbvh_box(s, stream);
+  case ACCEL_CBVH_GRID: return launch_service_cbvh_grid(s, stream);
+  case ACCEL_CBVH_FULL: return launch_service_cbvh_full(s, stream);
+#endif
+  case ACCEL_CBVH_LEAF: return launch_service_cbvh_leaf(s, stream);
   default: return hipErrorInvalidValue;
   }
 }
@@ -138,11 +150,18 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_TRI_MOELLER: return launch_trace_tri(p, stream);
   case ACCEL_QUAD_PLUECKER:
   case ACCEL_QUAD_MOELLER: return launch_trace_quad(p, stream);
+  case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
+#ifdef TRACE_DEV_METRIC_ONLY
+  case ACCEL_GRIDSOA:
   case ACCEL_CBVH_BOX:
-  case ACCEL_CBVH_LEAF:
   case ACCEL_CBVH_GRID:
-  case ACCEL_CBVH_FULL:
-  case ACCEL_GRIDSOA: return launch_trace_subdiv(p, stream);
+  case ACCEL_CBVH_FULL: return hipErrorInvalidValue;
+#else
+  case ACCEL_GRIDSOA: return launch_trace_grid(p, stream);
+  case ACCEL_CBVH_BOX: return launch_trace_cbvh_box(p, stream);
+  case ACCEL_CBVH_GRID: return launch_trace_cbvh_grid(p, stream);
+  case ACCEL_CBVH_FULL: return launch_trace_cbvh_full(p, stream);
+#endif
   default: return hipSuccess;
   }
 }

@@ -1,7 +1,5 @@
 // Subdivision-surface leaves of the quantized BVH8 on gfx950:
-//   GridCellLeaf   eager path: one 3x3-vertex cell = 8 Pluecker triangles with patch-uv mapping
-//                  (kernels/geometry/grid_soa_intersector1.h:44-117, Gather3x3 grid_soa.h:198-245, MapUV :137-156,
-//                   decodeUV :248-257, Intersect1EpilogMU intersector_epilog.h:460-530)
+//   GridCellLeaf   eager path: trace_grid.hip
 //   CbvhLeaf<MODE> fork path: traversal of one compressed per-sub-grid BVH blob
 //                  (kernels/geometry/compressed.h:454-752, node decode compressed_node.h:488-510,
 //                   helpers compressed_help.h:86-308, leaf z decode compressed_leaf.h:93-111)
@@ -12,211 +10,15 @@
 // that produced them (compressed.h:544-549,617); the traversal ray's tfar is never tightened (compressed.h:523).
 // Scalar arithmetic of the fork is written without fused operations (the reference leaves contraction to its
 // compiler; this path is "parity unpinned").
-#include "trace_loop.hip.h"
-#include "trace_pool.hip.h"
+// Each mode's kernels are instantiated by a translation unit of their own (trace_cbvh_box.hip, _leaf, _grid, _full): they are
+// independent of each other and compile in parallel.
+#pragma once
+#include "trace_leaf.hip.h"
 #include "trace_service.hip.h"
 
 namespace rtamd {
 namespace dev {
 
-// ---------------------------------------------------------------------------------------------------
-// eager: grid cell
-// ---------------------------------------------------------------------------------------------------
-struct RelV
-{
-  float x, y, z;
-};
-
-// Pluecker on vertices already relative to the ray origin; returns un-mapped barycentrics.
-__device__ __forceinline__ bool pluecker_rel(const RayState& r, const RelV a, const RelV b, const RelV c, float tfarBlock, TriHit& h)
-{
-  const float e0x = c.x - a.x, e0y = c.y - a.y, e0z = c.z - a.z;
-  const float e1x = a.x - b.x, e1y = a.y - b.y, e1z = a.z - b.z;
-  const float e2x = b.x - c.x, e2y = b.y - c.y, e2z = b.z - c.z;
-  float sx = c.x + a.x, sy = c.y + a.y, sz = c.z + a.z;
-  const float U = dot3(msub(e0y, sz, e0z * sy), msub(e0z, sx, e0x * sz), msub(e0x, sy, e0y * sx), r.dx, r.dy, r.dz);
-  sx = a.x + b.x; sy = a.y + b.y; sz = a.z + b.z;
-  const float V = dot3(msub(e1y, sz, e1z * sy), msub(e1z, sx, e1x * sz), msub(e1x, sy, e1y * sx), r.dx, r.dy, r.dz);
-  sx = b.x + c.x; sy = b.y + c.y; sz = b.z + c.z;
-  const float W = dot3(msub(e2y, sz, e2z * sy), msub(e2z, sx, e2x * sz), msub(e2x, sy, e2y * sx), r.dx, r.dy, r.dz);
-  const float minUVW = fminf(fminf(U, V), W);
-  const float maxUVW = fmaxf(fmaxf(U, V), W);
-  if (!((minUVW >= 0.0f) | (maxUVW <= 0.0f))) return false;
-  const float ab_x = e0z * e1y, ab_y = e0x * e1z, ab_z = e0y * e1x;
-  const float bc_x = e1z * e2y, bc_y = e1x * e2z, bc_z = e1y * e2x;
-  const float cab_x = msub(e0y, e1z, ab_x), cab_y = msub(e0z, e1x, ab_y), cab_z = msub(e0x, e1y, ab_z);
-  const float cbc_x = msub(e1y, e2z, bc_x), cbc_y = msub(e1z, e2x, bc_y), cbc_z = msub(e1x, e2y, bc_z);
-  const float ngx = fabsf(ab_x) < fabsf(bc_x) ? cab_x : cbc_x;
-  const float ngy = fabsf(ab_y) < fabsf(bc_y) ? cab_y : cbc_y;
-  const float ngz = fabsf(ab_z) < fabsf(bc_z) ? cab_z : cbc_z;
-  const float dn = dot3(ngx, ngy, ngz, r.dx, r.dy, r.dz);
-  const float den = dn + dn;
-  const float absDen = fabsf(den);
-  const uint32_t sgnDen = __float_as_uint(den) & 0x80000000u;
-  const float tn = dot3(a.x, a.y, a.z, ngx, ngy, ngz);
-  const float T = tn + tn;
-  const float Ts = xorf(T, sgnDen);
-  if (!(absDen * r.tnear < Ts)) return false;
-  if (!(Ts <= absDen * tfarBlock)) return false;
-  if (!(den != 0.0f)) return false;
-  const float rcpDen = 1.0f / den;
-  h.t = T * rcpDen;
-  const float UVW = U + V + W;
-  const float rcpUVW = fabsf(UVW) < 1e-18f ? 0.0f : 1.0f / UVW;
-  h.u = U * rcpUVW;
-  h.v = V * rcpUVW;
-  h.ngx = ngx; h.ngy = ngy; h.ngz = ngz;
-  return true;
-}
-
-// Filter re-trace (row f3, LaunchParams::exclOffsets): a triangle of patch (geomID, primID) whose distance is bit-equal to one the
-// host filter rejected for this ray in an earlier round stays rejected (Intersect1EpilogMU offers the candidates of a cell one by
-// one, intersector_epilog.h:488-509; here the host does, between passes).
-__device__ __forceinline__ bool cell_candidate_excluded(const LaunchParams& P, uint32_t rayIdx, uint32_t geomID, uint32_t primID, float t)
-{
-  const uint32_t e1 = P.exclOffsets[rayIdx + 1];
-  for (uint32_t e = P.exclOffsets[rayIdx]; e < e1; e++) {
-    const uint2 q = P.exclPairs[e];
-    if (q.x == geomID && q.y == primID && P.exclT[e] == __float_as_uint(t)) return true;
-  }
-  return false;
-}
-
-struct GridCellLeaf
-{
-  static constexpr bool OCTET = true;
-  static constexpr bool OCTET_ONLY = true; // lane kernel: cells are always tested 8 lanes per ray (intersect() below serves the ray-pool kernel)
-  static constexpr int GROUP = 8;
-  static constexpr bool HIT_IN_MEMORY = false;
-  static constexpr bool CONST_NG = false;
-  static constexpr int MIN_WAVES = TRACE_MIN_WAVES_PER_SIMD;
-  static __device__ __forceinline__ bool octet_ok(const LaunchParams&) { return true; }
-  static __device__ __forceinline__ void prepare() {}
-
-  // Child-parallel form (trace_loop.hip.h): lane 8g+k tests triangle k of the cell of the ray in exchange row `x`
-  // (words 0..7 = org, tnear, dir, tfar; word 8 = leaf ref).  Same vertex differences, same Pluecker test against the tfar
-  // at cell entry, same winner (minimum t, lowest triangle on ties, select_min vfloat4_sse2.h:654-659) as intersect()
-  // below; the winning lane maps uv and writes the hit into the row (words 0..7 = t, Ng, u, v, geomID, primID; word 9 = 1).
-  template <bool OCCLUDED, bool COUNT>
-  static __device__ __forceinline__ void octet_pass(const LaunchParams& P, float* x, bool valid, uint32_t lid, WorkCounters& wc)
-  {
-    const uint32_t k = lid & 7u;
-    RayState r;
-    r.ox = x[0]; r.oy = x[1]; r.oz = x[2]; r.tnear = x[3];
-    r.dx = x[4]; r.dy = x[5]; r.dz = x[6]; r.tfar = x[7];
-    const uint32_t idx = __float_as_uint(x[8]) & 0x7FFFFFFFu;
-    const float* gp = (const float*)(P.accel.blobs + (size_t)idx * sizeof(GridCell));
-    // Gather3x3 lane -> vertex indices (grid_soa.h:218-223), one nibble per triangle
-    const uint32_t i0 = (0x74634130u >> (4u * k)) & 15u, i1 = (0x55442211u >> (4u * k)) & 15u, i2 = (0x87765443u >> (4u * k)) & 15u;
-    const RelV a = RelV{gp[i0] - r.ox, gp[9u + i0] - r.oy, gp[18u + i0] - r.oz};
-    const RelV b = RelV{gp[i1] - r.ox, gp[9u + i1] - r.oy, gp[18u + i1] - r.oz};
-    const RelV c = RelV{gp[i2] - r.ox, gp[9u + i2] - r.oy, gp[18u + i2] - r.oz};
-    TriHit h;
-    h.t = RT_INF;
-    bool ok = pluecker_rel(r, a, b, c, r.tfar, h) && valid;
-    if (ok && P.exclOffsets) ok = !cell_candidate_excluded(P, __float_as_uint(x[10]), __float_as_uint(gp[36]), __float_as_uint(gp[37]), h.t);
-    const uint32_t mask8 = (uint32_t)(__ballot(ok) >> (lid & 56u)) & 0xffu;
-    if (COUNT && valid && k == 0u) {
-      wc.prims++;
-      wc.inner += (OCCLUDED && mask8) ? (unsigned long long)__ffs(mask8) : 8ull; // the lane-per-ray any-hit loop stops at the first valid triangle
-    }
-    if (OCCLUDED) {
-      if (valid && k == 0u && mask8 != 0u) x[9] = __uint_as_float(1u);
-      return;
-    }
-    float tmin = ok ? h.t : RT_INF;
-    tmin = fminf(tmin, __uint_as_float(dpp_u32<DPP_XOR1>(__float_as_uint(tmin))));
-    tmin = fminf(tmin, __uint_as_float(dpp_u32<DPP_XOR2>(__float_as_uint(tmin))));
-    tmin = fminf(tmin, __uint_as_float(dpp_u32<DPP_HALF_MIRROR>(__float_as_uint(tmin))));
-    const uint32_t win8 = (uint32_t)(__ballot(ok && h.t == tmin) >> (lid & 56u)) & 0xffu;
-    if (ok && win8 != 0u && k == (uint32_t)__ffs(win8) - 1u) {
-      // MapUV (grid_soa.h:148-155): uv = u*uv1 + v*uv2 + (1-u-v)*uv0 on the 16-bit decoded vertex uvs
-      const uint32_t w0 = __float_as_uint(gp[27u + i0]), w1 = __float_as_uint(gp[27u + i1]), w2 = __float_as_uint(gp[27u + i2]);
-      const float s = 8.0f / 0x10000;
-      const float u0 = (float)(w0 & 0xffffu) * s, v0 = (float)(w0 >> 16) * s;
-      const float u1 = (float)(w1 & 0xffffu) * s, v1 = (float)(w1 >> 16) * s;
-      const float u2 = (float)(w2 & 0xffffu) * s, v2 = (float)(w2 >> 16) * s;
-      const float bu = h.u, bv = h.v;
-      const float bw = (1.0f - bu) - bv;
-      x[0] = h.t; x[1] = h.ngx; x[2] = h.ngy; x[3] = h.ngz;
-      x[4] = (bu * u1 + bv * u2) + bw * u0;
-      x[5] = (bu * v1 + bv * v2) + bw * v0;
-      x[6] = gp[36];
-      x[7] = gp[37];
-      x[9] = __uint_as_float(1u);
-    }
-  }
-
-  template <bool OCCLUDED, bool COUNT>
-  static __device__ __forceinline__ bool intersect(const LaunchParams& P, uint32_t ref, RayState& r, WorkCounters& wc, uint32_t rayIdx)
-  {
-    const uint32_t idx = ref & 0x7FFFFFFFu;
-    const float4* gp = (const float4*)(P.accel.blobs + (size_t)idx * sizeof(GridCell));
-    float f[40];
-#pragma unroll
-    for (int k = 0; k < 10; k++) {
-      const float4 q = gp[k];
-      f[4 * k] = q.x; f[4 * k + 1] = q.y; f[4 * k + 2] = q.z; f[4 * k + 3] = q.w;
-    }
-    if (COUNT) wc.prims++;
-    // f[0..8] px, f[9..17] py, f[18..26] pz, f[27..35] packed uv, f[36] geomID, f[37] primID
-    RelV p[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) p[k] = RelV{f[k] - r.ox, f[9 + k] - r.oy, f[18 + k] - r.oz};
-    // Gather3x3 lane -> (v0,v1,v2) vertex indices r*3+c (grid_soa.h:218-223)
-    constexpr int T0[8] = {0, 3, 1, 4, 3, 6, 4, 7};
-    constexpr int T1[8] = {1, 1, 2, 2, 4, 4, 5, 5};
-    constexpr int T2[8] = {3, 4, 4, 5, 6, 7, 7, 8};
-    const float tfarBlock = r.tfar;
-    bool found = false;
-    TriHit best;
-    best.t = RT_INF;
-    int bestLane = 0;
-#pragma unroll
-    for (int l = 0; l < 8; l++) {
-      if (COUNT) wc.inner++;
-      TriHit h;
-      if (pluecker_rel(r, p[T0[l]], p[T1[l]], p[T2[l]], tfarBlock, h)) {
-        if (P.exclOffsets && cell_candidate_excluded(P, rayIdx, __float_as_uint(f[36]), __float_as_uint(f[37]), h.t)) continue;
-        if (OCCLUDED) return true;
-        if (!found || h.t < best.t) { // select_min: lowest lane among equal minima
-          best = h;
-          bestLane = l;
-          found = true;
-        }
-      }
-    }
-    if (found) {
-      // MapUV (grid_soa.h:148-155): uv = u*uv1 + v*uv2 + (1-u-v)*uv0 on the 16-bit decoded vertex uvs
-      uint32_t w0 = 0, w1 = 0, w2 = 0;
-#pragma unroll
-      for (int l = 0; l < 8; l++)
-        if (l == bestLane) {
-          w0 = __float_as_uint(f[27 + T0[l]]);
-          w1 = __float_as_uint(f[27 + T1[l]]);
-          w2 = __float_as_uint(f[27 + T2[l]]);
-        }
-      const float s = 8.0f / 0x10000;
-      const float u0 = (float)(w0 & 0xffffu) * s, v0 = (float)(w0 >> 16) * s;
-      const float u1 = (float)(w1 & 0xffffu) * s, v1 = (float)(w1 >> 16) * s;
-      const float u2 = (float)(w2 & 0xffffu) * s, v2 = (float)(w2 >> 16) * s;
-      const float bu = best.u, bv = best.v;
-      const float bw = (1.0f - bu) - bv;
-      r.u = (bu * u1 + bv * u2) + bw * u0;
-      r.v = (bu * v1 + bv * v2) + bw * v0;
-      r.tfar = best.t;
-      r.ngx = best.ngx; r.ngy = best.ngy; r.ngz = best.ngz;
-      r.geomID = __float_as_uint(f[36]);
-      r.primID = __float_as_uint(f[37]);
-      r.hit = 1u;
-    }
-    return false;
-  }
-};
-
-// ---------------------------------------------------------------------------------------------------
-// fork: cBVH blob
-// ---------------------------------------------------------------------------------------------------
 // MODE_FULL (subdiv_accel=bvh4.compressed.full, compressed.h:40,774): the box mode's cells and hits over quadtree nodes that hold
 // their four child boxes as floats (96 B, plane-major: lx[4] ux[4] ly[4] uy[4] lz[4] uz[4]) instead of a 4-byte code of planes
 // relative to the parent box - nothing to decode and nothing inherited from the parent, so a descent carries only the node index.
@@ -231,9 +33,9 @@ enum { MODE_BOX = 0, MODE_LEAF = 1, MODE_GRID = 2, MODE_FULL = 3 };
 // Node decode tables (compressed_node.h:488-510): border planes, mid planes, and their complements 1-x (the same
 // fp32 subtraction the reference performs per decode, done once).  They live in LDS: a lookup is one ds_read (~100
 // cycles) instead of a global load per plane; with eight lookups per node and up to five dependent levels per blob the
-// global-memory version put several extra L1/L2 round trips on every ray's critical path.
-__constant__ float c_tblBorder[8] = {0.000f, 0.005f, 0.010f, 0.050f, 0.100f, 0.200f, 0.400f, 0.600f};
-__constant__ float c_tblMid[8] = {0.00f, 0.40f, 0.48f, 0.49f, 0.50f, 0.51f, 0.52f, 0.60f};
+// global-memory version put several extra L1/L2 round trips on every ray's critical path.  (static: one copy per mode's unit)
+static __constant__ float c_tblBorder[8] = {0.000f, 0.005f, 0.010f, 0.050f, 0.100f, 0.200f, 0.400f, 0.600f};
+static __constant__ float c_tblMid[8] = {0.00f, 0.40f, 0.48f, 0.49f, 0.50f, 0.51f, 0.52f, 0.60f};
 enum { TBL_BORDER = 0, TBL_MID = 8, TBL_ONE_MINUS_MID = 16, TBL_ONE_MINUS_BORDER = 24 };
 __device__ __forceinline__ float* cbvh_tables()
 {
@@ -605,7 +407,6 @@ __device__ __forceinline__ void cbvh_node(CbvhCtx& c, uint32_t curr, uint32_t w,
 // first, compressed.h:690-749) and every quirk are those of the lane-per-ray form - which the ray-pool kernel still runs, so the
 // two are compared byte for byte by tests/test_gpu_properties.py - hence of the reference.
 enum : int { DPP_Q0 = 0x00, DPP_Q1 = 0x55, DPP_Q2 = 0xAA, DPP_Q3 = 0xFF }; // quad_perm: broadcast lane 0..3 of the quad
-template <int CTRL> __device__ __forceinline__ float dpp_f32(float v) { return __uint_as_float(dpp_u32<CTRL>(__float_as_uint(v))); }
 // value `v` of lane `src` (0..3, uniform within the quad) of this lane's quad
 __device__ __forceinline__ uint32_t quad_get(uint32_t v, uint32_t src, uint32_t lid)
 {
@@ -808,9 +609,7 @@ template <int MODE, int LEVELS, bool QUAD = true> struct CbvhLeaf
   {
     if (!valid) return; // uniform within the quad
     const uint32_t q = lid & 3u;
-    RayState r;
-    r.ox = x[0]; r.oy = x[1]; r.oz = x[2]; r.tnear = x[3];
-    r.dx = x[4]; r.dy = x[5]; r.dz = x[6]; r.tfar = x[7];
+    const RayState r = row_ray(x);
     const uint32_t idx = __float_as_uint(x[8]) & 0x7FFFFFFFu;
     const CbvhHeader* H = (const CbvhHeader*)(P.accel.blobs + (size_t)idx * P.accel.blobStride);
     float lox, loy, loz, ldx, ldy, ldz, near, far;
@@ -825,9 +624,7 @@ template <int MODE, int LEVELS, bool QUAD = true> struct CbvhLeaf
   {
     if (!valid) return; // uniform within the quad
     const uint32_t q = lid & 3u;
-    RayState r;
-    r.ox = x[0]; r.oy = x[1]; r.oz = x[2]; r.tnear = x[3];
-    r.dx = x[4]; r.dy = x[5]; r.dz = x[6]; r.tfar = x[7];
+    RayState r = row_ray(x);
     r.hit = 0u;
     const uint32_t idx = __float_as_uint(x[8]) & 0x7FFFFFFFu;
     const CbvhHeader* H = (const CbvhHeader*)(P.accel.blobs + (size_t)idx * P.accel.blobStride);
@@ -1032,85 +829,51 @@ template <int MODE, int LEVELS, bool QUAD = true> struct CbvhLeaf
   }
 };
 
-template <int MODE> hipError_t launch_cbvh(const LaunchParams& p, hipStream_t stream, uint32_t levels)
+// one kernel per compression level C = 1..5 of the scene (rtcSetSceneLevels)
+template <typename Leaf, bool POOL> inline hipError_t launch_cbvh_policy(const LaunchParams& p, hipStream_t stream)
 {
-#ifdef TRACE_DEV_METRIC_ONLY
-  // Development builds (`make OUT=lib_wdev EXTRA=-DTRACE_DEV_METRIC_ONLY`, with the other objects copied from lib/: seconds instead of four
-  // minutes): only the metric's kernel is instantiated - cbvh.leaf, C = 3, quad form.  Everything else fails with hipErrorInvalidValue.
-  if constexpr (MODE == MODE_LEAF) { if (levels == 3 && !p.poolKernel && !p.cbvhLaneForm) return launch_leaf<CbvhLeaf<MODE, 3, true>, true>(p, stream); }
-  return hipErrorInvalidValue;
-#else
-  if (p.poolKernel) switch (levels) {
-    case 1: return launch_leaf_pool<CbvhLeaf<MODE, 1, false>, true>(p, stream);
-    case 2: return launch_leaf_pool<CbvhLeaf<MODE, 2, false>, true>(p, stream);
-    case 3: return launch_leaf_pool<CbvhLeaf<MODE, 3, false>, true>(p, stream);
-    case 4: return launch_leaf_pool<CbvhLeaf<MODE, 4, false>, true>(p, stream);
-    case 5: return launch_leaf_pool<CbvhLeaf<MODE, 5, false>, true>(p, stream);
-    default: return hipErrorInvalidValue;
-    }
-  if (p.cbvhLaneForm) switch (levels) { // coherent batches: one ray per lane
-    case 1: return launch_leaf<CbvhLeaf<MODE, 1, false>, true>(p, stream);
-    case 2: return launch_leaf<CbvhLeaf<MODE, 2, false>, true>(p, stream);
-    case 3: return launch_leaf<CbvhLeaf<MODE, 3, false>, true>(p, stream);
-    case 4: return launch_leaf<CbvhLeaf<MODE, 4, false>, true>(p, stream);
-    case 5: return launch_leaf<CbvhLeaf<MODE, 5, false>, true>(p, stream);
-    default: return hipErrorInvalidValue;
-    }
-  switch (levels) {
-  case 1: return launch_leaf<CbvhLeaf<MODE, 1, true>, true>(p, stream);
-  case 2: return launch_leaf<CbvhLeaf<MODE, 2, true>, true>(p, stream);
-  case 3: return launch_leaf<CbvhLeaf<MODE, 3, true>, true>(p, stream);
-  case 4: return launch_leaf<CbvhLeaf<MODE, 4, true>, true>(p, stream);
-  case 5: return launch_leaf<CbvhLeaf<MODE, 5, true>, true>(p, stream);
+  if constexpr (POOL) return launch_leaf_pool<Leaf, true>(p, stream);
+  else return launch_leaf<Leaf, true>(p, stream);
+}
+template <int MODE, bool QUAD, bool POOL> inline hipError_t launch_cbvh_levels(const LaunchParams& p, hipStream_t stream)
+{
+  switch (p.cbvhLevels) {
+  case 1: return launch_cbvh_policy<CbvhLeaf<MODE, 1, QUAD>, POOL>(p, stream);
+  case 2: return launch_cbvh_policy<CbvhLeaf<MODE, 2, QUAD>, POOL>(p, stream);
+  case 3: return launch_cbvh_policy<CbvhLeaf<MODE, 3, QUAD>, POOL>(p, stream);
+  case 4: return launch_cbvh_policy<CbvhLeaf<MODE, 4, QUAD>, POOL>(p, stream);
+  case 5: return launch_cbvh_policy<CbvhLeaf<MODE, 5, QUAD>, POOL>(p, stream);
   default: return hipErrorInvalidValue;
   }
+}
+
+template <int MODE> inline hipError_t launch_cbvh(const LaunchParams& p, hipStream_t stream)
+{
+#ifdef TRACE_DEV_METRIC_ONLY
+  // Development builds (`make OUT=lib_wdev EXTRA=-DTRACE_DEV_METRIC_ONLY`, with the other objects copied from lib/): only the metric's
+  // kernel is instantiated - cbvh.leaf, C = 3, quad form.  Everything else fails with hipErrorInvalidValue (trace.h dispatches nothing else).
+  if constexpr (MODE == MODE_LEAF) { if (p.cbvhLevels == 3 && !p.poolKernel && !p.cbvhLaneForm) return launch_leaf<CbvhLeaf<MODE, 3, true>, true>(p, stream); }
+  return hipErrorInvalidValue;
+#else
+  if (p.poolKernel) return launch_cbvh_levels<MODE, false, true>(p, stream);
+  if (p.cbvhLaneForm) return launch_cbvh_levels<MODE, false, false>(p, stream); // coherent batches: one ray per lane
+  return launch_cbvh_levels<MODE, true, false>(p, stream);
 #endif
 }
 
-} // namespace dev
-
-// service kernels (trace_service.hip.h): grid cells, and the fork's four modes in the quad form at the compression levels the tutorials use
-// (C = 2: the framework's default, 3: bomberman.ecs, 4: displacement_geometry); other levels keep the call combiner
-template <int MODE> static hipError_t launch_service_cbvh(const ServiceParams& s, hipStream_t stream)
+// service kernels (trace_service.hip.h): the quad form at the compression levels the tutorials use (C = 2: the framework's default,
+// 3: bomberman.ecs, 4: displacement_geometry); other levels keep the call combiner
+template <int MODE> inline hipError_t launch_service_cbvh(const ServiceParams& s, hipStream_t stream)
 {
   switch (s.base.cbvhLevels) {
 #ifndef TRACE_DEV_METRIC_ONLY
-  case 2: return dev::launch_service_kernel<dev::CbvhLeaf<MODE, 2, true>, true>(s, stream);
-  case 4: return dev::launch_service_kernel<dev::CbvhLeaf<MODE, 4, true>, true>(s, stream);
+  case 2: return launch_service_kernel<CbvhLeaf<MODE, 2, true>, true>(s, stream);
+  case 4: return launch_service_kernel<CbvhLeaf<MODE, 4, true>, true>(s, stream);
 #endif
-  case 3: return dev::launch_service_kernel<dev::CbvhLeaf<MODE, 3, true>, true>(s, stream);
+  case 3: return launch_service_kernel<CbvhLeaf<MODE, 3, true>, true>(s, stream);
   default: return hipErrorInvalidValue;
   }
 }
 
-hipError_t launch_service_subdiv(const ServiceParams& s, hipStream_t stream)
-{
-  switch (s.base.accel.kind) {
-#ifndef TRACE_DEV_METRIC_ONLY
-  case ACCEL_GRIDSOA: return dev::launch_service_kernel<dev::GridCellLeaf, true>(s, stream);
-  case ACCEL_CBVH_BOX: return launch_service_cbvh<dev::MODE_BOX>(s, stream);
-  case ACCEL_CBVH_GRID: return launch_service_cbvh<dev::MODE_GRID>(s, stream);
-  case ACCEL_CBVH_FULL: return launch_service_cbvh<dev::MODE_FULL>(s, stream);
-#endif
-  case ACCEL_CBVH_LEAF: return launch_service_cbvh<dev::MODE_LEAF>(s, stream);
-  default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_trace_subdiv(const LaunchParams& p, hipStream_t stream)
-{
-  switch (p.accel.kind) {
-#ifndef TRACE_DEV_METRIC_ONLY
-  case ACCEL_GRIDSOA:
-    if (p.poolKernel) return dev::launch_leaf_pool<dev::GridCellLeaf, true>(p, stream);
-    return dev::launch_leaf<dev::GridCellLeaf, true>(p, stream);
-#endif
-  case ACCEL_CBVH_BOX: return dev::launch_cbvh<dev::MODE_BOX>(p, stream, p.cbvhLevels);
-  case ACCEL_CBVH_LEAF: return dev::launch_cbvh<dev::MODE_LEAF>(p, stream, p.cbvhLevels);
-  case ACCEL_CBVH_GRID: return dev::launch_cbvh<dev::MODE_GRID>(p, stream, p.cbvhLevels);
-  case ACCEL_CBVH_FULL: return dev::launch_cbvh<dev::MODE_FULL>(p, stream, p.cbvhLevels);
-  default: return hipErrorInvalidValue;
-  }
-}
-
+} // namespace dev
 } // namespace rtamd

@@ -1,0 +1,9 @@
+// Fork path, subdiv_accel=bvh4.compressed.grid: the trace and service kernels of CbvhLeaf<MODE_GRID> (trace_cbvh.hip.h), a translation unit of their own.
+#include "trace_cbvh.hip.h"
+
+namespace rtamd {
+
+hipError_t launch_trace_cbvh_grid(const LaunchParams& p, hipStream_t stream) { return dev::launch_cbvh<dev::MODE_GRID>(p, stream); }
+hipError_t launch_service_cbvh_grid(const ServiceParams& s, hipStream_t stream) { return dev::launch_service_cbvh<dev::MODE_GRID>(s, stream); }
+
+} // namespace rtamd

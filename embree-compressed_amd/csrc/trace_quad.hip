@@ -7,8 +7,7 @@
 // Hits on a B triangle report the quad's parametrisation and the negated triangle normal; the u / v mapping differs per variant:
 //   Pluecker  u = 1 - v_tri, v = 1 - u_tri after the division (QuadHitPlueckerM::finalize, the AVX branch, pluecker.h:45-66)
 //   Moeller   U' = absDen - V, V' = absDen - U before the division by absDen (quad_intersector_moeller.h:268-282)
-#include "trace_loop.hip.h"
-#include "trace_pool.hip.h"
+#include "trace_leaf.hip.h"
 #include "trace_service.hip.h"
 
 namespace rtamd {
@@ -63,30 +62,12 @@ __device__ __forceinline__ bool pluecker_quad(const RayState& r, const float4 a,
   return true;
 }
 
-// Filter re-trace (LaunchParams::exclOffsets): both triangles of a quad carry the quad's (geomID, primID), so a rejected candidate
-// is identified by its distance as well (exclT, the scheme of the grid cells).  A ray through the diagonal v1-v3 hits A and B at a
-// bit-identical t: rejecting one rejects both, where the reference would offer B after A.
-__device__ __forceinline__ bool quad_candidate_excluded(const LaunchParams& P, uint32_t rayIdx, uint32_t geomID, uint32_t primID, float t)
+// Filter re-trace (candidate_excluded with the distance, trace_leaf.hip.h): both triangles of a quad carry the quad's (geomID,
+// primID).  A ray through the diagonal v1-v3 hits A and B at a bit-identical t: rejecting one rejects both, where the reference
+// would offer B after A.
+template <bool PLUECKER> struct QuadLeaf : LeafTraits // both forms in the lane kernel, as for triangle leaves (trace_tri.hip)
 {
-  const uint32_t e1 = P.exclOffsets[rayIdx + 1];
-  for (uint32_t e = P.exclOffsets[rayIdx]; e < e1; e++) {
-    const uint2 q = P.exclPairs[e];
-    if (q.x == geomID && q.y == primID && P.exclT[e] == __float_as_uint(t)) return true;
-  }
-  return false;
-}
-
-template <bool PLUECKER> struct QuadLeaf
-{
-  static constexpr bool OCTET = true;
-  static constexpr bool CONST_NG = false;
-  static constexpr int GROUP = 8;
-  static constexpr bool HIT_IN_MEMORY = false;
-  static constexpr bool OCTET_ONLY = false; // both forms, as for triangle leaves (trace_tri.hip)
-  static constexpr int MIN_WAVES = TRACE_MIN_WAVES_PER_SIMD;
   static constexpr uint32_t FETCH = PLUECKER ? QUAD_FETCH_PLUECKER : QUAD_FETCH_MOELLER;
-  static __device__ __forceinline__ bool octet_ok(const LaunchParams&) { return true; }
-  static __device__ __forceinline__ void prepare() {}
 
   static __device__ __forceinline__ bool test(const RayState& r, const float4 a, const float4 b, const float4 c, float tfar, bool flip, TriHit& h)
   {
@@ -102,9 +83,7 @@ template <bool PLUECKER> struct QuadLeaf
     const QuadRecord* __restrict__ quads = (const QuadRecord*)P.accel.blobs;
     const uint32_t k = lid & 7u, sh = lid & 56u;
     const bool isB = k >= 4u;
-    RayState r;
-    r.ox = x[0]; r.oy = x[1]; r.oz = x[2]; r.tnear = x[3];
-    r.dx = x[4]; r.dy = x[5]; r.dz = x[6]; r.tfar = x[7];
+    const RayState r = row_ray(x);
     const uint32_t ref = __float_as_uint(x[8]);
     const uint32_t first = ref & ((1u << TRI_START_BITS) - 1u);
     uint32_t cnt = valid ? (ref >> TRI_START_BITS) & 31u : 0u;
@@ -120,7 +99,7 @@ template <bool PLUECKER> struct QuadLeaf
       TriHit h;
       h.t = RT_INF; h.Ts = 0.f; h.absDen = 0.f;
       bool ok = test(r, V0, V1, V3, tfar, isB, h) && present;
-      if (ok && P.exclOffsets) ok = !quad_candidate_excluded(P, __float_as_uint(x[10]), isB ? geomID : __float_as_uint(V0.w), primID, h.t);
+      if (ok && P.exclOffsets) ok = !candidate_excluded(P, __float_as_uint(x[10]), isB ? geomID : __float_as_uint(V0.w), primID, h.t);
       const uint32_t m8 = (uint32_t)(__ballot(ok) >> sh) & 0xffu;
       if (OCCLUDED) { // Occluded1EpilogM: any valid lane
         if (m8 != 0u) {
@@ -129,10 +108,8 @@ template <bool PLUECKER> struct QuadLeaf
         }
         continue;
       }
-      float tm = ok ? h.t : RT_INF;
-      tm = fminf(tm, __uint_as_float(dpp_u32<DPP_XOR1>(__float_as_uint(tm))));
-      tm = fminf(tm, __uint_as_float(dpp_u32<DPP_XOR2>(__float_as_uint(tm))));
-      tm = fminf(tm, __uint_as_float(dpp_u32<DPP_HALF_MIRROR>(__float_as_uint(tm)))); // minimum of the 8 lanes, in all 8
+      const float tm = octet_min8(ok ? h.t : RT_INF);
+      // (octet_ballot, row_write_hit and leaf_range change the instruction schedule of this leaf's octet form: written out)
       const uint32_t w = (uint32_t)(__ballot(ok && h.t == tm) >> sh) & 0xffu;
       const uint32_t winner = w != 0u ? (uint32_t)__ffs(w) - 1u : 8u;
       if (k == winner) { // Intersect1EpilogM, intersector_epilog.h:293-305
@@ -151,8 +128,8 @@ template <bool PLUECKER> struct QuadLeaf
   static __device__ __forceinline__ bool intersect(const LaunchParams& P, uint32_t ref, RayState& r, WorkCounters& wc, uint32_t rayIdx)
   {
     const QuadRecord* __restrict__ quads = (const QuadRecord*)P.accel.blobs;
-    const uint32_t first = ref & ((1u << TRI_START_BITS) - 1u);
-    const uint32_t count = (ref >> TRI_START_BITS) & 31u;
+    uint32_t first, count;
+    leaf_range(ref, first, count);
     for (uint32_t b = 0; b < count; b += 4) {
       const float tfarBlock = r.tfar;
       const uint32_t nb = min(4u, count - b);
@@ -177,7 +154,7 @@ template <bool PLUECKER> struct QuadLeaf
           for (uint32_t half = 0; half < 2; half++) { // A then B of this quad (lanes g+k and 4+g+k)
             TriHit h;
             bool ok = test(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h);
-            if (ok && P.exclOffsets) ok = !quad_candidate_excluded(P, rayIdx, gid, pid, h.t);
+            if (ok && P.exclOffsets) ok = !candidate_excluded(P, rayIdx, gid, pid, h.t);
             if (ok) {
               if (OCCLUDED) return true; // Occluded1EpilogM: any valid lane
               // select_min over the 8 lanes, lowest lane wins ties
@@ -194,11 +171,7 @@ template <bool PLUECKER> struct QuadLeaf
         }
       }
       if (found) { // Intersect1EpilogM, intersector_epilog.h:293-305
-        r.tfar = best.t;
-        r.ngx = best.ngx; r.ngy = best.ngy; r.ngz = best.ngz;
-        r.u = best.u; r.v = best.v;
-        r.primID = bestPrim; r.geomID = bestGeom;
-        r.hit = 1u;
+        commit_hit(r, best, bestGeom, bestPrim);
       }
     }
     return false;
@@ -209,23 +182,14 @@ template <bool PLUECKER> struct QuadLeaf
 
 hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream)
 {
-#ifdef TRACE_DEV_METRIC_ONLY
-  return hipErrorInvalidValue;
-#else
   if (s.base.accel.kind == ACCEL_QUAD_PLUECKER) return dev::launch_service_kernel<dev::QuadLeaf<true>, true>(s, stream);
   return dev::launch_service_kernel<dev::QuadLeaf<false>, false>(s, stream);
-#endif
 }
 
 hipError_t launch_trace_quad(const LaunchParams& p, hipStream_t stream)
 {
   // Quad4v: Pluecker <-> robust traversal, Moeller <-> fast traversal (bvh_intersector1_bvh8.cpp:37-39)
-  if (p.poolKernel) {
-    if (p.accel.kind == ACCEL_QUAD_PLUECKER) return dev::launch_leaf_pool<dev::QuadLeaf<true>, true>(p, stream);
-    return dev::launch_leaf_pool<dev::QuadLeaf<false>, false>(p, stream);
-  }
-  if (p.accel.kind == ACCEL_QUAD_PLUECKER) return dev::launch_leaf<dev::QuadLeaf<true>, true>(p, stream);
-  return dev::launch_leaf<dev::QuadLeaf<false>, false>(p, stream);
+  return dev::launch_pluecker_moeller<dev::QuadLeaf>(p, stream, p.accel.kind == ACCEL_QUAD_PLUECKER);
 }
 
 } // namespace rtamd

@@ -3,8 +3,7 @@
 // reference's 4-wide SIMD semantics.
 //   block loop            kernels/geometry/intersector_iterators.h:32-36 (ArrayIntersector1)
 //   epilog / tie rules    kernels/geometry/intersector_epilog.h:226-307 (closest), :388-450 (any hit)
-#include "trace_loop.hip.h"
-#include "trace_pool.hip.h"
+#include "trace_leaf.hip.h"
 #include "trace_service.hip.h"
 #include "trace_cull.hip.h"
 
@@ -16,20 +15,13 @@ namespace dev {
 #define TRI_FETCH 4
 #endif
 
-template <bool PLUECKER> struct TriLeaf
+template <bool PLUECKER> struct TriLeaf : LeafTraits
 {
-  static constexpr bool OCTET = true;
-  static constexpr bool CONST_NG = false;
-  static constexpr int GROUP = 8;
-  static constexpr bool HIT_IN_MEMORY = false;
   // Both forms stay in the lane kernel.  Measured with the lane-per-ray form dropped (127 VGPRs, four waves per SIMD): random
   // rays 18.0 -> 19.2 Grays/s in flight, 0.098 -> 0.089 ms alone, but rays that visit many full leaves lose: camera rays 11.4 ->
   // 10.8, bounce rays 10.3 -> 9.4, shadow rays 15.9 -> 13.2 Grays/s (8 lanes per ray test a 4-triangle leaf at half occupancy;
   // with 64 rays at a leaf the lane-per-ray block loop is the better use of the wave).
   static constexpr bool OCTET_ONLY = false;
-  static constexpr int MIN_WAVES = TRACE_MIN_WAVES_PER_SIMD;
-  static __device__ __forceinline__ bool octet_ok(const LaunchParams&) { return true; }
-  static __device__ __forceinline__ void prepare() {}
 
   // Child-parallel form (trace_loop.hip.h): the 8 lanes of an octet test 8 consecutive records of the leaf of the ray in
   // exchange row `x`, i.e. two of the reference's blocks of 4 per pass: lanes 0-3 block A, lanes 4-7 block B.  Block
@@ -42,10 +34,9 @@ template <bool PLUECKER> struct TriLeaf
   {
     const TriRecord* __restrict__ prims = P.accel.prims;
     const uint32_t k = lid & 7u, sh = lid & 56u;
-    RayState r;
-    r.ox = x[0]; r.oy = x[1]; r.oz = x[2]; r.tnear = x[3];
-    r.dx = x[4]; r.dy = x[5]; r.dz = x[6]; r.tfar = x[7];
+    const RayState r = row_ray(x);
     const uint32_t ref = __float_as_uint(x[8]);
+    // (leaf_range and a shared exclusion scan change the instruction schedule of this leaf's kernels: written out, here and in intersect())
     const uint32_t first = ref & ((1u << TRI_START_BITS) - 1u);
     uint32_t cnt = valid ? (ref >> TRI_START_BITS) & 31u : 0u;
     float tfar = r.tfar;
@@ -65,7 +56,7 @@ template <bool PLUECKER> struct TriLeaf
           if (q.x == __float_as_uint(A.w) && q.y == __float_as_uint(B.w)) ok = false;
         }
       }
-      const uint32_t m8 = (uint32_t)(__ballot(ok) >> sh) & 0xffu;
+      const uint32_t m8 = octet_ballot(ok, lid);
       if (OCCLUDED) { // Occluded1EpilogM: any valid lane
         if (m8 != 0u) {
           if (k == 0u) x[9] = __uint_as_float(1u);
@@ -74,26 +65,20 @@ template <bool PLUECKER> struct TriLeaf
         continue;
       }
       // block A (also evaluated, unused, in the lanes of block B: the quads reduce separately)
-      float tq = ok ? h.t : RT_INF;
-      tq = fminf(tq, __uint_as_float(dpp_u32<DPP_XOR1>(__float_as_uint(tq))));
-      tq = fminf(tq, __uint_as_float(dpp_u32<DPP_XOR2>(__float_as_uint(tq))));
-      const float tqm = __uint_as_float(dpp_u32<DPP_HALF_MIRROR>(__float_as_uint(tq)));
+      const float tq = quad_min4(ok ? h.t : RT_INF);
+      const float tqm = dpp_f32<DPP_HALF_MIRROR>(tq);
       const float tA = k < 4u ? tq : tqm; // minimum of block A, in all 8 lanes
       const bool hasA = (m8 & 0x0fu) != 0u;
       const float tfarB = hasA ? tA : tfar;
       const bool okB = ok && k >= 4u && (h.Ts <= h.absDen * tfarB);
-      float tb = okB ? h.t : RT_INF;
-      tb = fminf(tb, __uint_as_float(dpp_u32<DPP_XOR1>(__float_as_uint(tb))));
-      tb = fminf(tb, __uint_as_float(dpp_u32<DPP_XOR2>(__float_as_uint(tb))));
-      const float tbm = __uint_as_float(dpp_u32<DPP_HALF_MIRROR>(__float_as_uint(tb)));
+      const float tb = quad_min4(okB ? h.t : RT_INF);
+      const float tbm = dpp_f32<DPP_HALF_MIRROR>(tb);
       const float tB = k >= 4u ? tb : tbm; // minimum of block B, in all 8 lanes
-      const uint32_t wA = (uint32_t)(__ballot(ok && k < 4u && h.t == tA) >> sh) & 0x0fu;
-      const uint32_t wB = (uint32_t)(__ballot(okB && h.t == tB) >> sh) & 0xf0u;
+      const uint32_t wA = octet_ballot(ok && k < 4u && h.t == tA, lid) & 0x0fu;
+      const uint32_t wB = octet_ballot(okB && h.t == tB, lid) & 0xf0u;
       const uint32_t winner = wB != 0u ? (uint32_t)__ffs(wB) - 1u : (wA != 0u ? (uint32_t)__ffs(wA) - 1u : 8u);
       if (k == winner) { // Intersect1EpilogM, intersector_epilog.h:293-305
-        x[0] = h.t; x[1] = h.ngx; x[2] = h.ngy; x[3] = h.ngz; x[4] = h.u; x[5] = h.v;
-        x[6] = A.w; x[7] = B.w;
-        x[9] = __uint_as_float(1u);
+        row_write_hit(x, h, __float_as_uint(A.w), __float_as_uint(B.w));
       }
       tfar = wB != 0u ? tB : (wA != 0u ? tA : tfar);
     }
@@ -103,8 +88,8 @@ template <bool PLUECKER> struct TriLeaf
   static __device__ __forceinline__ bool intersect(const LaunchParams& P, uint32_t ref, RayState& r, WorkCounters& wc, uint32_t rayIdx)
   {
     const TriRecord* __restrict__ prims = P.accel.prims;
-    const uint32_t first = ref & ((1u << TRI_START_BITS) - 1u);
-    const uint32_t count = (ref >> TRI_START_BITS) & 31u;
+    uint32_t first, count;
+    leaf_range(ref, first, count);
     for (uint32_t b = 0; b < count; b += 4) {
       const float tfarBlock = r.tfar; // all lanes of a block see the tfar at block entry
       const uint32_t nb = min(4u, count - b);
@@ -147,11 +132,7 @@ template <bool PLUECKER> struct TriLeaf
         }
       }
       if (found) { // Intersect1EpilogM, intersector_epilog.h:293-305
-        r.tfar = best.t;
-        r.ngx = best.ngx; r.ngy = best.ngy; r.ngz = best.ngz;
-        r.u = best.u; r.v = best.v;
-        r.primID = bestPrim; r.geomID = bestGeom;
-        r.hit = 1u;
+        commit_hit(r, best, bestGeom, bestPrim);
       }
     }
     return false;
@@ -171,23 +152,14 @@ hipError_t launch_cull(const LaunchParams& p, hipStream_t stream)
 
 hipError_t launch_service_tri(const ServiceParams& s, hipStream_t stream)
 {
-#ifdef TRACE_DEV_METRIC_ONLY
-  return hipErrorInvalidValue;
-#else
   if (s.base.accel.kind == ACCEL_TRI_PLUECKER) return dev::launch_service_kernel<dev::TriLeaf<true>, true>(s, stream);
   return dev::launch_service_kernel<dev::TriLeaf<false>, false>(s, stream);
-#endif
 }
 
 hipError_t launch_trace_tri(const LaunchParams& p, hipStream_t stream)
 {
   // Triangle4v <-> robust traversal, Triangle4 <-> fast traversal (bvh_intersector1_bvh8.cpp:27-29)
-  if (p.poolKernel) {
-    if (p.accel.kind == ACCEL_TRI_PLUECKER) return dev::launch_leaf_pool<dev::TriLeaf<true>, true>(p, stream);
-    return dev::launch_leaf_pool<dev::TriLeaf<false>, false>(p, stream);
-  }
-  if (p.accel.kind == ACCEL_TRI_PLUECKER) return dev::launch_leaf<dev::TriLeaf<true>, true>(p, stream);
-  return dev::launch_leaf<dev::TriLeaf<false>, false>(p, stream);
+  return dev::launch_pluecker_moeller<dev::TriLeaf>(p, stream, p.accel.kind == ACCEL_TRI_PLUECKER);
 }
 
 } // namespace rtamd

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / scratch / LDS usage of every traversal kernel of one .hip source (development aid; cross-compiles, no GPU).
-# usage: tools/kernel_resources.sh csrc/trace_subdiv.hip [extra hipcc flags]
+# usage: tools/kernel_resources.sh csrc/trace_cbvh_leaf.hip [extra hipcc flags]
 cd "$(dirname "$0")/../embree-compressed_amd" || exit 1
 src=$1; shift
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -I../include --offload-arch=gfx950 --offload-device-only -c \

@@ -4,7 +4,8 @@
 //   nodes   : QNode8[]       96-byte quantized BVH8 nodes, index 0 = root (if the root is inner)
 //   prims   : TriRecord[]    48-byte triangle records (v0,v1,v2 or v0,e1,e2 + ids), leaf-contiguous
 //   blobs   : bytes          cBVH / GridSOA leaf blobs for subdivision geometry (16-byte aligned each),
-//                            or QuadRecord[] (64-byte quad records, leaf-contiguous) for quad geometry
+//                            or QuadRecord[] (64-byte quad records, leaf-contiguous) for quad geometry,
+//                            or TriMBRecord[] (96-byte motion-blur triangle records, leaf-contiguous) for triangle meshes with time steps
 // The reference keeps the same information behind 64-bit tagged pointers (kernels/bvh/bvh.h:150-396,
 // AlignedNode :433-594, QuantizedNode :1150-1324, Triangle4v kernels/geometry/trianglev.h:24-162).
 #pragma once
@@ -21,6 +22,7 @@ namespace rtamd {
 // inner       : bits 0..30 = node index
 // triangle leaf: bits 26..30 = triangle count (1..28, i.e. up to 7 blocks of 4 like bvh.h:140), bits 0..25 = first record
 // quad leaf   : the same form, counting quads
+// MB tri leaf : the same form, counting TriMBRecords (one per triangle and time segment)
 // subdiv leaf : bits 0..30 = blob index (one blob per leaf, like encodeTypedLeaf(ptr,1) bvh_builder_subdiv.cpp:728)
 static const uint32_t REF_EMPTY = 0xFFFFFFFFu; // no child (reference: BVH::emptyNode, bvh.h:117-132)
 static const uint32_t REF_LEAF = 0x80000000u;
@@ -79,6 +81,30 @@ struct alignas(16) QuadRecord
   uint32_t pad1;
 };
 static_assert(sizeof(QuadRecord) == 64, "QuadRecord must be 64 bytes");
+
+// ---- motion-blur triangle record, 96 bytes = 6 x dwordx4 -------------------------------------------------------------
+// The three vertices of a triangle at both ends of ONE time segment of its mesh (a0..c0 at step `segment`, a1..c1 at step `segment` + 1).
+// A mesh with N time steps has S = N - 1 segments and contributes S records per triangle.  For a ray (getTimeSegment, geometry.h:28-34):
+//   ts = time * S, itime = clamp(floor(ts), 0, S - 1), ftime = ts - itime   (times outside [0, 1] extrapolate the first / last segment)
+// a record is tested only when itime == segment; its vertices are then lerp(p0, p1, ftime) = fmaf(1 - ftime, p0, ftime * p1)
+// (TriangleMi::gather with a time, trianglei.h:343-364) and go through the Pluecker / Moeller test of the static leaf.  Blocks are
+// groups of 4 records from the leaf start, as for TriRecord.
+struct alignas(16) TriMBRecord
+{
+  float a0x, a0y, a0z;
+  uint32_t geomID;
+  float b0x, b0y, b0z;
+  uint32_t primID;
+  float c0x, c0y, c0z;
+  uint32_t segment;     // itime this record serves
+  float a1x, a1y, a1z;
+  uint32_t numSegments; // S of the mesh
+  float b1x, b1y, b1z;
+  uint32_t pad0;
+  float c1x, c1y, c1z;
+  uint32_t pad1;
+};
+static_assert(sizeof(TriMBRecord) == 96, "TriMBRecord must be 96 bytes");
 
 // ---- eager subdivision leaf: one 3x3-vertex cell (2x2 quads = 8 triangles), 160 bytes = 10 x dwordx4 ------
 // Replaces the inner leaves of GridSOA (kernels/geometry/grid_soa.h:267-286, :85-90): the reference stores whole
@@ -159,7 +185,9 @@ enum AccelKind : uint32_t
   ACCEL_GRIDSOA = 6,      // eager subdiv (default subdiv accel)
   ACCEL_CBVH_FULL = 7,    // subdiv_accel=bvh4.compressed.full: the fork's box mode over UNcompressed quadtree nodes (compressed.h:40,774)
   ACCEL_QUAD_PLUECKER = 8, // quad_accel=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:251-330): QuadMv + Pluecker, robust traversal
-  ACCEL_QUAD_MOELLER = 9   // quad_accel=default / bvh8.quad4v / bvh4.quad4v / *.quad4i: QuadMv + Moeller, fast traversal
+  ACCEL_QUAD_MOELLER = 9,  // quad_accel=default / bvh8.quad4v / bvh4.quad4v / *.quad4i: QuadMv + Moeller, fast traversal
+  ACCEL_TRIMB_PLUECKER = 10, // tri_accel_mb=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:213-247): interpolated triangle + Pluecker, robust traversal
+  ACCEL_TRIMB_MOELLER = 11   // tri_accel_mb=default / bvh8.triangle4imb / bvh4.triangle4imb / *.triangle4vmb: interpolated triangle + Moeller, fast traversal
 };
 
 // What a kernel launch needs to know about one committed scene.
@@ -167,7 +195,7 @@ struct AccelDesc
 {
   const QNode8* nodes;
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] of a motion-blur triangle accel
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind
@@ -186,7 +214,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (up to three launches per batch: triangles, quads, subdiv)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (up to four launches per batch: triangles, motion-blur triangles, quads, subdiv)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

@@ -38,6 +38,7 @@ void Device::parse(const std::string& cfg)
     if (key == "tri_accel" || key == "accel") tri_accel = val;
     else if (key == "subdiv_accel") subdiv_accel = val;
     else if (key == "quad_accel") { quad_accel = val; quadAccelNamed = true; }
+    else if (key == "tri_accel_mb") tri_accel_mb = val;
     else if (key == "verbose") verbose = atoi(val.c_str());
     else if (key == "gpu" || key == "device") { gpu = (val == "none") ? -1 : atoi(val.c_str()); gpuList.clear(); }
     else if (key == "gpus") {
@@ -119,7 +120,7 @@ Device::Device(const char* cfg)
     sh->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     HIP_CHECK(hipStreamCreateWithFlags(&sh->stream, hipStreamNonBlocking));
     sh->ownsStream = true;
-    HIP_CHECK(hipMalloc(&sh->countersDev, 3 * (size_t)WAVE_LOG_CAPACITY * sizeof(WaveRecord))); // triangle, subdiv, quad launches
+    HIP_CHECK(hipMalloc(&sh->countersDev, (size_t)Scene::NUM_ACCELS * WAVE_LOG_CAPACITY * sizeof(WaveRecord))); // one slice per accel of a scene
     HIP_CHECK(hipHostMalloc((void**)&sh->overflowHost, 64, hipHostMallocMapped));
     *sh->overflowHost = 0u;
     HIP_CHECK(hipHostGetDevicePointer((void**)&sh->overflowDev, sh->overflowHost, 0));

@@ -198,7 +198,8 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
           uint32_t tb;
           memcpy(&tb, &got.ray.tfar, 4);
           const bool onQuad = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD;
-          excl[onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : Scene::TRI)].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb});
+          const bool onTriMB = geo && geo->type == RTC_GEOMETRY_TYPE_TRIANGLE && geo->timeSteps > 1; // one record per segment, a ray sees one segment: (geomID, primID) names the candidate
+          excl[onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onTriMB ? Scene::TRIMB : Scene::TRI))].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb});
           next.push_back(i);
         }
       }

@@ -28,6 +28,7 @@ struct Device : RefCounted
   std::string tri_accel = "default";
   std::string subdiv_accel = "default";
   std::string quad_accel = "default";
+  std::string tri_accel_mb = "default"; // triangle meshes with more than one time step
   bool quadAccelNamed = false; // "quad_accel=" given (a host-only device takes quad geometry only then, quads_enabled())
   int verbose = 0;
   int gpu = 0;            // HIP device ordinal ("gpu=" key; falls back to env RTAMD_GPU, LOCAL_RANK is NOT read here)
@@ -272,8 +273,8 @@ struct Geometry : RefCounted
   size_t numTriangles() const;
   size_t numVertices() const;
   void triangle(size_t i, unsigned idx[3]) const;
-  V3 vertex(size_t i) const;
-  bool validTriangle(size_t i) const;
+  V3 vertex(size_t i, unsigned slot = 0) const; // slot = time step
+  bool validTriangle(size_t i, unsigned slot = 0) const;
   // quad mesh accessors (reference: QuadMesh, kernels/common/scene_quad_mesh.h)
   size_t numQuads() const { return numTriangles(); } // index buffer records (UINT4 for quads)
   void quad(size_t i, unsigned idx[4]) const;
@@ -333,12 +334,13 @@ struct Scene : RefCounted
 
   std::vector<uint8_t> debugGrids; // keep_grids=1: per patch {geomID,primID,n} + x[],y[],z[] of the (n+1)^2 grid
 
-  Accel triAccel;    // triangles
-  Accel quadAccel;   // quads (QuadRecord[] in `blobs`); traced after the triangles, before the subdivision patches (scene.cpp:650-654)
+  Accel triAccel;    // triangles with one time step
+  Accel triMBAccel;  // triangles with several time steps (TriMBRecord[] in `blobs`); traced after the static triangles, before the quads (scene.cpp:650-654)
+  Accel quadAccel;   // quads (QuadRecord[] in `blobs`); traced after the triangles, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
-  // the accels in trace order; TRI / QUAD / SUBDIV index whatever a path keeps per accel
-  enum { TRI = 0, QUAD = 1, SUBDIV = 2, NUM_ACCELS = 3 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &quadAccel, &subdivAccel}; }
+  // the accels in trace order; TRI / TRIMB / QUAD / SUBDIV index whatever a path keeps per accel
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, SUBDIV = 3, NUM_ACCELS = 4 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &subdivAccel}; }
 
   explicit Scene(Device* d);
   ~Scene() override;

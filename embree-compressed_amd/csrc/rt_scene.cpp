@@ -89,19 +89,20 @@ void Geometry::triangle(size_t i, unsigned idx[3]) const
   idx[0] = p[0]; idx[1] = p[1]; idx[2] = p[2];
 }
 
-V3 Geometry::vertex(size_t i) const
+V3 Geometry::vertex(size_t i, unsigned slot) const
 {
-  const float* p = (const float*)view(RTC_BUFFER_TYPE_VERTEX, 0)->at(i);
+  const float* p = (const float*)view(RTC_BUFFER_TYPE_VERTEX, slot)->at(i);
   return V3(p[0], p[1], p[2]);
 }
 
 // the vertex test of TriangleMesh::valid / QuadMesh::valid: every index in range, every vertex finite and within FLT_LARGE
-static bool valid_vertices(const Geometry& g, const unsigned* idx, int n)
+static bool valid_vertices(const Geometry& g, const unsigned* idx, int n, unsigned slot = 0)
 {
-  const size_t nv = g.numVertices();
+  const BufferView* vv = g.view(RTC_BUFFER_TYPE_VERTEX, slot);
+  const size_t nv = vv && vv->valid() ? vv->count : 0;
   for (int k = 0; k < n; k++) {
     if (idx[k] >= nv) return false;
-    V3 p = g.vertex(idx[k]);
+    V3 p = g.vertex(idx[k], slot);
     if (!(std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z))) return false;
     if (fabsf(p.x) > 1.844e18f || fabsf(p.y) > 1.844e18f || fabsf(p.z) > 1.844e18f) return false; // FLT_LARGE
   }
@@ -109,11 +110,11 @@ static bool valid_vertices(const Geometry& g, const unsigned* idx, int n)
 }
 
 // TriangleMesh::valid (scene_triangle_mesh.h)
-bool Geometry::validTriangle(size_t i) const
+bool Geometry::validTriangle(size_t i, unsigned slot) const
 {
   unsigned idx[3];
   triangle(i, idx);
-  return valid_vertices(*this, idx, 3);
+  return valid_vertices(*this, idx, 3, slot);
 }
 
 void Geometry::quad(size_t i, unsigned idx[4]) const
@@ -270,7 +271,10 @@ static bool build_mesh_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char
   for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
     Geometry* g = s->geometries[gid];
     if (!g || !g->enabled || g->type != type) continue;
-    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry is not supported by the device path");
+    if (g->timeSteps != 1) {
+      if (type == RTC_GEOMETRY_TYPE_TRIANGLE) continue; // build_trimb_accel
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry is not supported by the device path");
+    }
     const size_t n = g->numTriangles(); // index buffer records
     for (size_t i = 0; i < n; i++) {
       if (!(NV == 4 ? g->validQuad(i) : g->validTriangle(i))) continue;
@@ -370,6 +374,98 @@ static void build_quad_accel(Scene* s)
   memcpy(A.blobs.data(), recs.data(), A.blobs.size());
 }
 
+// Triangle meshes with more than one time step (scene.cpp:213-247): one BVH8 with the triangle settings over (triangle, time segment)
+// pairs.  A pair's box is the union of the triangle's boxes at the two ends of the segment - the vertices move on straight lines in
+// between, so the box holds the triangle at every time of the segment (and, by the same argument, NOT at extrapolated times: a ray
+// with a time outside [0, 1] sees the first / last segment only where it still is inside its box).  Every name is served by this one
+// layout: default = Pluecker + robust traversal for a robust scene, Moeller + fast traversal otherwise; an explicit triangle4imb /
+// triangle4vmb accel is the fast (Moeller) variant.
+static void build_trimb_accel(Scene* s)
+{
+  Accel& A = s->triMBAccel;
+  A.clear();
+  const std::string& name = s->device->tri_accel_mb;
+  bool pluecker;
+  if (name == "default") pluecker = s->isRobust();
+  else if (name == "bvh8.triangle4imb" || name == "bvh4.triangle4imb" || name == "bvh8.triangle4vmb" || name == "bvh4.triangle4vmb") pluecker = false;
+  else RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown motion blur triangle acceleration structure " + name);
+
+  struct Src { unsigned geomID, primID, segment; };
+  std::vector<Src> src;
+  std::vector<BuildPrim> bp;
+  auto vertices = [](const Geometry* g, size_t i, unsigned slot, V3* v) {
+    unsigned idx[3];
+    g->triangle(i, idx);
+    for (int k = 0; k < 3; k++) v[k] = g->vertex(idx[k], slot);
+  };
+  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
+    Geometry* g = s->geometries[gid];
+    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_TRIANGLE || g->timeSteps == 1) continue;
+    for (unsigned t = 0; t < g->timeSteps; t++) {
+      const BufferView* vv = g->view(RTC_BUFFER_TYPE_VERTEX, t);
+      if (!vv || !vv->valid()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry: a time step has no vertex buffer");
+    }
+    const size_t n = g->numTriangles();
+    std::vector<char> ok(g->timeSteps);
+    for (size_t i = 0; i < n; i++) {
+      for (unsigned t = 0; t < g->timeSteps; t++) ok[t] = g->validTriangle(i, t);
+      for (unsigned seg = 0; seg + 1 < g->timeSteps; seg++) {
+        if (!ok[seg] || !ok[seg + 1]) continue; // invalid at either end of the segment: no record for it
+        V3 v[6];
+        vertices(g, i, seg, v);
+        vertices(g, i, seg + 1, v + 3);
+        BuildPrim p;
+        for (int k = 0; k < 6; k++) p.box.extend(v[k]);
+        p.id = (uint32_t)src.size();
+        src.push_back({gid, (unsigned)i, seg});
+        bp.push_back(p);
+      }
+    }
+  }
+  if (bp.empty()) return;
+  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many motion blur triangle segments for the 26-bit leaf reference");
+
+  std::vector<TriMBRecord> recs;
+  recs.reserve(bp.size());
+  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
+    const uint32_t first = (uint32_t)recs.size();
+    for (size_t i = begin; i < end; i++) {
+      const Src& sr = src[prims[i].id];
+      const Geometry* g = s->geometries[sr.geomID];
+      V3 v[6];
+      vertices(g, sr.primID, sr.segment, v);
+      vertices(g, sr.primID, sr.segment + 1, v + 3);
+      TriMBRecord r;
+      memset(&r, 0, sizeof(r));
+      r.a0x = v[0].x; r.a0y = v[0].y; r.a0z = v[0].z;
+      r.b0x = v[1].x; r.b0y = v[1].y; r.b0z = v[1].z;
+      r.c0x = v[2].x; r.c0y = v[2].y; r.c0z = v[2].z;
+      r.a1x = v[3].x; r.a1y = v[3].y; r.a1z = v[3].z;
+      r.b1x = v[4].x; r.b1y = v[4].y; r.b1z = v[4].z;
+      r.c1x = v[5].x; r.c1y = v[5].y; r.c1z = v[5].z;
+      r.geomID = sr.geomID;
+      r.primID = sr.primID;
+      r.segment = sr.segment;
+      r.numSegments = g->timeSteps - 1;
+      recs.push_back(r);
+    }
+    return make_tri_leaf(first, (uint32_t)(end - begin));
+  };
+  BuildSettings cfg;
+  cfg.threads = host_threads(s->device);
+  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
+  A.nodes = std::move(r.nodes);
+  A.root = r.root;
+  A.maxDepth = r.maxDepth;
+  A.leafCount = r.leafCount;
+  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  A.kind = pluecker ? ACCEL_TRIMB_PLUECKER : ACCEL_TRIMB_MOELLER; // only once there are records
+  A.robust = pluecker ? 1 : 0;
+  A.blobStride = sizeof(TriMBRecord);
+  A.blobs.resize(recs.size() * sizeof(TriMBRecord));
+  memcpy(A.blobs.data(), recs.data(), A.blobs.size());
+}
+
 void Scene::commit()
 {
   std::lock_guard<std::mutex> g(buildMutex);
@@ -396,6 +492,7 @@ void Scene::commit()
   if (progressFn && !progressFn(progressUser, 0.0)) RT_THROW(RTC_ERROR_CANCELLED, "progress monitor forced termination");
   bounds = Box3();
   build_triangle_accel(this);
+  build_trimb_accel(this);
   build_quad_accel(this);
   build_subdiv_accel(this);
   for (Accel* a : accels()) a->upload(device);
@@ -404,6 +501,9 @@ void Scene::commit()
     fprintf(stderr, "embree3-amd: tri accel kind %u: %zu nodes (%zu B), %zu tris, depth %u; subdiv accel kind %u: %zu nodes, %zu blobs (%zu B)\n",
             triAccel.kind, triAccel.nodes.size(), triAccel.nodes.size() * sizeof(QNode8), triAccel.prims.size(), triAccel.maxDepth,
             subdivAccel.kind, subdivAccel.nodes.size(), subdivAccel.blobOffsets.size(), subdivAccel.blobs.size());
+    if (triMBAccel.kind != ACCEL_NONE)
+      fprintf(stderr, "embree3-amd: motion blur triangle accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", triMBAccel.kind, triMBAccel.nodes.size(),
+              triMBAccel.nodes.size() * sizeof(QNode8), triMBAccel.blobs.size() / sizeof(TriMBRecord), triMBAccel.blobs.size(), triMBAccel.maxDepth);
     if (quadAccel.kind != ACCEL_NONE)
       fprintf(stderr, "embree3-amd: quad accel kind %u: %zu nodes (%zu B), %zu quads (%zu B), depth %u\n", quadAccel.kind, quadAccel.nodes.size(),
               quadAccel.nodes.size() * sizeof(QNode8), quadAccel.blobs.size() / sizeof(QuadRecord), quadAccel.blobs.size(), quadAccel.maxDepth);

@@ -139,6 +139,7 @@ def load_library(path=LIB_PATH):
         "rtcSetGeometryDisplacementFunction": (None, [vp, vp]),
         "rtcSetGeometrySubdivisionMode": (None, [vp, u, C.c_int]),
         "rtcSetGeometryTessellationRate": (None, [vp, C.c_float]),
+        "rtcSetGeometryTimeStepCount": (None, [vp, u]),
         "rtcSetGeometryUserData": (None, [vp, vp]),
         "rtcSetGeometryIntersectFilterFunction": (None, [vp, vp]),
         "rtcSetGeometryOccludedFilterFunction": (None, [vp, vp]),
@@ -299,6 +300,31 @@ class Scene:
         L.rtcReleaseGeometry(g)
         self._keep += [vpad, t]
         self.device.check("add_triangles")
+        return gid
+
+    def add_triangles_mb(self, verts_per_step, tris, geom_id=None):
+        """Motion-blur triangle mesh: verts_per_step is a sequence of N >= 2 float32 [nv,3] arrays (time steps 0..N-1, vertex buffer
+        slots 0..N-1 after rtcSetGeometryTimeStepCount), tris uint32 [nt,3]; shared buffers like add_triangles."""
+        L = self.lib
+        steps = [np.ascontiguousarray(v, dtype=np.float32) for v in verts_per_step]
+        t = np.ascontiguousarray(tris, dtype=np.uint32)
+        g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_TRIANGLE)
+        L.rtcSetGeometryTimeStepCount(g, len(steps))
+        for slot, v in enumerate(steps):
+            vpad = np.zeros((v.shape[0] + 2, 3), dtype=np.float32)
+            vpad[: v.shape[0]] = v
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_VERTEX, slot, RTC_FORMAT_FLOAT3, vpad.ctypes.data, 0, 12, v.shape[0])
+            self._keep.append(vpad)
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_INDEX, 0, RTC_FORMAT_UINT3, t.ctypes.data, 0, 12, t.shape[0])
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self._keep.append(t)
+        self.device.check("add_triangles_mb")
         return gid
 
     def add_quads(self, verts, quads, geom_id=None):

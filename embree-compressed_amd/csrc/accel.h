@@ -5,7 +5,8 @@
 //   prims   : TriRecord[]    48-byte triangle records (v0,v1,v2 or v0,e1,e2 + ids), leaf-contiguous
 //   blobs   : bytes          cBVH / GridSOA leaf blobs for subdivision geometry (16-byte aligned each),
 //                            or QuadRecord[] (64-byte quad records, leaf-contiguous) for quad geometry,
-//                            or TriMBRecord[] (96-byte motion-blur triangle records, leaf-contiguous) for triangle meshes with time steps
+//                            or TriMBRecord[] (96-byte motion-blur triangle records, leaf-contiguous) for triangle meshes with time steps,
+//                            or QuadMBRecord[] (128-byte motion-blur quad records, leaf-contiguous) for quad meshes with time steps
 // The reference keeps the same information behind 64-bit tagged pointers (kernels/bvh/bvh.h:150-396,
 // AlignedNode :433-594, QuantizedNode :1150-1324, Triangle4v kernels/geometry/trianglev.h:24-162).
 #pragma once
@@ -23,6 +24,7 @@ namespace rtamd {
 // triangle leaf: bits 26..30 = triangle count (1..28, i.e. up to 7 blocks of 4 like bvh.h:140), bits 0..25 = first record
 // quad leaf   : the same form, counting quads
 // MB tri leaf : the same form, counting TriMBRecords (one per triangle and time segment)
+// MB quad leaf: the same form, counting QuadMBRecords (one per quad and time segment)
 // subdiv leaf : bits 0..30 = blob index (one blob per leaf, like encodeTypedLeaf(ptr,1) bvh_builder_subdiv.cpp:728)
 static const uint32_t REF_EMPTY = 0xFFFFFFFFu; // no child (reference: BVH::emptyNode, bvh.h:117-132)
 static const uint32_t REF_LEAF = 0x80000000u;
@@ -106,6 +108,34 @@ struct alignas(16) TriMBRecord
 };
 static_assert(sizeof(TriMBRecord) == 96, "TriMBRecord must be 96 bytes");
 
+// ---- motion-blur quad record, 128 bytes = 8 x dwordx4 ----------------------------------------------------------------
+// The four vertices of a quad at both ends of ONE time segment of its mesh (v0a..v3a at step `segment`, v0b..v3b at step `segment` + 1);
+// segments, record selection and interpolation as for TriMBRecord (QuadMi::gather with a time, quadi.h:441-457), then the A / B split
+// and the tests of the static quad leaf.  Blocks are groups of 4 records from the leaf start = one 8-wide block of triangles, as for
+// QuadRecord.  The four id words sit in the w of v1 and v3, the vertices BOTH triangles of a quad read (A = v0 v1 v3, B = v2 v1 v3):
+// a lane of the octet form that tests B never loads v0 and still has all ids (the static record keeps geomID in v0.w and moves it
+// across lanes).
+struct alignas(16) QuadMBRecord
+{
+  float v0ax, v0ay, v0az;
+  uint32_t pad0;
+  float v1ax, v1ay, v1az;
+  uint32_t primID;
+  float v2ax, v2ay, v2az;
+  uint32_t pad1;
+  float v3ax, v3ay, v3az;
+  uint32_t geomID;
+  float v0bx, v0by, v0bz;
+  uint32_t pad2;
+  float v1bx, v1by, v1bz;
+  uint32_t segment;     // itime this record serves
+  float v2bx, v2by, v2bz;
+  uint32_t pad3;
+  float v3bx, v3by, v3bz;
+  uint32_t numSegments; // S of the mesh
+};
+static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
+
 // ---- eager subdivision leaf: one 3x3-vertex cell (2x2 quads = 8 triangles), 160 bytes = 10 x dwordx4 ------
 // Replaces the inner leaves of GridSOA (kernels/geometry/grid_soa.h:267-286, :85-90): the reference stores whole
 // <=9x9 sub-grids in SoA form and a private BVH4 down to 3x3-vertex cells; here every cell is self-contained and the
@@ -187,7 +217,9 @@ enum AccelKind : uint32_t
   ACCEL_QUAD_PLUECKER = 8, // quad_accel=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:251-330): QuadMv + Pluecker, robust traversal
   ACCEL_QUAD_MOELLER = 9,  // quad_accel=default / bvh8.quad4v / bvh4.quad4v / *.quad4i: QuadMv + Moeller, fast traversal
   ACCEL_TRIMB_PLUECKER = 10, // tri_accel_mb=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:213-247): interpolated triangle + Pluecker, robust traversal
-  ACCEL_TRIMB_MOELLER = 11   // tri_accel_mb=default / bvh8.triangle4imb / bvh4.triangle4imb / *.triangle4vmb: interpolated triangle + Moeller, fast traversal
+  ACCEL_TRIMB_MOELLER = 11,  // tri_accel_mb=default / bvh8.triangle4imb / bvh4.triangle4imb / *.triangle4vmb: interpolated triangle + Moeller, fast traversal
+  ACCEL_QUADMB_PLUECKER = 12, // quad_accel_mb=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:332-367): interpolated quad + Pluecker, robust traversal
+  ACCEL_QUADMB_MOELLER = 13   // quad_accel_mb=default / bvh8.quad4imb / bvh4.quad4imb: interpolated quad + Moeller, fast traversal
 };
 
 // What a kernel launch needs to know about one committed scene.
@@ -195,7 +227,7 @@ struct AccelDesc
 {
   const QNode8* nodes;
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] of a motion-blur triangle accel
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind
@@ -214,7 +246,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (up to four launches per batch: triangles, motion-blur triangles, quads, subdiv)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (up to five launches per batch: triangles, motion-blur triangles, quads, motion-blur quads, subdiv)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

@@ -124,7 +124,7 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
   }
   ExclList excl[Scene::NUM_ACCELS];
   for (ExclList& e : excl) e.perRay.resize(M);
-  excl[Scene::QUAD].keyedByT = excl[Scene::SUBDIV].keyedByT = true;
+  excl[Scene::QUAD].keyedByT = excl[Scene::QUADMB].keyedByT = excl[Scene::SUBDIV].keyedByT = true;
   std::vector<uint32_t> next;
   void* dExcl = nullptr;
   size_t dExclBytes = 0;
@@ -197,9 +197,10 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
         } else {
           uint32_t tb;
           memcpy(&tb, &got.ray.tfar, 4);
-          const bool onQuad = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD;
+          const bool onQuad = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD && geo->timeSteps == 1;
+          const bool onQuadMB = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD && geo->timeSteps > 1; // as onTriMB; the two triangles of the quad are told apart by t
           const bool onTriMB = geo && geo->type == RTC_GEOMETRY_TYPE_TRIANGLE && geo->timeSteps > 1; // one record per segment, a ray sees one segment: (geomID, primID) names the candidate
-          excl[onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onTriMB ? Scene::TRIMB : Scene::TRI))].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb});
+          excl[onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onQuadMB ? Scene::QUADMB : (onTriMB ? Scene::TRIMB : Scene::TRI)))].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb});
           next.push_back(i);
         }
       }

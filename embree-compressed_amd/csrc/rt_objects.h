@@ -29,6 +29,8 @@ struct Device : RefCounted
   std::string subdiv_accel = "default";
   std::string quad_accel = "default";
   std::string tri_accel_mb = "default"; // triangle meshes with more than one time step
+  std::string quad_accel_mb = "default"; // quad meshes with more than one time step
+  bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
   bool quadAccelNamed = false; // "quad_accel=" given (a host-only device takes quad geometry only then, quads_enabled())
   int verbose = 0;
   int gpu = 0;            // HIP device ordinal ("gpu=" key; falls back to env RTAMD_GPU, LOCAL_RANK is NOT read here)
@@ -197,8 +199,11 @@ struct Device : RefCounted
   void synchronize();     // all shards' streams; raises a pending stack-overflow report
   // Quad meshes are traced by the GPU kernels (trace_quad.hip): every device with a GPU takes them.  A host-only device (gpu=none) keeps
   // the geometry set of the host object model as it was - RTC_GEOMETRY_TYPE_QUAD raises INVALID_OPERATION there, as in a build without
-  // the feature - unless its config names a quad accel (quad_accel=...), which builds quad scenes for inspection.
-  bool quads_enabled() const { return gpu >= 0 || quadAccelNamed; }
+  // the feature - unless its config names a quad accel (quad_accel=... or quad_accel_mb=...), which builds quad scenes for inspection.
+  bool quads_enabled() const { return gpu >= 0 || quadAccelNamed || quadAccelMBNamed; }
+  // Quad meshes with time steps follow the same rule with their own key: a host-only device whose config does not name quad_accel_mb=
+  // raises INVALID_OPERATION at commit for them, as before the motion-blur quad accel existed.
+  bool quads_mb_enabled() const { return gpu >= 0 || quadAccelMBNamed; }
   bool tuneBlocksAuto = true; // no RTAMD_BLOCKS_PER_CU given: 2 workgroups per CU, 1 when >= 2 batches run on other streams
   void memoryMonitor(ssize_t bytes, bool post);
 };
@@ -278,7 +283,7 @@ struct Geometry : RefCounted
   // quad mesh accessors (reference: QuadMesh, kernels/common/scene_quad_mesh.h)
   size_t numQuads() const { return numTriangles(); } // index buffer records (UINT4 for quads)
   void quad(size_t i, unsigned idx[4]) const;
-  bool validQuad(size_t i) const;
+  bool validQuad(size_t i, unsigned slot = 0) const;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -336,11 +341,12 @@ struct Scene : RefCounted
 
   Accel triAccel;    // triangles with one time step
   Accel triMBAccel;  // triangles with several time steps (TriMBRecord[] in `blobs`); traced after the static triangles, before the quads (scene.cpp:650-654)
-  Accel quadAccel;   // quads (QuadRecord[] in `blobs`); traced after the triangles, before the subdivision patches
+  Accel quadAccel;   // quads with one time step (QuadRecord[] in `blobs`); traced after the triangles, before the motion-blur quads
+  Accel quadMBAccel; // quads with several time steps (QuadMBRecord[] in `blobs`); traced after the static quads, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
-  // the accels in trace order; TRI / TRIMB / QUAD / SUBDIV index whatever a path keeps per accel
-  enum { TRI = 0, TRIMB = 1, QUAD = 2, SUBDIV = 3, NUM_ACCELS = 4 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &subdivAccel}; }
+  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV index whatever a path keeps per accel
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, NUM_ACCELS = 5 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel}; }
 
   explicit Scene(Device* d);
   ~Scene() override;

@@ -124,11 +124,11 @@ void Geometry::quad(size_t i, unsigned idx[4]) const
 }
 
 // QuadMesh::valid (scene_quad_mesh.h:121-138)
-bool Geometry::validQuad(size_t i) const
+bool Geometry::validQuad(size_t i, unsigned slot) const
 {
   unsigned idx[4];
   quad(i, idx);
-  return valid_vertices(*this, idx, 4);
+  return valid_vertices(*this, idx, 4, slot);
 }
 
 // ---- Accel -------------------------------------------------------------------------------------------------
@@ -273,6 +273,7 @@ static bool build_mesh_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char
     if (!g || !g->enabled || g->type != type) continue;
     if (g->timeSteps != 1) {
       if (type == RTC_GEOMETRY_TYPE_TRIANGLE) continue; // build_trimb_accel
+      if (s->device->quads_mb_enabled()) continue;      // build_quadmb_accel
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry is not supported by the device path");
     }
     const size_t n = g->numTriangles(); // index buffer records
@@ -374,75 +375,62 @@ static void build_quad_accel(Scene* s)
   memcpy(A.blobs.data(), recs.data(), A.blobs.size());
 }
 
-// Triangle meshes with more than one time step (scene.cpp:213-247): one BVH8 with the triangle settings over (triangle, time segment)
-// pairs.  A pair's box is the union of the triangle's boxes at the two ends of the segment - the vertices move on straight lines in
-// between, so the box holds the triangle at every time of the segment (and, by the same argument, NOT at extrapolated times: a ray
-// with a time outside [0, 1] sees the first / last segment only where it still is inside its box).  Every name is served by this one
-// layout: default = Pluecker + robust traversal for a robust scene, Moeller + fast traversal otherwise; an explicit triangle4imb /
-// triangle4vmb accel is the fast (Moeller) variant.
-static void build_trimb_accel(Scene* s)
+// The frame of the motion-blur builders, as build_mesh_bvh8 is the one of the static builders: one BVH8 with the triangle settings over
+// (primitive, time segment) pairs of the scene's enabled geometries of `type` with more than one time step.  A pair's box is the union
+// of the primitive's boxes at the two ends of the segment - the vertices move on straight lines in between, so the box holds the
+// primitive at every time of the segment (and, by the same argument, NOT at extrapolated times: a ray with a time outside [0, 1] sees
+// the first / last segment only where it still is inside its box).  A pair gets a record only when the primitive is valid at both ends.
+// fill(rec, v) writes the 2 * NV vertices (segment start, then segment end) into a zeroed record; the four id words are set here.
+// false (and `A` untouched): no record.
+template <int NV, class Rec, class Fill>
+static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* tooMany, std::vector<Rec>& recs, const Fill& fill)
 {
-  Accel& A = s->triMBAccel;
-  A.clear();
-  const std::string& name = s->device->tri_accel_mb;
-  bool pluecker;
-  if (name == "default") pluecker = s->isRobust();
-  else if (name == "bvh8.triangle4imb" || name == "bvh4.triangle4imb" || name == "bvh8.triangle4vmb" || name == "bvh4.triangle4vmb") pluecker = false;
-  else RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown motion blur triangle acceleration structure " + name);
-
   struct Src { unsigned geomID, primID, segment; };
   std::vector<Src> src;
   std::vector<BuildPrim> bp;
   auto vertices = [](const Geometry* g, size_t i, unsigned slot, V3* v) {
-    unsigned idx[3];
-    g->triangle(i, idx);
-    for (int k = 0; k < 3; k++) v[k] = g->vertex(idx[k], slot);
+    const unsigned* idx = (const unsigned*)g->view(RTC_BUFFER_TYPE_INDEX, 0)->at(i);
+    for (int k = 0; k < NV; k++) v[k] = g->vertex(idx[k], slot);
   };
   for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
     Geometry* g = s->geometries[gid];
-    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_TRIANGLE || g->timeSteps == 1) continue;
+    if (!g || !g->enabled || g->type != type || g->timeSteps == 1) continue;
     for (unsigned t = 0; t < g->timeSteps; t++) {
       const BufferView* vv = g->view(RTC_BUFFER_TYPE_VERTEX, t);
       if (!vv || !vv->valid()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry: a time step has no vertex buffer");
     }
-    const size_t n = g->numTriangles();
+    const size_t n = g->numTriangles(); // index buffer records
     std::vector<char> ok(g->timeSteps);
     for (size_t i = 0; i < n; i++) {
-      for (unsigned t = 0; t < g->timeSteps; t++) ok[t] = g->validTriangle(i, t);
+      for (unsigned t = 0; t < g->timeSteps; t++) ok[t] = NV == 4 ? g->validQuad(i, t) : g->validTriangle(i, t);
       for (unsigned seg = 0; seg + 1 < g->timeSteps; seg++) {
         if (!ok[seg] || !ok[seg + 1]) continue; // invalid at either end of the segment: no record for it
-        V3 v[6];
+        V3 v[2 * NV];
         vertices(g, i, seg, v);
-        vertices(g, i, seg + 1, v + 3);
+        vertices(g, i, seg + 1, v + NV);
         BuildPrim p;
-        for (int k = 0; k < 6; k++) p.box.extend(v[k]);
+        for (int k = 0; k < 2 * NV; k++) p.box.extend(v[k]);
         p.id = (uint32_t)src.size();
         src.push_back({gid, (unsigned)i, seg});
         bp.push_back(p);
       }
     }
   }
-  if (bp.empty()) return;
-  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many motion blur triangle segments for the 26-bit leaf reference");
+  if (bp.empty()) return false;
+  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, tooMany);
 
-  std::vector<TriMBRecord> recs;
   recs.reserve(bp.size());
   auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
     const uint32_t first = (uint32_t)recs.size();
     for (size_t i = begin; i < end; i++) {
       const Src& sr = src[prims[i].id];
       const Geometry* g = s->geometries[sr.geomID];
-      V3 v[6];
+      V3 v[2 * NV];
       vertices(g, sr.primID, sr.segment, v);
-      vertices(g, sr.primID, sr.segment + 1, v + 3);
-      TriMBRecord r;
+      vertices(g, sr.primID, sr.segment + 1, v + NV);
+      Rec r;
       memset(&r, 0, sizeof(r));
-      r.a0x = v[0].x; r.a0y = v[0].y; r.a0z = v[0].z;
-      r.b0x = v[1].x; r.b0y = v[1].y; r.b0z = v[1].z;
-      r.c0x = v[2].x; r.c0y = v[2].y; r.c0z = v[2].z;
-      r.a1x = v[3].x; r.a1y = v[3].y; r.a1z = v[3].z;
-      r.b1x = v[4].x; r.b1y = v[4].y; r.b1z = v[4].z;
-      r.c1x = v[5].x; r.c1y = v[5].y; r.c1z = v[5].z;
+      fill(r, v);
       r.geomID = sr.geomID;
       r.primID = sr.primID;
       r.segment = sr.segment;
@@ -459,11 +447,66 @@ static void build_trimb_accel(Scene* s)
   A.maxDepth = r.maxDepth;
   A.leafCount = r.leafCount;
   for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  A.blobStride = sizeof(Rec);
+  A.blobs.resize(recs.size() * sizeof(Rec));
+  memcpy(A.blobs.data(), recs.data(), A.blobs.size());
+  return true;
+}
+
+// Triangle meshes with more than one time step (scene.cpp:213-247).  Every name is served by the one TriMBRecord layout: default =
+// Pluecker + robust traversal for a robust scene, Moeller + fast traversal otherwise; an explicit triangle4imb / triangle4vmb accel is
+// the fast (Moeller) variant.
+static void build_trimb_accel(Scene* s)
+{
+  Accel& A = s->triMBAccel;
+  A.clear();
+  const std::string& name = s->device->tri_accel_mb;
+  bool pluecker;
+  if (name == "default") pluecker = s->isRobust();
+  else if (name == "bvh8.triangle4imb" || name == "bvh4.triangle4imb" || name == "bvh8.triangle4vmb" || name == "bvh4.triangle4vmb") pluecker = false;
+  else RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown motion blur triangle acceleration structure " + name);
+
+  std::vector<TriMBRecord> recs;
+  auto fill = [](TriMBRecord& r, const V3* v) {
+    r.a0x = v[0].x; r.a0y = v[0].y; r.a0z = v[0].z;
+    r.b0x = v[1].x; r.b0y = v[1].y; r.b0z = v[1].z;
+    r.c0x = v[2].x; r.c0y = v[2].y; r.c0z = v[2].z;
+    r.a1x = v[3].x; r.a1y = v[3].y; r.a1z = v[3].z;
+    r.b1x = v[4].x; r.b1y = v[4].y; r.b1z = v[4].z;
+    r.c1x = v[5].x; r.c1y = v[5].y; r.c1z = v[5].z;
+  };
+  if (!build_mb_bvh8<3>(s, A, RTC_GEOMETRY_TYPE_TRIANGLE, "too many motion blur triangle segments for the 26-bit leaf reference", recs, fill)) return;
   A.kind = pluecker ? ACCEL_TRIMB_PLUECKER : ACCEL_TRIMB_MOELLER; // only once there are records
   A.robust = pluecker ? 1 : 0;
-  A.blobStride = sizeof(TriMBRecord);
-  A.blobs.resize(recs.size() * sizeof(TriMBRecord));
-  memcpy(A.blobs.data(), recs.data(), A.blobs.size());
+}
+
+// Quad meshes with more than one time step (scene.cpp:332-367): QuadMBRecords, default = Pluecker + robust traversal for a robust
+// scene, Moeller + fast traversal otherwise; an explicit quad4imb accel is the fast (Moeller) variant.  A host-only device builds
+// this accel only when its config names quad_accel_mb= (Device::quads_mb_enabled; build_mesh_bvh8 raises otherwise).
+static void build_quadmb_accel(Scene* s)
+{
+  Accel& A = s->quadMBAccel;
+  A.clear();
+  const std::string& name = s->device->quad_accel_mb;
+  bool pluecker;
+  if (name == "default") pluecker = s->isRobust();
+  else if (name == "bvh8.quad4imb" || name == "bvh4.quad4imb") pluecker = false;
+  else RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown motion blur quad acceleration structure " + name);
+
+  std::vector<QuadMBRecord> recs;
+  auto fill = [](QuadMBRecord& q, const V3* v) {
+    q.v0ax = v[0].x; q.v0ay = v[0].y; q.v0az = v[0].z;
+    q.v1ax = v[1].x; q.v1ay = v[1].y; q.v1az = v[1].z;
+    q.v2ax = v[2].x; q.v2ay = v[2].y; q.v2az = v[2].z;
+    q.v3ax = v[3].x; q.v3ay = v[3].y; q.v3az = v[3].z;
+    q.v0bx = v[4].x; q.v0by = v[4].y; q.v0bz = v[4].z;
+    q.v1bx = v[5].x; q.v1by = v[5].y; q.v1bz = v[5].z;
+    q.v2bx = v[6].x; q.v2by = v[6].y; q.v2bz = v[6].z;
+    q.v3bx = v[7].x; q.v3by = v[7].y; q.v3bz = v[7].z;
+  };
+  if (!build_mb_bvh8<4>(s, A, RTC_GEOMETRY_TYPE_QUAD, "too many motion blur quad segments for the 26-bit leaf reference", recs, fill)) return;
+  A.kind = pluecker ? ACCEL_QUADMB_PLUECKER : ACCEL_QUADMB_MOELLER; // only once there are records
+  A.robust = pluecker ? 1 : 0;
 }
 
 void Scene::commit()
@@ -494,6 +537,7 @@ void Scene::commit()
   build_triangle_accel(this);
   build_trimb_accel(this);
   build_quad_accel(this);
+  build_quadmb_accel(this);
   build_subdiv_accel(this);
   for (Accel* a : accels()) a->upload(device);
   if (progressFn) progressFn(progressUser, 1.0);
@@ -507,6 +551,9 @@ void Scene::commit()
     if (quadAccel.kind != ACCEL_NONE)
       fprintf(stderr, "embree3-amd: quad accel kind %u: %zu nodes (%zu B), %zu quads (%zu B), depth %u\n", quadAccel.kind, quadAccel.nodes.size(),
               quadAccel.nodes.size() * sizeof(QNode8), quadAccel.blobs.size() / sizeof(QuadRecord), quadAccel.blobs.size(), quadAccel.maxDepth);
+    if (quadMBAccel.kind != ACCEL_NONE)
+      fprintf(stderr, "embree3-amd: motion blur quad accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", quadMBAccel.kind, quadMBAccel.nodes.size(),
+              quadMBAccel.nodes.size() * sizeof(QNode8), quadMBAccel.blobs.size() / sizeof(QuadMBRecord), quadMBAccel.blobs.size(), quadMBAccel.maxDepth);
   }
   modified = false;
 }

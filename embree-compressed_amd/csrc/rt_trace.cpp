@@ -68,7 +68,8 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   // (quad leaves stay on the lane kernel unless RTAMD_KERNEL=pool: not measured)
   const bool poolPays = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER || A.kind == ACCEL_CBVH_GRID;
   p.poolKernel = dev->tunePoolKernel == 2u ? (poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel;
-  if (A.kind == ACCEL_TRIMB_PLUECKER || A.kind == ACCEL_TRIMB_MOELLER) p.poolKernel = 0u; // the motion-blur leaf exists in the lane kernel only (trace_tri_mb.hip)
+  if (A.kind == ACCEL_TRIMB_PLUECKER || A.kind == ACCEL_TRIMB_MOELLER || A.kind == ACCEL_QUADMB_PLUECKER || A.kind == ACCEL_QUADMB_MOELLER)
+    p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip)
   // worst-case stack: 7 siblings per level plus the entry being expanded.  The overflow area is sized for it, so a push
   // can only be dropped if the tree is deeper than the builder reported; the kernels then raise `overflow` (below).
   const uint32_t worst = 7u * (A.maxDepth + 1u) + 2u;

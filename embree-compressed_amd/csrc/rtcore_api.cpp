@@ -751,12 +751,13 @@ API void rtcamdSynchronizeDevice(RTCDevice h)
 API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 
 // the accel the inspection calls describe: the subdivision accel if there is one, else the triangle accel, else the motion-blur triangle
-// accel, else (quad-only scene) the quad accel
+// accel, else the quad accel, else (a scene of nothing but quads with time steps) the motion-blur quad accel
 static const Accel& exported_accel(const Scene* s)
 {
   if (s->subdivAccel.kind != ACCEL_NONE) return s->subdivAccel;
   if (s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind != ACCEL_NONE) return s->triMBAccel;
   if (s->triAccel.kind == ACCEL_NONE && s->quadAccel.kind != ACCEL_NONE) return s->quadAccel;
+  if (s->triAccel.kind == ACCEL_NONE && s->quadMBAccel.kind != ACCEL_NONE) return s->quadMBAccel;
   return s->triAccel;
 }
 

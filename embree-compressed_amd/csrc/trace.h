@@ -84,7 +84,7 @@ struct ServiceParams
   uint32_t* activity;  // device word: jobs served by any wavefront
 };
 // start the service kernel for base.accel.kind (and base.cbvhLevels); hipErrorInvalidValue: no service kernel for this accel kind / level
-// (the motion-blur triangle accel has none: rt_service.cpp hands its small calls to the combiner)
+// (the motion-blur triangle and quad accels have none: rt_service.cpp hands their small calls to the combiner)
 hipError_t launch_service_tri(const ServiceParams& s, hipStream_t stream);       // trace_tri.hip
 hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream);      // trace_quad.hip
 hipError_t launch_service_grid(const ServiceParams& s, hipStream_t stream);      // trace_grid.hip
@@ -121,6 +121,7 @@ hipError_t launch_trace_tri(const LaunchParams& p, hipStream_t stream);       //
 hipError_t launch_cull(const LaunchParams& p, hipStream_t stream);            // trace_tri.hip (trace_cull.hip.h): root cull pre-pass
 hipError_t launch_trace_quad(const LaunchParams& p, hipStream_t stream);      // trace_quad.hip
 hipError_t launch_trace_trimb(const LaunchParams& p, hipStream_t stream);     // trace_tri_mb.hip
+hipError_t launch_trace_quadmb(const LaunchParams& p, hipStream_t stream);    // trace_quad_mb.hip
 hipError_t launch_trace_grid(const LaunchParams& p, hipStream_t stream);      // trace_grid.hip
 hipError_t launch_trace_cbvh_box(const LaunchParams& p, hipStream_t stream);  // trace_cbvh_box.hip
 hipError_t launch_trace_cbvh_leaf(const LaunchParams& p, hipStream_t stream); // trace_cbvh_leaf.hip
@@ -154,6 +155,8 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_QUAD_MOELLER: return launch_trace_quad(p, stream);
   case ACCEL_TRIMB_PLUECKER:
   case ACCEL_TRIMB_MOELLER: return launch_trace_trimb(p, stream);
+  case ACCEL_QUADMB_PLUECKER:
+  case ACCEL_QUADMB_MOELLER: return launch_trace_quadmb(p, stream);
   case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
 #ifdef TRACE_DEV_METRIC_ONLY
   case ACCEL_GRIDSOA:

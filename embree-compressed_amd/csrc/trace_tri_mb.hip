@@ -13,6 +13,7 @@
 // Deviation: the reference's triangle4vmb leaf stores v0 and the per-segment deltas (trianglev_mb.h); here the vmb names run the
 // arithmetic of triangle4imb on the same records.
 #include "trace_leaf.hip.h"
+#include "trace_mb.hip.h"
 
 namespace rtamd {
 namespace dev {
@@ -22,28 +23,6 @@ namespace dev {
 #ifndef TRIMB_FETCH
 #define TRIMB_FETCH 2
 #endif
-
-__device__ __forceinline__ float ray_time(const LaunchParams& P, uint32_t rayIdx)
-{
-  return ((const float*)((const char*)P.rays + (size_t)rayIdx * P.stride))[7];
-}
-
-// lerp(p0, p1, f) of the reference (math.h): madd(1 - f, p0, f * p1); w is not interpolated
-__device__ __forceinline__ float4 lerp_vertex(const float4 p0, const float4 p1, float f)
-{
-  const float g = 1.0f - f;
-  return make_float4(madd(g, p0.x, f * p1.x), madd(g, p0.y, f * p1.y), madd(g, p0.z, f * p1.z), 0.0f);
-}
-
-// does the record with `segment` of a mesh with `numSegments` serve a ray at `time`?  f = ftime of the ray in that mesh
-__device__ __forceinline__ bool time_segment(float time, uint32_t segment, uint32_t numSegments, float& f)
-{
-  const float S = (float)numSegments;
-  const float ts = time * S;
-  const float itimef = fminf(fmaxf(floorf(ts), 0.0f), S - 1.0f);
-  f = ts - itimef;
-  return (uint32_t)(int)itimef == segment;
-}
 
 template <bool PLUECKER> struct TriMBLeaf : LeafTraits
 {

@@ -349,6 +349,32 @@ class Scene:
         self.device.check("add_quads")
         return gid
 
+    def add_quads_mb(self, verts_per_step, quads, geom_id=None):
+        """Motion-blur quad mesh: verts_per_step is a sequence of N >= 2 float32 [nv,3] arrays (time steps 0..N-1, vertex buffer
+        slots 0..N-1 after rtcSetGeometryTimeStepCount), quads uint32 [nq,4]; shared buffers like add_quads."""
+        L = self.lib
+        steps = [np.ascontiguousarray(v, dtype=np.float32) for v in verts_per_step]
+        q = np.ascontiguousarray(quads, dtype=np.uint32).reshape(-1, 4)
+        g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_QUAD)
+        self.device.check("rtcNewGeometry(QUAD)")
+        L.rtcSetGeometryTimeStepCount(g, len(steps))
+        for slot, v in enumerate(steps):
+            vpad = np.zeros((v.shape[0] + 2, 3), dtype=np.float32)
+            vpad[: v.shape[0]] = v
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_VERTEX, slot, RTC_FORMAT_FLOAT3, vpad.ctypes.data, 0, 12, v.shape[0])
+            self._keep.append(vpad)
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_INDEX, 0, RTC_FORMAT_UINT4, q.ctypes.data, 0, 16, q.shape[0])
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self._keep.append(q)
+        self.device.check("add_quads_mb")
+        return gid
+
     def add_subdiv(self, verts, face_sizes, face_index, level=1.0, geom_id=None, displacement=None, user_data=None,
                    edge_creases=None, vertex_creases=None):
         """edge_creases: (uint32 [k,2] vertex pairs, float32 [k] weights); vertex_creases: (uint32 [m], float32 [m])."""

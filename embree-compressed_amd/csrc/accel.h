@@ -6,7 +6,8 @@
 //   blobs   : bytes          cBVH / GridSOA leaf blobs for subdivision geometry (16-byte aligned each),
 //                            or QuadRecord[] (64-byte quad records, leaf-contiguous) for quad geometry,
 //                            or TriMBRecord[] (96-byte motion-blur triangle records, leaf-contiguous) for triangle meshes with time steps,
-//                            or QuadMBRecord[] (128-byte motion-blur quad records, leaf-contiguous) for quad meshes with time steps
+//                            or QuadMBRecord[] (128-byte motion-blur quad records, leaf-contiguous) for quad meshes with time steps,
+//                            or InstanceRecord[] (64-byte instance records, one per top-level leaf) for instances
 // The reference keeps the same information behind 64-bit tagged pointers (kernels/bvh/bvh.h:150-396,
 // AlignedNode :433-594, QuantizedNode :1150-1324, Triangle4v kernels/geometry/trianglev.h:24-162).
 #pragma once
@@ -136,6 +137,25 @@ struct alignas(16) QuadMBRecord
 };
 static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 
+// ---- instance record, 64 bytes = 4 x dwordx4 -------------------------------------------------------------------------
+// One per enabled instance of the scene (Instance, kernels/common/scene_instance.h).  The instance accel keeps, in ONE node array, a
+// top-level BVH8 over the instances' world bounds with exactly one instance per leaf (leaf reference = make_tri_leaf(record index, 1))
+// and behind it a copy of the triangle tree of every distinct instanced scene, child indices and leaf record offsets rebased into the
+// accel's own `nodes` / `prims`; `root` is the rebased root reference of this instance's scene.
+// world2local = inverse(local2world) as the columns vx, vy, vz, p of an AffineSpace3f: a ray enters the instance as
+// org' = xfmPoint(world2local, org), dir' = xfmVector(world2local, dir) (instance_intersector.cpp:51-56); t is common to both spaces.
+struct alignas(16) InstanceRecord
+{
+  float world2local[12]; // vx.xyz, vy.xyz, vz.xyz, p.xyz
+  uint32_t geomID;       // of the instance in the top scene: the hit's instID (instance_intersector.cpp:57)
+  uint32_t root;         // rebased root reference of the instanced scene's triangle tree
+  uint32_t pad[2];
+};
+static_assert(sizeof(InstanceRecord) == 64, "InstanceRecord must be 64 bytes");
+// Marker on the traversal stack of the instance kernel (trace_instance.hip): popping it leaves the instance.  A leaf-flagged reference with
+// count 0, which make_tri_leaf never produces (counts are 1..28), and not REF_EMPTY.
+static const uint32_t REF_INST_EXIT = 0x80000000u;
+
 // ---- eager subdivision leaf: one 3x3-vertex cell (2x2 quads = 8 triangles), 160 bytes = 10 x dwordx4 ------
 // Replaces the inner leaves of GridSOA (kernels/geometry/grid_soa.h:267-286, :85-90): the reference stores whole
 // <=9x9 sub-grids in SoA form and a private BVH4 down to 3x3-vertex cells; here every cell is self-contained and the
@@ -219,7 +239,9 @@ enum AccelKind : uint32_t
   ACCEL_TRIMB_PLUECKER = 10, // tri_accel_mb=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:213-247): interpolated triangle + Pluecker, robust traversal
   ACCEL_TRIMB_MOELLER = 11,  // tri_accel_mb=default / bvh8.triangle4imb / bvh4.triangle4imb / *.triangle4vmb: interpolated triangle + Moeller, fast traversal
   ACCEL_QUADMB_PLUECKER = 12, // quad_accel_mb=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:332-367): interpolated quad + Pluecker, robust traversal
-  ACCEL_QUADMB_MOELLER = 13   // quad_accel_mb=default / bvh8.quad4imb / bvh4.quad4imb: interpolated quad + Moeller, fast traversal
+  ACCEL_QUADMB_MOELLER = 13,  // quad_accel_mb=default / bvh8.quad4imb / bvh4.quad4imb: interpolated quad + Moeller, fast traversal
+  ACCEL_INST_TRI_PLUECKER = 14, // instances of scenes whose triangle accel is ACCEL_TRI_PLUECKER: robust traversal on both levels
+  ACCEL_INST_TRI_MOELLER = 15   // instances of scenes whose triangle accel is ACCEL_TRI_MOELLER: fast traversal on both levels
 };
 
 // What a kernel launch needs to know about one committed scene.
@@ -227,7 +249,7 @@ struct AccelDesc
 {
   const QNode8* nodes;
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[]
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind
@@ -246,7 +268,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (up to five launches per batch: triangles, motion-blur triangles, quads, motion-blur quads, subdiv)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (up to six launches per batch: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, instances)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

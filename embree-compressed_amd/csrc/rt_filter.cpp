@@ -168,8 +168,11 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
         const bool found = got.hit.geomID != RTC_INVALID_GEOMETRY_ID &&
                            (got.ray.tfar != W[i].ray.tfar || got.hit.primID != W[i].hit.primID || got.hit.geomID != W[i].hit.geomID);
         if (!found) continue; // miss: the caller's record stays as it is
-        // the hit reports instID in geomID when instanced; instancing is not on this path, so geomID is the geometry
-        Geometry* geo = got.hit.geomID < s->geometries.size() ? s->geometries[got.hit.geomID] : nullptr;
+        // a hit inside an instance names a geometry of the INSTANCED scene, and no filter applies to it (geometry filters inside instanced
+        // scenes are refused at commit, context filters on scenes with instances at the call): accepted as it is.  Such a hit carries the
+        // instance's geomID in instID, every other hit the context's value.
+        const bool onInstance = s->hasInstances() && got.hit.instID[0] != instID;
+        Geometry* geo = !onInstance && got.hit.geomID < s->geometries.size() ? s->geometries[got.hit.geomID] : nullptr;
         const bool onSubdiv = geo && geo->type == RTC_GEOMETRY_TYPE_SUBDIVISION;
         const bool unfiltered = onSubdiv && forkAccel;
         RTCFilterFunctionN fn = geo && !unfiltered ? (occluded ? geo->occludedFilter : geo->intersectFilter) : nullptr;

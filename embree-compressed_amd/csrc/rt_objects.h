@@ -267,6 +267,12 @@ struct Geometry : RefCounted
   std::shared_ptr<void> interpCache;
   std::mutex interpMutex;
 
+  // RTC_GEOMETRY_TYPE_INSTANCE (reference: Instance, kernels/common/scene_instance.h): the instanced scene (retained) and the
+  // local-to-world transform of time step 0 as the columns vx, vy, vz, p of an AffineSpace3f (identity by default)
+  Scene* instScene = nullptr;
+  float local2world[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+  void setInstancedScene(Scene* s);
+
   Geometry(Device* d, RTCGeometryType t);
   ~Geometry() override;
 
@@ -344,9 +350,11 @@ struct Scene : RefCounted
   Accel quadAccel;   // quads with one time step (QuadRecord[] in `blobs`); traced after the triangles, before the motion-blur quads
   Accel quadMBAccel; // quads with several time steps (QuadMBRecord[] in `blobs`); traced after the static quads, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
-  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV index whatever a path keeps per accel
-  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, NUM_ACCELS = 5 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel}; }
+  Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle trees behind the top-level tree); traced last (scene.cpp:661-665)
+  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / INST index whatever a path keeps per accel
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, INST = 5, NUM_ACCELS = 6 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &instAccel}; }
+  bool hasInstances() const { return instAccel.kind != ACCEL_NONE; }
 
   explicit Scene(Device* d);
   ~Scene() override;

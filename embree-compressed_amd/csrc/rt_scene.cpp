@@ -1,5 +1,6 @@
 // Geometry / Scene objects, accel selection at commit, upload to HBM.
 #include <algorithm>
+#include <map>
 
 #include "bvh8_builder.h"
 #include "rt_objects.h"
@@ -14,7 +15,18 @@ Geometry::Geometry(Device* d, RTCGeometryType t) : device(d), type(t) { device->
 Geometry::~Geometry()
 {
   for (auto& kv : views) kv.second.clear();
+  if (instScene) instScene->release();
   device->release();
+}
+
+void Geometry::setInstancedScene(Scene* s)
+{
+  if (type != RTC_GEOMETRY_TYPE_INSTANCE) RT_THROW(RTC_ERROR_INVALID_OPERATION, "operation not supported for this geometry");
+  if (s->device != device) RT_THROW(RTC_ERROR_INVALID_OPERATION, "inputs are from different devices");
+  s->retain();
+  if (instScene) instScene->release();
+  instScene = s;
+  committed = false;
 }
 
 BufferView* Geometry::view(RTCBufferType t, unsigned slot)
@@ -509,6 +521,143 @@ static void build_quadmb_accel(Scene* s)
   A.robust = pluecker ? 1 : 0;
 }
 
+// world2local = inverse(local2world), both as the columns vx, vy, vz, p: inverted in double precision and rounded once to fp32
+// (deviation: the reference inverts in fp32 with its rcp, affinespace.h rcp()).  false: singular (or not finite) - the caller stores
+// an all-zero matrix, under which no triangle test passes (the local direction is 0: den == 0 in both tests).
+static bool invert_affine(const float* m, float* out)
+{
+  const double a[3][3] = {{m[0], m[3], m[6]}, {m[1], m[4], m[7]}, {m[2], m[5], m[8]}}; // a[row][col], columns vx vy vz
+  const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1], c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2], c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];
+  const double det = a[0][0] * c00 + a[0][1] * c01 + a[0][2] * c02;
+  if (!(det != 0.0) || !std::isfinite(det)) return false;
+  double inv[3][3];
+  inv[0][0] = c00 / det;
+  inv[1][0] = c01 / det;
+  inv[2][0] = c02 / det;
+  inv[0][1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det;
+  inv[1][1] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det;
+  inv[2][1] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det;
+  inv[0][2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det;
+  inv[1][2] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det;
+  inv[2][2] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det;
+  float r[12];
+  for (int col = 0; col < 3; col++)
+    for (int row = 0; row < 3; row++) r[3 * col + row] = (float)inv[row][col];
+  for (int row = 0; row < 3; row++) r[9 + row] = (float)-(inv[row][0] * m[9] + inv[row][1] * m[10] + inv[row][2] * m[11]);
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(r[i])) return false;
+  memcpy(out, r, sizeof(r));
+  return true;
+}
+
+// xfmPoint (affinespace.h:110): madd(p.x, vx, madd(p.y, vy, madd(p.z, vz, p)))
+static V3 xfm_point(const float* m, V3 q)
+{
+  V3 r;
+  for (int k = 0; k < 3; k++) r[k] = fmaf(q.x, m[k], fmaf(q.y, m[3 + k], fmaf(q.z, m[6 + k], m[9 + k])));
+  return r;
+}
+
+// Instances (RTC_GEOMETRY_TYPE_INSTANCE, one time step, one level): a top-level BVH8 over the instances' world bounds - xfmBounds of
+// the instanced scene's bounds, its eight transformed corners (instance_intersector.cpp:24-39, affinespace.h:114-126) - with ONE
+// instance per leaf, followed in the same arrays by the triangle tree and records of every distinct instanced scene, rebased.  The
+// instanced scenes were committed before; what this commit sees of them is their committed triangle accel.
+static void build_instance_accel(Scene* s)
+{
+  Accel& A = s->instAccel;
+  A.clear();
+  struct Src { unsigned geomID; Scene* scene; };
+  std::vector<Src> src;
+  std::vector<BuildPrim> bp;
+  uint32_t kind = ACCEL_NONE;
+  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
+    Geometry* g = s->geometries[gid];
+    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_INSTANCE) continue;
+    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instances with more than one time step are not supported");
+    Scene* o = g->instScene;
+    if (!o) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance without an instanced scene");
+    if (o->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instanced scene got not committed");
+    for (Geometry* og : o->geometries) {
+      if (!og || !og->enabled) continue;
+      if (og->type != RTC_GEOMETRY_TYPE_TRIANGLE || og->timeSteps != 1)
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene may hold static triangle meshes only (no quads, time steps, subdivision meshes or instances)");
+      if (og->intersectFilter || og->occludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
+    }
+    for (const Accel* oa : o->accels())
+      if (oa != &o->triAccel && oa->kind != ACCEL_NONE)
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene may hold static triangle meshes only (no quads, time steps, subdivision meshes or instances)");
+    if (o->triIntersectFilter || o->triOccludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
+    if (!o->triAccel.traceable()) continue; // empty scene: nothing to hit
+    if (kind != ACCEL_NONE && kind != o->triAccel.kind)
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
+    kind = o->triAccel.kind;
+    BuildPrim p;
+    const V3 c[2] = {o->bounds.lo, o->bounds.hi};
+    for (int i = 0; i < 8; i++) p.box.extend(xfm_point(g->local2world, V3(c[i >> 2].x, c[(i >> 1) & 1].y, c[i & 1].z)));
+    if (!(std::isfinite(p.box.lo.x) && std::isfinite(p.box.lo.y) && std::isfinite(p.box.lo.z) && std::isfinite(p.box.hi.x) && std::isfinite(p.box.hi.y) && std::isfinite(p.box.hi.z)))
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance transform yields bounds that are not finite");
+    p.id = (uint32_t)src.size();
+    src.push_back({gid, o});
+    bp.push_back(p);
+  }
+  if (bp.empty()) return;
+  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances for the 26-bit leaf reference");
+
+  // top-level tree, one instance per leaf: leaf reference = record index, count 1
+  std::vector<InstanceRecord> recs(bp.size());
+  std::vector<uint32_t> order; // record index -> src index, leaf order
+  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
+    if (end - begin != 1) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: a leaf must hold one instance");
+    order.push_back(prims[begin].id);
+    return make_tri_leaf((uint32_t)order.size() - 1u, 1u);
+  };
+  BuildSettings cfg;
+  cfg.blockSize = 1; cfg.minLeaf = 1; cfg.maxLeaf = 1;
+  cfg.threads = 1; // the leaf callback appends in leaf order
+  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
+  A.nodes = std::move(r.nodes);
+  A.root = r.root;
+  A.leafCount = r.leafCount;
+
+  // the distinct instanced scenes' trees behind it, rebased
+  std::map<Scene*, uint32_t> rootOf;
+  uint32_t deepest = 0;
+  for (const Src& sr : src) {
+    if (rootOf.count(sr.scene)) continue;
+    const Accel& O = sr.scene->triAccel;
+    const size_t nodeBase = A.nodes.size(), primBase = A.prims.size();
+    if (primBase + O.prims.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced triangles for the 26-bit leaf reference");
+    if (nodeBase + O.nodes.size() >= (size_t)REF_LEAF) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced nodes for the 31-bit node reference");
+    auto rebase = [&](uint32_t ref) -> uint32_t {
+      if (ref == REF_EMPTY) return ref;
+      if (ref & REF_LEAF) return ref + (uint32_t)primBase; // first record in bits 0..25, guarded above
+      return ref + (uint32_t)nodeBase;
+    };
+    for (QNode8 n : O.nodes) {
+      for (uint32_t& c : n.child) c = rebase(c);
+      A.nodes.push_back(n);
+    }
+    A.prims.insert(A.prims.end(), O.prims.begin(), O.prims.end());
+    rootOf[sr.scene] = rebase(O.root);
+    deepest = std::max(deepest, O.maxDepth);
+  }
+  for (size_t i = 0; i < order.size(); i++) {
+    const Src& sr = src[order[i]];
+    InstanceRecord& rec = recs[i];
+    memset(&rec, 0, sizeof(rec));
+    if (!invert_affine(s->geometries[sr.geomID]->local2world, rec.world2local)) memset(rec.world2local, 0, sizeof(rec.world2local)); // singular: never hit
+    rec.geomID = sr.geomID;
+    rec.root = rootOf[sr.scene];
+  }
+  A.kind = kind == ACCEL_TRI_PLUECKER ? ACCEL_INST_TRI_PLUECKER : ACCEL_INST_TRI_MOELLER;
+  A.robust = kind == ACCEL_TRI_PLUECKER ? 1 : 0;
+  A.maxDepth = r.maxDepth + 1u + deepest; // top-level levels, the exit marker, the deepest instanced tree (launch_on's stack bound)
+  A.blobStride = sizeof(InstanceRecord);
+  A.blobs.resize(recs.size() * sizeof(InstanceRecord));
+  memcpy(A.blobs.data(), recs.data(), A.blobs.size());
+}
+
 void Scene::commit()
 {
   std::lock_guard<std::mutex> g(buildMutex);
@@ -518,7 +667,8 @@ void Scene::commit()
     switch (geo->type) {
     case RTC_GEOMETRY_TYPE_TRIANGLE:
     case RTC_GEOMETRY_TYPE_QUAD:
-    case RTC_GEOMETRY_TYPE_SUBDIVISION: break;
+    case RTC_GEOMETRY_TYPE_SUBDIVISION:
+    case RTC_GEOMETRY_TYPE_INSTANCE: break;
     default: // scene.cpp:25-30: geometry types compiled out raise INVALID_OPERATION
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry type not supported by the MI355X traversal path");
     }
@@ -529,7 +679,7 @@ void Scene::commit()
     if (geo->type == RTC_GEOMETRY_TYPE_TRIANGLE || geo->type == RTC_GEOMETRY_TYPE_QUAD) {
       triIntersectFilter |= geo->intersectFilter != nullptr;
       triOccludedFilter |= geo->occludedFilter != nullptr;
-    } else
+    } else if (geo->type == RTC_GEOMETRY_TYPE_SUBDIVISION)
       subdivFilter |= geo->intersectFilter != nullptr || geo->occludedFilter != nullptr;
   }
   if (progressFn && !progressFn(progressUser, 0.0)) RT_THROW(RTC_ERROR_CANCELLED, "progress monitor forced termination");
@@ -539,6 +689,7 @@ void Scene::commit()
   build_quad_accel(this);
   build_quadmb_accel(this);
   build_subdiv_accel(this);
+  build_instance_accel(this);
   for (Accel* a : accels()) a->upload(device);
   if (progressFn) progressFn(progressUser, 1.0);
   if (device->verbose >= 2) {
@@ -555,6 +706,9 @@ void Scene::commit()
       fprintf(stderr, "embree3-amd: motion blur quad accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", quadMBAccel.kind, quadMBAccel.nodes.size(),
               quadMBAccel.nodes.size() * sizeof(QNode8), quadMBAccel.blobs.size() / sizeof(QuadMBRecord), quadMBAccel.blobs.size(), quadMBAccel.maxDepth);
   }
+  if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
+    fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, depth %u\n", instAccel.kind, instAccel.nodes.size(),
+            instAccel.nodes.size() * sizeof(QNode8), instAccel.blobs.size() / sizeof(InstanceRecord), instAccel.prims.size(), instAccel.maxDepth);
   modified = false;
 }
 

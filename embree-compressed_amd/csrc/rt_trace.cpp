@@ -70,6 +70,8 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   p.poolKernel = dev->tunePoolKernel == 2u ? (poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel;
   if (A.kind == ACCEL_TRIMB_PLUECKER || A.kind == ACCEL_TRIMB_MOELLER || A.kind == ACCEL_QUADMB_PLUECKER || A.kind == ACCEL_QUADMB_MOELLER)
     p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip)
+  const bool instKernel = A.kind == ACCEL_INST_TRI_PLUECKER || A.kind == ACCEL_INST_TRI_MOELLER;
+  if (instKernel) p.poolKernel = 0u; // the two-level kernel is a lane-per-ray kernel of its own (trace_instance.hip): no pool form, no root cull pre-pass
   // worst-case stack: 7 siblings per level plus the entry being expanded.  The overflow area is sized for it, so a push
   // can only be dropped if the tree is deeper than the builder reported; the kernels then raise `overflow` (below).
   const uint32_t worst = 7u * (A.maxDepth + 1u) + 2u;
@@ -137,7 +139,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   // Root cull pre-pass (trace_cull.hip.h): large batches on the lane kernel whose root is an inner node.  Filter re-traces
   // (exclusion lists) are small and skip it.
   p.survivors = nullptr;
-  if (dev->tuneCull && !p.poolKernel && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
+  if (dev->tuneCull && !p.poolKernel && !instKernel && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
     const size_t need = ((size_t)(M + TRACE_QUEUES - 1) / TRACE_QUEUES) * TRACE_QUEUES * 4u;
     if (need > ctx.survivorsBytes) { // first batch of this size on this context (an allocation synchronises the device)
       HIP_CHECK(hipStreamSynchronize(stream));
@@ -283,6 +285,10 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
   Device* dev = s->device;
   if (s->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "scene got not committed"); // scene.cpp:25,54
   if (M == 0) return;
+  if (s->hasInstances()) { // refused before anything touches the GPU
+    if (ctx && ctx->filter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "RTCIntersectContext::filter is not supported on a scene with instances");
+    if (countersOut) RT_THROW(RTC_ERROR_INVALID_OPERATION, "counted batches are not supported on a scene with instances");
+  }
   dev->useDevice();
   if (byteStride > 0xFFFFFFFFull) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "byteStride too large");
   if (((uintptr_t)rays) & 3) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "ray not aligned to 4 bytes"); // rtcore.cpp:413

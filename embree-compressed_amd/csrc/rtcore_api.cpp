@@ -158,8 +158,8 @@ API RTCGeometry rtcNewGeometry(RTCDevice h, enum RTCGeometryType type)
   case RTC_GEOMETRY_TYPE_QUAD:
     if (!D(h)->quads_enabled()) unsupported("RTC_GEOMETRY_TYPE_QUAD on a host-only device without quad_accel=");
     return (RTCGeometry) new Geometry(D(h), type);
+  case RTC_GEOMETRY_TYPE_INSTANCE: return (RTCGeometry) new Geometry(D(h), type); // every device, host-only ones included
   case RTC_GEOMETRY_TYPE_USER: unsupported("RTC_GEOMETRY_TYPE_USER");
-  case RTC_GEOMETRY_TYPE_INSTANCE: unsupported("RTC_GEOMETRY_TYPE_INSTANCE");
   case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE:
   case RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE:
   case RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE:
@@ -309,9 +309,55 @@ API void rtcFilterOcclusion(const struct RTCOccludedFunctionNArguments*, const s
 {
   CATCH_BEGIN unsupported("rtcFilterOcclusion"); CATCH_END(nullptr)
 }
-API void rtcSetGeometryInstancedScene(RTCGeometry h, RTCScene) { CATCH_BEGIN VERIFY(h); unsupported("instancing"); CATCH_END(devOf(h)) }
-API void rtcSetGeometryTransform(RTCGeometry h, unsigned int, enum RTCFormat, const void*) { CATCH_BEGIN VERIFY(h); unsupported("instancing"); CATCH_END(devOf(h)) }
-API void rtcGetGeometryTransform(RTCGeometry h, float, enum RTCFormat, void*) { CATCH_BEGIN VERIFY(h); unsupported("instancing"); CATCH_END(devOf(h)) }
+// ---- instances (rtcore.cpp:870-965) ------------------------------------------------------------------------------------
+API void rtcSetGeometryInstancedScene(RTCGeometry h, RTCScene scene)
+{
+  CATCH_BEGIN
+  VERIFY(h);
+  VERIFY(scene);
+  G(h)->setInstancedScene(S(scene));
+  CATCH_END(devOf(h))
+}
+
+// index of element (row, column) of the 3x4 affine matrix [vx vy vz p] in a caller's array of `format`; -1: not a transform format
+// (loadTransform / storeTransform, rtcore.cpp:882-943)
+static int transform_index(enum RTCFormat format, int row, int col)
+{
+  switch (format) {
+  case RTC_FORMAT_FLOAT3X4_ROW_MAJOR: return 4 * row + col;
+  case RTC_FORMAT_FLOAT3X4_COLUMN_MAJOR: return 3 * col + row;
+  case RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR: return 4 * col + row;
+  default: return -1;
+  }
+}
+
+API void rtcSetGeometryTransform(RTCGeometry h, unsigned int timeStep, enum RTCFormat format, const void* xfm)
+{
+  CATCH_BEGIN
+  VERIFY(h);
+  VERIFY(xfm);
+  if (G(h)->type != RTC_GEOMETRY_TYPE_INSTANCE) RT_THROW(RTC_ERROR_INVALID_OPERATION, "operation not supported for this geometry");
+  if (transform_index(format, 0, 0) < 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid matrix format");
+  if (timeStep != 0) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instances with more than one time step are not supported: only time step 0 takes a transform");
+  for (int col = 0; col < 4; col++)
+    for (int row = 0; row < 3; row++) G(h)->local2world[3 * col + row] = ((const float*)xfm)[transform_index(format, row, col)];
+  G(h)->committed = false;
+  CATCH_END(devOf(h))
+}
+
+API void rtcGetGeometryTransform(RTCGeometry h, float, enum RTCFormat format, void* xfm)
+{
+  CATCH_BEGIN
+  VERIFY(h);
+  VERIFY(xfm);
+  if (G(h)->type != RTC_GEOMETRY_TYPE_INSTANCE) RT_THROW(RTC_ERROR_INVALID_OPERATION, "operation not supported for this geometry");
+  if (transform_index(format, 0, 0) < 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid matrix format");
+  for (int col = 0; col < 4; col++)
+    for (int row = 0; row < 3; row++) ((float*)xfm)[transform_index(format, row, col)] = G(h)->local2world[3 * col + row];
+  if (format == RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR) // the bottom row (storeTransform, rtcore.cpp:934-940)
+    for (int col = 0; col < 4; col++) ((float*)xfm)[4 * col + 3] = col == 3 ? 1.0f : 0.0f;
+  CATCH_END(devOf(h))
+}
 
 API void rtcSetGeometryTessellationRate(RTCGeometry h, float rate) { CATCH_BEGIN VERIFY(h); G(h)->tessellationRate = rate; CATCH_END(devOf(h)) }
 
@@ -751,13 +797,15 @@ API void rtcamdSynchronizeDevice(RTCDevice h)
 API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 
 // the accel the inspection calls describe: the subdivision accel if there is one, else the triangle accel, else the motion-blur triangle
-// accel, else the quad accel, else (a scene of nothing but quads with time steps) the motion-blur quad accel
+// accel, else the quad accel, else (a scene of nothing but quads with time steps) the motion-blur quad accel, else (a scene of nothing
+// but instances) the instance accel
 static const Accel& exported_accel(const Scene* s)
 {
   if (s->subdivAccel.kind != ACCEL_NONE) return s->subdivAccel;
   if (s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind != ACCEL_NONE) return s->triMBAccel;
   if (s->triAccel.kind == ACCEL_NONE && s->quadAccel.kind != ACCEL_NONE) return s->quadAccel;
   if (s->triAccel.kind == ACCEL_NONE && s->quadMBAccel.kind != ACCEL_NONE) return s->quadMBAccel;
+  if (s->triAccel.kind == ACCEL_NONE && s->instAccel.kind != ACCEL_NONE) return s->instAccel;
   return s->triAccel;
 }
 

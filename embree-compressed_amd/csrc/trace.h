@@ -84,7 +84,7 @@ struct ServiceParams
   uint32_t* activity;  // device word: jobs served by any wavefront
 };
 // start the service kernel for base.accel.kind (and base.cbvhLevels); hipErrorInvalidValue: no service kernel for this accel kind / level
-// (the motion-blur triangle and quad accels have none: rt_service.cpp hands their small calls to the combiner)
+// (the motion-blur triangle and quad accels and the instance accel have none: rt_service.cpp hands their small calls to the combiner)
 hipError_t launch_service_tri(const ServiceParams& s, hipStream_t stream);       // trace_tri.hip
 hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream);      // trace_quad.hip
 hipError_t launch_service_grid(const ServiceParams& s, hipStream_t stream);      // trace_grid.hip
@@ -127,6 +127,7 @@ hipError_t launch_trace_cbvh_box(const LaunchParams& p, hipStream_t stream);  //
 hipError_t launch_trace_cbvh_leaf(const LaunchParams& p, hipStream_t stream); // trace_cbvh_leaf.hip
 hipError_t launch_trace_cbvh_grid(const LaunchParams& p, hipStream_t stream); // trace_cbvh_grid.hip
 hipError_t launch_trace_cbvh_full(const LaunchParams& p, hipStream_t stream); // trace_cbvh_full.hip
+hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  // trace_instance.hip
 // Development builds (-DTRACE_DEV_METRIC_ONLY, tools/README.md): of the subdivision accels only the metric's kind is dispatched (the
 // others fail with hipErrorInvalidValue, so that only trace_cbvh_leaf.hip has to be rebuilt), and launch_service serves no other kind.
 inline hipError_t launch_service(const ServiceParams& s, hipStream_t stream)
@@ -157,6 +158,8 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_TRIMB_MOELLER: return launch_trace_trimb(p, stream);
   case ACCEL_QUADMB_PLUECKER:
   case ACCEL_QUADMB_MOELLER: return launch_trace_quadmb(p, stream);
+  case ACCEL_INST_TRI_PLUECKER:
+  case ACCEL_INST_TRI_MOELLER: return launch_trace_instance(p, stream);
   case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
 #ifdef TRACE_DEV_METRIC_ONLY
   case ACCEL_GRIDSOA:

@@ -18,6 +18,7 @@ RTC_INVALID_GEOMETRY_ID = 0xFFFFFFFF
 RTC_GEOMETRY_TYPE_TRIANGLE = 0
 RTC_GEOMETRY_TYPE_QUAD = 1
 RTC_GEOMETRY_TYPE_SUBDIVISION = 8
+RTC_GEOMETRY_TYPE_INSTANCE = 121
 RTC_BUFFER_TYPE_INDEX = 0
 RTC_BUFFER_TYPE_VERTEX = 1
 RTC_BUFFER_TYPE_VERTEX_ATTRIBUTE = 2
@@ -32,6 +33,9 @@ RTC_FORMAT_UINT3 = 0x5003
 RTC_FORMAT_UINT4 = 0x5004
 RTC_FORMAT_FLOAT = 0x9001
 RTC_FORMAT_FLOAT3 = 0x9003
+RTC_FORMAT_FLOAT3X4_ROW_MAJOR = 0x9134
+RTC_FORMAT_FLOAT3X4_COLUMN_MAJOR = 0x9234
+RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR = 0x9244
 RTC_SCENE_FLAG_NONE = 0
 RTC_SCENE_FLAG_ROBUST = 4
 RTC_ERROR_NONE, RTC_ERROR_UNKNOWN, RTC_ERROR_INVALID_ARGUMENT, RTC_ERROR_INVALID_OPERATION = 0, 1, 2, 3
@@ -143,6 +147,9 @@ def load_library(path=LIB_PATH):
         "rtcSetGeometryUserData": (None, [vp, vp]),
         "rtcSetGeometryIntersectFilterFunction": (None, [vp, vp]),
         "rtcSetGeometryOccludedFilterFunction": (None, [vp, vp]),
+        "rtcSetGeometryInstancedScene": (None, [vp, vp]),
+        "rtcSetGeometryTransform": (None, [vp, u, C.c_int, vp]),
+        "rtcGetGeometryTransform": (None, [vp, C.c_float, C.c_int, vp]),
         "rtcNewScene": (vp, [vp]),
         "rtcRetainScene": (None, [vp]),
         "rtcReleaseScene": (None, [vp]),
@@ -417,6 +424,46 @@ class Scene:
         self._keep += [vpad, fs, fi, lv]
         self.device.check("add_subdiv")
         return gid
+
+    def add_instance(self, scene, xfm=None, geom_id=None):
+        """RTC_GEOMETRY_TYPE_INSTANCE of `scene` (a committed Scene of static triangle meshes on the same device).  xfm: the
+        local-to-world transform as a float32 [3,4] row-major matrix (None: identity)."""
+        L = self.lib
+        g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_INSTANCE)
+        self.device.check("rtcNewGeometry(INSTANCE)")
+        L.rtcSetGeometryInstancedScene(g, scene.handle)
+        if xfm is not None:
+            m = np.ascontiguousarray(xfm, dtype=np.float32).reshape(3, 4)
+            L.rtcSetGeometryTransform(g, 0, RTC_FORMAT_FLOAT3X4_ROW_MAJOR, m.ctypes.data)
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self._keep.append(scene)
+        self.device.check("add_instance")
+        return gid
+
+    def set_instance_transform(self, geom_id, xfm, fmt=RTC_FORMAT_FLOAT3X4_ROW_MAJOR):
+        """Set the local-to-world transform of an attached instance and re-commit the geometry (the scene is committed by the caller).
+        xfm: float32 values in `fmt` (3x4 row-major by default; 3x4 or 4x4 column-major)."""
+        g = self.lib.rtcGetGeometry(self.handle, geom_id)
+        m = np.ascontiguousarray(xfm, dtype=np.float32).reshape(-1)
+        self.lib.rtcSetGeometryTransform(g, 0, fmt, m.ctypes.data)
+        self.lib.rtcCommitGeometry(g)
+        self.device.check("set_instance_transform")
+
+    def get_instance_transform(self, geom_id, fmt=RTC_FORMAT_FLOAT3X4_ROW_MAJOR):
+        """The stored local-to-world transform in `fmt`: float32 [3,4] (row-major), [12] (3x4 column-major) or [16] (4x4 column-major)."""
+        g = self.lib.rtcGetGeometry(self.handle, geom_id)
+        out = np.zeros(16, np.float32)
+        self.lib.rtcGetGeometryTransform(g, 0.0, fmt, out.ctypes.data)
+        self.device.check("get_instance_transform")
+        if fmt == RTC_FORMAT_FLOAT3X4_ROW_MAJOR:
+            return out[:12].reshape(3, 4).copy()
+        return out[:16 if fmt == RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR else 12].copy()
 
     def set_filters(self, geom_id, intersect=None, occluded=None):
         """intersect / occluded: FILTER_FUNC objects (kept alive by the scene wrapper) or None."""

@@ -183,6 +183,12 @@ struct Device : RefCounted
   // to the other batches, and takes its rays in fewer, larger grabs).
   uint32_t tuneChunk = 256, tuneLeafBatch = 32, tuneBlocksPerCU = 2;
   uint32_t tuneChunkBusy = 512; // env RTAMD_CHUNK_BUSY: upper bound of the chunk of a large batch launched while two or more others run (rt_trace.cpp launch_on)
+  // env RTAMD_WG_POOL=0|1: workgroup ray pool of the lane kernel (trace_loop.hip.h RayPool); 0 = every wave grabs for itself, 1 = always shared,
+  // unset (2) = shared from tuneWgPoolMinRays rays per launch on.  Measured on MI355X, cbvh.leaf, four batches in flight, parent -> pool
+  // (profiles/r04_wg_pool_ab.txt): 1 M rays 13.08 -> 13.65 Grays/s, 128 k 3.45 -> 3.77, 64 k 2.02 -> 2.83, 16 k 0.83 -> 0.89, but 4 k 215 -> 173 Mrays/s:
+  // 32 workgroups whose four waves wait for one grab instead of grabbing side by side.
+  uint32_t tuneWgPool = 2;
+  uint32_t tuneWgPoolMinRays = 16384;
   bool tuneChunkFixed = false; // RTAMD_CHUNK given: every batch uses exactly that chunk (otherwise small batches are cut finer, rt_trace.cpp ray_chunk_for)
   // traversal skeleton: 0 lane-per-ray (trace_loop.hip.h), 1 ray pool (trace_pool.hip.h), 2 by batch size: the pool kernel's
   // steady state is 14 % faster, its drain slower - it wins from ~2.5 M rays per launch on (env RTAMD_KERNEL=lane|pool|auto)

@@ -97,6 +97,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   p.octMax = dev->tuneOctMax;
   p.walkBatch = dev->tuneWalkBatch;
   p.inlineRay = 0u;
+  p.wgPool = dev->tuneWgPool == 2u ? (M >= dev->tuneWgPoolMinRays ? 1u : 0u) : dev->tuneWgPool; // small batches: see rt_objects.h
   p.octSteps = dev->tuneOctSteps;
   // waiting rays from which the child-parallel leaf phase runs: triangle leaves 16, grid cells 24 (measured optima), cBVH blobs
   // (quad form, 16 rays per pass) 16

@@ -31,6 +31,8 @@ struct LaunchParams
   uint32_t inlineRay;      // service kernel (DIRECT), a job of one ray: its org, tnear, dir, tfar lie in words 0..7 of the wave's exchange row 0, not only in P.rays
   uint32_t walkBatch;      // two-stage leaves: parked rays from which the walk stage runs (env RTAMD_WALK_BATCH)
   uint32_t octMax;         // lanes with node work up to which a wave runs the child-parallel node step (0 = never; env RTAMD_OCT_MAX)
+  uint32_t wgPool;         // 1: the four waves of a workgroup share the rays of a queue grab (RayPool in trace_loop.hip.h; a grab takes rayChunk per wave
+                           // of the workgroup), 0: every wave grabs for itself (env RTAMD_WG_POOL)
   uint32_t* queues;        // TRACE_QUEUES work-queue heads, zeroed on the stream before the launch
   // Filter-function re-trace (row f3): ray i skips the triangles (geomID, primID) listed in
   // exclPairs[exclOffsets[i] .. exclOffsets[i+1]) - the candidates a host filter callback rejected in earlier rounds.

@@ -7,8 +7,12 @@
 //    traffic stays far below what one counter word sustains (~70 ns per RMW and address) and the batch is balanced
 //    dynamically: random rays differ by more than 10x in traversal cost and a static assignment leaves most SIMDs
 //    idle in the tail.
-//  * A lane whose ray has finished is refilled from the wave's chunk (ballot + mbcnt rank), so finished rays do
-//    not park lanes ("wavefront ballot for active-ray compaction").
+//  * A lane whose ray has finished is refilled (ballot + mbcnt rank), so finished rays do not park lanes ("wavefront
+//    ballot for active-ray compaction").  The fresh rays come from a pool in LDS that the four waves of the workgroup
+//    share (RayPool below): one wave makes the global queue grab for all four, every wave claims what its idle lanes
+//    need with one LDS fetch-add, so the rays of a chunk go to whichever wave has free lanes.  Measured (1 M rays,
+//    profiles/r04_wg_pool_ab.txt): the VALU instruction count does not fall (43.3 -> 43.5 M) and a wave runs MORE
+//    iterations (13.2 -> 15.8), but the median wave ends at 74 instead of 96 us and the kernel takes 126 instead of 133 us.
 //  * if-if traversal step: every iteration each lane handles ONE event: an inner node, a leaf, or a pop.  Leaves
 //    are expensive and rare, so lanes that reached a leaf wait until leafBatch lanes want one (or no lane can do
 //    node work): the leaf code then runs with many lanes active instead of a handful.
@@ -44,8 +48,8 @@ namespace dev {
 #ifndef TRACE_PHASE_STAMPS
 #define TRACE_PHASE_STAMPS 0
 #endif
-// rays a wave takes from a queue per atomic and lanes that must wait at a leaf before the leaf code runs come from
-// LaunchParams::rayChunk / leafBatch (defaults 256 / 32, Device::tuneChunk / tuneLeafBatch)
+// rays per wave a queue grab brings in (a workgroup grabs four such shares at once into its pool) and lanes that must wait at a leaf
+// before the leaf code runs come from LaunchParams::rayChunk / leafBatch (defaults 256 / 32, Device::tuneChunk / tuneLeafBatch)
 static constexpr uint32_t QUEUE_STRIDE = TRACE_QUEUE_STRIDE; // queue heads live in separate 128-byte lines
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) // number of set bits of `mask` below this lane
@@ -83,9 +87,30 @@ template <int CTRL> __device__ __forceinline__ uint32_t dpp_u32(uint32_t v)
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
 }
 
-// DIRECT (service kernel, trace_service.hip.h): the rays [0, P.count) belong to THIS wavefront - no work queues, nothing to grab
+// ---- workgroup ray pool -------------------------------------------------------------------------------------------
+// The entries (ray indices, or positions in the survivor lists) a global queue grab brought in are shared by the four waves of the
+// workgroup: a wave that refills k idle lanes claims k entries of the pool, so a wave that still runs because of one deep ray keeps
+// filling its free lanes with the fresh rays its siblings would otherwise spend whole iterations on.  Only untraced rays are shared;
+// a ray that has started stays with its lane.  (LaunchParams::wgPool == 0: every wave uses a pool of its own, the hand-out of
+// before.)
+struct RayPool
+{
+  // `next` in the low half, `end` in the high half: entries [next, end) are left.  Claimed with ONE 64-bit LDS fetch-add of k on the
+  // low half (the claimer sees next and end of the same moment), published with ONE 64-bit LDS store by the wave that holds `state`.
+  // LDS atomics on one address are serialised, so a fetch-add either lands before a publication - then it found the old, empty word,
+  // took nothing, and the store overwrites what it added - or after it and sees the new word whole.  There is no third case.
+  // (next can run past end by the claims that found the pool empty: at most 64 per claim, far from carrying into `end`.)
+  unsigned long long word;
+  uint32_t state; // POOL_IDLE / POOL_GRABBING (one wave is at the global queues: compare-and-swap IDLE -> GRABBING) / POOL_EXHAUSTED (no
+                  // queue is live for this pool's stagger class any more: final, and set only while the pool is empty)
+  uint32_t qCur;  // bits 0..7: queue the next global grab starts at, bits 8..: the pool's stagger class (percent of a queue after which the
+                  // pool treats it as closed); read and written only by the wave that holds `state`
+};
+enum : uint32_t { POOL_IDLE = 0u, POOL_GRABBING = 1u, POOL_EXHAUSTED = 2u };
+
+// DIRECT (service kernel, trace_service.hip.h): the rays [0, P.count) belong to THIS wavefront - no work queues, no pool, nothing to grab
 template <typename Leaf, bool ROBUST, bool OCCLUDED, bool COUNT, bool VEC, bool DIRECT = false>
-__device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsStack)[TRACE_BLOCK], float (*octX)[OCT_WORDS])
+__device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsStack)[TRACE_BLOCK], float (*octX)[OCT_WORDS], RayPool* pools = nullptr)
 {
   const uint32_t tid = threadIdx.x;
   const uint32_t gthread = blockIdx.x * TRACE_BLOCK + tid;
@@ -113,8 +138,7 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
     const uint32_t lo = min(q * perQ, P.count);
     return min(lo + perQ, P.count) - lo;
   };
-  uint32_t qCur = (blockIdx.x * (TRACE_BLOCK / 64) + (tid >> 6)) & (uint32_t)(TRACE_QUEUES - 1); // wave-uniform
-  uint32_t poolNext = 0, poolEnd = DIRECT ? P.count : 0u; // wave-uniform: rays [poolNext, poolEnd) belong to this wave
+  uint32_t poolNext = 0, poolEnd = DIRECT ? P.count : 0u; // DIRECT only, wave-uniform: rays [poolNext, poolEnd) belong to this wave
   // Staggered exhaustion: a quarter of the waves treats a queue as closed once 85 % of it are handed out, another quarter
   // at 92 %, the rest drains it.  The waves then enter their drain (few deep rays, few active lanes) at different times
   // instead of all at once; the SIMD slots of the early leavers are free for the other batches in flight.  Measured on
@@ -133,8 +157,22 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
 #endif
   // (the third class only in the kernels that run four workgroups per CU - grid cells, cBVH quad form: one 256-ray chunk per wave; the triangle
   // kernels, two workgroups per CU and two chunks per wave, lose with it: alone 0.102 -> 0.107 ms)
-  const uint32_t stag = (wIdx & 3u) == 1u ? TRACE_STAG_A : ((wIdx & 3u) == 3u ? TRACE_STAG_B : (((wIdx & 3u) == 2u && Leaf::OCTET_ONLY) ? TRACE_STAG_C : 100u));
-  bool exhausted = P.accel.root == REF_EMPTY;
+  // One global grab serves a whole pool, so the class (and the home queue) belongs to the pool: to the workgroup with the workgroup
+  // pool, to the wave without it.  The levels and every figure quoted above were measured with per-WAVE classes; with the workgroup
+  // pool a whole workgroup leaves early together, and the levels have NOT been re-swept for that population (85/92/100 and no
+  // staggering are untried) - they are carried over, not tuned.  Measured with them: profiles/r04_wg_pool_ab.txt.
+  const uint32_t pIdx = (!DIRECT && P.wgPool) ? blockIdx.x : wIdx;
+  const uint32_t stag = (pIdx & 3u) == 1u ? TRACE_STAG_A : ((pIdx & 3u) == 3u ? TRACE_STAG_B : (((pIdx & 3u) == 2u && Leaf::OCTET_ONLY) ? TRACE_STAG_C : 100u));
+  bool exhausted = P.accel.root == REF_EMPTY; // this wave will get no more rays (with a pool: the pool is empty and POOL_EXHAUSTED)
+  RayPool* const pool = DIRECT ? nullptr : pools + (P.wgPool ? 0u : __builtin_amdgcn_readfirstlane(tid >> 6)); // wave-uniform
+  if constexpr (!DIRECT) {
+    if (laneId == 0u && (!P.wgPool || tid == 0u)) {
+      pool->word = 0ull;
+      pool->state = exhausted ? POOL_EXHAUSTED : POOL_IDLE;
+      pool->qCur = (pIdx & (uint32_t)(TRACE_QUEUES - 1)) | (stag << 8);
+    }
+    __syncthreads(); // the only workgroup barrier: the waves leave the loop below at different times
+  }
 
   WorkCounters wc;
   RayState r;
@@ -198,45 +236,102 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
     // refilling a handful of lanes costs as many instructions as refilling all 64: wait until refillBatch lanes are
     // idle (or until nothing else can run)
     if (idleMask != 0ull && !exhausted && (__popcll(idleMask) >= (int)P.refillBatch || idleMask == ~0ull)) {
-      if (DIRECT && poolNext == poolEnd) exhausted = true;
-      else if (poolNext == poolEnd) { // take a new chunk (one lane does the atomic, the result is wave-uniform)
-        for (;;) {
-          const uint32_t qLo = qCur * perQ; // first entry of the queue (ray index, or position in the survivor lists)
-          const uint32_t qLen = queue_len(qCur);
-          uint32_t base = 0xFFFFFFFFu;
-          bool open = true;
-          if (stag != 100u) { // this wave treats the queue as closed once `stag` percent of it are handed out
-            uint32_t pre = 0;
-            if (laneId == 0u) pre = __hip_atomic_load(&queues[qCur * QUEUE_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            pre = __builtin_amdgcn_readfirstlane(pre);
-            open = pre < (uint32_t)((uint64_t)qLen * stag / 100u);
+      uint32_t first = 0, take = 0; // wave-uniform: this refill hands out the entries [first, first + take), one per idle lane
+      if constexpr (DIRECT) {
+        if (poolNext == poolEnd) exhausted = true;
+        else {
+          first = poolNext;
+          take = min((uint32_t)__popcll(idleMask), poolEnd - poolNext);
+          poolNext += take;
+        }
+      } else {
+        // (never more than one wave's share of a grab at once: a batch cut into 32-ray shares keeps spreading over four waves per workgroup)
+        const uint32_t want = min((uint32_t)__popcll(idleMask), P.rayChunk);
+        // claim `want` entries of the pool (one lane does the atomic, the result is wave-uniform)
+        unsigned long long w = 0ull;
+        if (laneId == 0u) w = __hip_atomic_fetch_add(&pool->word, (unsigned long long)want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        uint32_t cNext = __builtin_amdgcn_readfirstlane((uint32_t)w);
+        const uint32_t cEnd = __builtin_amdgcn_readfirstlane((uint32_t)(w >> 32));
+        if (cNext < cEnd) { // the comparison decides, then the difference is formed from an opaque copy: not `min(want, cEnd - cNext)` folded into a no-wrap subtraction
+          asm volatile("" : "+s"(cNext));
+          first = cNext;
+          take = min(want, cEnd - cNext);
+        } else {
+          // the pool is empty: one wave goes to the global queues, the others do not wait for it
+          uint32_t s = POOL_IDLE;
+          if (laneId == 0u) __hip_atomic_compare_exchange_strong(&pool->state, &s, (uint32_t)POOL_GRABBING, __ATOMIC_ACQUIRE, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+          s = __builtin_amdgcn_readfirstlane(s);
+          // POOL_GRABBING: a sibling is at the queues - this wave carries on with the rays it has and asks again in a later iteration
+          if (s == POOL_EXHAUSTED) exhausted = true; // empty, nobody grabbing, nothing left to grab
+          else if (s == POOL_IDLE) {
+            // This wave holds `state`.  A sibling may have refilled the pool between the claim above and the swap: look again - from
+            // here on an empty pool stays empty until this wave publishes, because only the holder of `state` writes new entries.
+            if (laneId == 0u) w = __hip_atomic_load(&pool->word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (__builtin_amdgcn_readfirstlane((uint32_t)w) < __builtin_amdgcn_readfirstlane((uint32_t)(w >> 32))) {
+              // refilled meanwhile: hand the state back, claim in the next iteration
+              if (laneId == 0u) __hip_atomic_store(&pool->state, (uint32_t)POOL_IDLE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else {
+              uint32_t qs = 0;
+              if (laneId == 0u) qs = pool->qCur;
+              qs = __builtin_amdgcn_readfirstlane(qs);
+              uint32_t qCur = qs & 0xffu;
+              const uint32_t poolStag = qs >> 8;
+              // entries per global grab: P.rayChunk is the share of one wave
+              const uint32_t grabChunk = P.wgPool ? P.rayChunk * (uint32_t)(TRACE_BLOCK / 64) : P.rayChunk;
+              uint32_t gNext = 0, gEnd = 0; // the grabbed chunk
+              for (;;) {
+                const uint32_t qLo = qCur * perQ; // first entry of the queue (ray index, or position in the survivor lists)
+                const uint32_t qLen = queue_len(qCur);
+                uint32_t base = 0xFFFFFFFFu;
+                bool open = true;
+                if (poolStag != 100u) { // this pool treats the queue as closed once `poolStag` percent of it are handed out
+                  uint32_t pre = 0;
+                  if (laneId == 0u) pre = __hip_atomic_load(&queues[qCur * QUEUE_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                  pre = __builtin_amdgcn_readfirstlane(pre);
+                  open = pre < (uint32_t)((uint64_t)qLen * poolStag / 100u);
+                }
+                if (open) {
+                  if (laneId == 0u) base = atomicAdd(&queues[qCur * QUEUE_STRIDE], grabChunk);
+                  base = __builtin_amdgcn_readfirstlane(base);
+                }
+                if (base < qLen) {
+                  gNext = qLo + base;
+                  gEnd = min(gNext + grabChunk, qLo + qLen);
+                  break;
+                }
+                // drained: lane l reads head l (heads only grow, so a stale value can only under-report "drained"), the
+                // ballot marks the queues that still have rays, take the next one cyclically after qCur
+                const uint32_t head = __hip_atomic_load(&queues[laneId * QUEUE_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const uint32_t myLen = queue_len(laneId);
+                const uint64_t live = __ballot(laneId < (uint32_t)TRACE_QUEUES && head < (uint32_t)((uint64_t)myLen * poolStag / 100u));
+                if (live == 0ull) break;
+                const uint64_t rot = (live >> qCur) | (qCur ? (live << (64u - qCur)) : 0ull); // bit k = queue (qCur+k)&63
+                qCur = (qCur + (uint32_t)__builtin_ctzll(rot)) & (uint32_t)(TRACE_QUEUES - 1);
+              }
+              if (gNext != gEnd) { // this wave's share first, the rest to the pool: the new word, THEN the state (release)
+                first = gNext;
+                take = min(want, gEnd - gNext);
+                if (laneId == 0u) {
+                  pool->qCur = qCur | (poolStag << 8);
+                  __hip_atomic_store(&pool->word, ((unsigned long long)gEnd << 32) | (unsigned long long)(gNext + take), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                  __hip_atomic_store(&pool->state, (uint32_t)POOL_IDLE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+              } else {
+                if (laneId == 0u) __hip_atomic_store(&pool->state, (uint32_t)POOL_EXHAUSTED, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                exhausted = true;
+              }
+            }
           }
-          if (open) {
-            if (laneId == 0u) base = atomicAdd(&queues[qCur * QUEUE_STRIDE], P.rayChunk);
-            base = __builtin_amdgcn_readfirstlane(base);
-          }
-          if (base < qLen) {
-            if (COUNT) rtLastGrab = __builtin_amdgcn_s_memrealtime();
-#ifdef TRACE_TIMELINE
-            if (!COUNT && P.timeline) { tlGrab = __builtin_amdgcn_s_memrealtime(); if (!tlFirst) tlFirst = tlGrab; tlRays += min(P.rayChunk, qLen - base); }
-#endif
-            poolNext = qLo + base;
-            poolEnd = min(poolNext + P.rayChunk, qLo + qLen);
-            break;
-          }
-          // drained: lane l reads head l (heads only grow, so a stale value can only under-report "drained"), the
-          // ballot marks the queues that still have rays, take the next one cyclically after qCur
-          const uint32_t head = __hip_atomic_load(&queues[laneId * QUEUE_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const uint32_t myLen = queue_len(laneId);
-          const uint64_t live = __ballot(laneId < (uint32_t)TRACE_QUEUES && head < (uint32_t)((uint64_t)myLen * stag / 100u));
-          if (live == 0ull) { exhausted = true; break; }
-          const uint64_t rot = (live >> qCur) | (qCur ? (live << (64u - qCur)) : 0ull); // bit k = queue (qCur+k)&63
-          qCur = (qCur + (uint32_t)__builtin_ctzll(rot)) & (uint32_t)(TRACE_QUEUES - 1);
         }
       }
-      if (poolNext != poolEnd) {
-        const uint32_t mine = poolNext + lane_rank(idleMask);
-        if (!(st & ST_ACTIVE) && mine < poolEnd) {
+      if (take != 0u) {
+        if (COUNT) rtLastGrab = __builtin_amdgcn_s_memrealtime();
+#ifdef TRACE_TIMELINE
+        if (!COUNT && P.timeline) { tlGrab = __builtin_amdgcn_s_memrealtime(); if (!tlFirst) tlFirst = tlGrab; tlRays += take; }
+#endif
+        const uint32_t rank = lane_rank(idleMask);
+        const uint32_t mine = first + rank;
+        if (!(st & ST_ACTIVE) && rank < take) {
           rayIdx = survivors ? survivors[mine] : mine;
           const char* rp = (const char*)P.rays + (size_t)rayIdx * P.stride;
           if (DIRECT && P.inlineRay) { // (service kernel: the ray came with the polled slot header - no second read of host memory)
@@ -259,7 +354,6 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
             st = ST_ACTIVE;
           }
         }
-        poolNext = min(poolNext + (uint32_t)__popcll(idleMask), poolEnd);
       }
     }
     stamp(tFetch);
@@ -269,6 +363,7 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
     }
     if (__ballot((st & ST_ACTIVE) != 0u) == 0ull) {
       if (exhausted) break;
+      if (!DIRECT) __builtin_amdgcn_s_sleep(1); // nothing to do while a sibling is at the global queues: do not hammer the pool word meanwhile
       continue;
     }
 
@@ -770,8 +865,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, COUNT ? TRACE_COUNT_MIN_WAVES(Leaf) : 
 {
   __shared__ uint2 ldsStack[TRACE_LDS_STACK + 1][TRACE_BLOCK]; // + one scratch row for the branch-free pushes
   __shared__ __attribute__((aligned(16))) float octX[TRACE_BLOCK / 64][OCT_ROWS][OCT_WORDS]; // octet node step: per-wave exchange rows
+  __shared__ __attribute__((aligned(8))) RayPool pools[TRACE_BLOCK / 64]; // [0]: the workgroup's pool; one per wave with LaunchParams::wgPool == 0
   Leaf::prepare();
-  trace_body<Leaf, ROBUST, OCCLUDED, COUNT, VEC>(P, ldsStack, octX[threadIdx.x >> 6]);
+  trace_body<Leaf, ROBUST, OCCLUDED, COUNT, VEC>(P, ldsStack, octX[threadIdx.x >> 6], pools);
 }
 
 template <typename Leaf, bool ROBUST, bool OCCLUDED, bool COUNT>

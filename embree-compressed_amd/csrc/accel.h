@@ -7,7 +7,8 @@
 //                            or QuadRecord[] (64-byte quad records, leaf-contiguous) for quad geometry,
 //                            or TriMBRecord[] (96-byte motion-blur triangle records, leaf-contiguous) for triangle meshes with time steps,
 //                            or QuadMBRecord[] (128-byte motion-blur quad records, leaf-contiguous) for quad meshes with time steps,
-//                            or InstanceRecord[] (64-byte instance records, one per top-level leaf) for instances
+//                            or InstanceRecord[] (64-byte instance records, one per top-level leaf) for instances, followed in
+//                            the kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER by the instanced scenes' QuadRecord[]
 // The reference keeps the same information behind 64-bit tagged pointers (kernels/bvh/bvh.h:150-396,
 // AlignedNode :433-594, QuantizedNode :1150-1324, Triangle4v kernels/geometry/trianglev.h:24-162).
 #pragma once
@@ -144,17 +145,31 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // accel's own `nodes` / `prims`; `root` is the rebased root reference of this instance's scene.
 // world2local = inverse(local2world) as the columns vx, vy, vz, p of an AffineSpace3f: a ray enters the instance as
 // org' = xfmPoint(world2local, org), dir' = xfmVector(world2local, dir) (instance_intersector.cpp:51-56); t is common to both spaces.
+//
+// Kinds ACCEL_INST_TRI_*: every instanced scene holds triangles only; the arrays are as above and `pad` is zero.
+// Kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER: at least one instanced scene has a quad tree.  Per distinct instanced scene (stored once,
+// however many instances share it), in the order of first use:
+//   nodes : top-level tree | scene 0: triangle nodes, quad nodes | scene 1: triangle nodes, quad nodes | ...   (child indices rebased)
+//   prims : scene 0's TriRecords | scene 1's | ...                                                          (triangle leaves rebased)
+//   blobs : the N InstanceRecords | scene 0's QuadRecords | scene 1's | ...
+// A quad leaf reference is rebased by N + the scene's quad base, so that the kernel indexes `blobs` as ONE array of 64-byte records
+// (sizeof(InstanceRecord) == sizeof(QuadRecord)); the rebased first record must stay below 2^26.  `root` is REF_EMPTY for a scene
+// without triangles, pad[0] the rebased quad root, REF_EMPTY for a scene without quads.
 struct alignas(16) InstanceRecord
 {
   float world2local[12]; // vx.xyz, vy.xyz, vz.xyz, p.xyz
   uint32_t geomID;       // of the instance in the top scene: the hit's instID (instance_intersector.cpp:57)
   uint32_t root;         // rebased root reference of the instanced scene's triangle tree
-  uint32_t pad[2];
+  uint32_t pad[2];       // pad[0]: rebased root reference of the instanced scene's quad tree (kinds ACCEL_INST_PLUECKER / _MOELLER only)
 };
 static_assert(sizeof(InstanceRecord) == 64, "InstanceRecord must be 64 bytes");
 // Marker on the traversal stack of the instance kernel (trace_instance.hip): popping it leaves the instance.  A leaf-flagged reference with
 // count 0, which make_tri_leaf never produces (counts are 1..28), and not REF_EMPTY.
 static const uint32_t REF_INST_EXIT = 0x80000000u;
+// Second marker of the kernel's QUADS form: stacked above the exit marker when the ray enters an instance whose scene has triangles
+// and quads, with the quad root in the entry's distance word; popping it continues in the quad tree.  Leaf-flagged with count 0 too.
+static const uint32_t REF_INST_QUADS = 0x80000001u;
+static_assert(sizeof(InstanceRecord) == sizeof(QuadRecord), "the instance kernel indexes InstanceRecords and QuadRecords as one array");
 
 // ---- eager subdivision leaf: one 3x3-vertex cell (2x2 quads = 8 triangles), 160 bytes = 10 x dwordx4 ------
 // Replaces the inner leaves of GridSOA (kernels/geometry/grid_soa.h:267-286, :85-90): the reference stores whole
@@ -241,15 +256,18 @@ enum AccelKind : uint32_t
   ACCEL_QUADMB_PLUECKER = 12, // quad_accel_mb=default with RTC_SCENE_FLAG_ROBUST (scene.cpp:332-367): interpolated quad + Pluecker, robust traversal
   ACCEL_QUADMB_MOELLER = 13,  // quad_accel_mb=default / bvh8.quad4imb / bvh4.quad4imb: interpolated quad + Moeller, fast traversal
   ACCEL_INST_TRI_PLUECKER = 14, // instances of scenes whose triangle accel is ACCEL_TRI_PLUECKER: robust traversal on both levels
-  ACCEL_INST_TRI_MOELLER = 15   // instances of scenes whose triangle accel is ACCEL_TRI_MOELLER: fast traversal on both levels
+  ACCEL_INST_TRI_MOELLER = 15,  // instances of scenes whose triangle accel is ACCEL_TRI_MOELLER: fast traversal on both levels
+  ACCEL_INST_PLUECKER = 16,     // instances of scenes with triangles (Pluecker) and / or quads (Pluecker): robust traversal on both levels
+  ACCEL_INST_MOELLER = 17       // instances of scenes with triangles (Moeller) and / or quads (Moeller): fast traversal on both levels
 };
+inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INST_MOELLER; } // traced by trace_instance.hip
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
 {
   const QNode8* nodes;
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[]
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[])
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind

@@ -40,6 +40,7 @@ void Device::parse(const std::string& cfg)
     else if (key == "quad_accel") { quad_accel = val; quadAccelNamed = true; }
     else if (key == "tri_accel_mb") tri_accel_mb = val;
     else if (key == "quad_accel_mb") { quad_accel_mb = val; quadAccelMBNamed = true; }
+    else if (key == "inst_accel") { inst_accel = val; instAccelNamed = true; }
     else if (key == "verbose") verbose = atoi(val.c_str());
     else if (key == "gpu" || key == "device") { gpu = (val == "none") ? -1 : atoi(val.c_str()); gpuList.clear(); }
     else if (key == "gpus") {

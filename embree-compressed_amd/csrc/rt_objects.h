@@ -30,6 +30,8 @@ struct Device : RefCounted
   std::string quad_accel = "default";
   std::string tri_accel_mb = "default"; // triangle meshes with more than one time step
   std::string quad_accel_mb = "default"; // quad meshes with more than one time step
+  std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel raises for any other at commit)
+  bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
   bool quadAccelNamed = false; // "quad_accel=" given (a host-only device takes quad geometry only then, quads_enabled())
   int verbose = 0;
@@ -210,6 +212,9 @@ struct Device : RefCounted
   // Quad meshes with time steps follow the same rule with their own key: a host-only device whose config does not name quad_accel_mb=
   // raises INVALID_OPERATION at commit for them, as before the motion-blur quad accel existed.
   bool quads_mb_enabled() const { return gpu >= 0 || quadAccelMBNamed; }
+  // Quad meshes inside an instanced scene, the same rule with the key inst_accel=: a host-only device without it refuses them at the top
+  // scene's commit, as before the instance accel took quads.
+  bool inst_quads_enabled() const { return gpu >= 0 || instAccelNamed; }
   bool tuneBlocksAuto = true; // no RTAMD_BLOCKS_PER_CU given: 2 workgroups per CU, 1 when >= 2 batches run on other streams
   void memoryMonitor(ssize_t bytes, bool post);
 };
@@ -356,7 +361,7 @@ struct Scene : RefCounted
   Accel quadAccel;   // quads with one time step (QuadRecord[] in `blobs`); traced after the triangles, before the motion-blur quads
   Accel quadMBAccel; // quads with several time steps (QuadMBRecord[] in `blobs`); traced after the static quads, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
-  Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle trees behind the top-level tree); traced last (scene.cpp:661-665)
+  Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle and quad trees behind the top-level tree); traced last (scene.cpp:661-665)
   // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / INST index whatever a path keeps per accel
   enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, INST = 5, NUM_ACCELS = 6 };
   std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &instAccel}; }

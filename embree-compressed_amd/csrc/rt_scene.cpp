@@ -560,16 +560,26 @@ static V3 xfm_point(const float* m, V3 q)
 
 // Instances (RTC_GEOMETRY_TYPE_INSTANCE, one time step, one level): a top-level BVH8 over the instances' world bounds - xfmBounds of
 // the instanced scene's bounds, its eight transformed corners (instance_intersector.cpp:24-39, affinespace.h:114-126) - with ONE
-// instance per leaf, followed in the same arrays by the triangle tree and records of every distinct instanced scene, rebased.  The
-// instanced scenes were committed before; what this commit sees of them is their committed triangle accel.
+// instance per leaf, followed in the same arrays by the trees and records of every distinct instanced scene, rebased.  The instanced
+// scenes were committed before; what this commit sees of them is their committed triangle and quad accels (their `bounds` cover both:
+// build_mesh_bvh8 extends them per accel).
+// As long as no instanced scene has a traceable quad accel the result is the triangle-only accel (kinds ACCEL_INST_TRI_*: triangle
+// trees behind the top-level tree, TriRecords, InstanceRecords, `pad` zero); otherwise it is the layout of accel.h InstanceRecord
+// (kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER).  A host-only device takes quads in an instanced scene only when its config names
+// inst_accel= (Device::inst_quads_enabled), as it takes quad meshes at all only with quad_accel=.
 static void build_instance_accel(Scene* s)
 {
   Accel& A = s->instAccel;
   A.clear();
+  if (s->device->inst_accel != "default") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown instance acceleration structure " + s->device->inst_accel);
+  const bool quadsOk = s->device->inst_quads_enabled();
+  const char* const onlyTris = "an instanced scene may hold static triangle meshes only (no quads, time steps, subdivision meshes or instances)";
+  const char* const onlyStatic = "an instanced scene may hold static triangle and quad meshes only (no time steps, subdivision meshes or instances)";
+  const char* const only = quadsOk ? onlyStatic : onlyTris;
   struct Src { unsigned geomID; Scene* scene; };
   std::vector<Src> src;
   std::vector<BuildPrim> bp;
-  uint32_t kind = ACCEL_NONE;
+  bool haveKind = false, pluecker = false, anyQuads = false;
   for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
     Geometry* g = s->geometries[gid];
     if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_INSTANCE) continue;
@@ -579,18 +589,28 @@ static void build_instance_accel(Scene* s)
     if (o->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instanced scene got not committed");
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
-      if (og->type != RTC_GEOMETRY_TYPE_TRIANGLE || og->timeSteps != 1)
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene may hold static triangle meshes only (no quads, time steps, subdivision meshes or instances)");
+      const bool mesh = og->type == RTC_GEOMETRY_TYPE_TRIANGLE || (quadsOk && og->type == RTC_GEOMETRY_TYPE_QUAD);
+      if (!mesh || og->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
       if (og->intersectFilter || og->occludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
     }
     for (const Accel* oa : o->accels())
-      if (oa != &o->triAccel && oa->kind != ACCEL_NONE)
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene may hold static triangle meshes only (no quads, time steps, subdivision meshes or instances)");
+      if (oa != &o->triAccel && !(quadsOk && oa == &o->quadAccel) && oa->kind != ACCEL_NONE) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
     if (o->triIntersectFilter || o->triOccludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
-    if (!o->triAccel.traceable()) continue; // empty scene: nothing to hit
-    if (kind != ACCEL_NONE && kind != o->triAccel.kind)
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
-    kind = o->triAccel.kind;
+    const bool tris = o->triAccel.traceable(), quads = o->quadAccel.traceable();
+    if (!tris && !quads) continue; // empty scene: nothing to hit
+    // the kernel runs ONE arithmetic on both levels and in both leaves: every accel below this scene is Pluecker / robust, or every one
+    // Moeller / fast
+    if (tris && quads && (o->triAccel.kind == ACCEL_TRI_PLUECKER) != (o->quadAccel.kind == ACCEL_QUAD_PLUECKER))
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "the triangle and quad accels of an instanced scene disagree in kind (Pluecker / robust triangles beside Moeller / fast quads, "
+                                            "as a robust scene under quad_accel=bvh8.quad4v builds them): instances need one arithmetic");
+    const bool pl = tris ? o->triAccel.kind == ACCEL_TRI_PLUECKER : o->quadAccel.kind == ACCEL_QUAD_PLUECKER;
+    if (haveKind && pl != pluecker) {
+      if (!anyQuads && !quads) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in accel kind (Pluecker / robust and Moeller / fast): instances need one arithmetic");
+    }
+    haveKind = true;
+    pluecker = pl;
+    anyQuads |= quads;
     BuildPrim p;
     const V3 c[2] = {o->bounds.lo, o->bounds.hi};
     for (int i = 0; i < 8; i++) p.box.extend(xfm_point(g->local2world, V3(c[i >> 2].x, c[(i >> 1) & 1].y, c[i & 1].z)));
@@ -620,27 +640,48 @@ static void build_instance_accel(Scene* s)
   A.root = r.root;
   A.leafCount = r.leafCount;
 
-  // the distinct instanced scenes' trees behind it, rebased
-  std::map<Scene*, uint32_t> rootOf;
+  // the distinct instanced scenes' trees behind it, rebased: the triangle tree, then (anyQuads) the quad tree
+  struct Roots { uint32_t tri, quad; };
+  std::map<Scene*, Roots> rootsOf;
+  std::vector<QuadRecord> quadRecs;
   uint32_t deepest = 0;
-  for (const Src& sr : src) {
-    if (rootOf.count(sr.scene)) continue;
-    const Accel& O = sr.scene->triAccel;
-    const size_t nodeBase = A.nodes.size(), primBase = A.prims.size();
-    if (primBase + O.prims.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced triangles for the 26-bit leaf reference");
+  // copies the nodes of O behind A.nodes; leaf references move by leafBase, which keeps the first record in bits 0..25 (guarded by the caller)
+  auto append_tree = [&](const Accel& O, size_t leafBase) -> uint32_t {
+    if (!O.traceable()) return REF_EMPTY;
+    const size_t nodeBase = A.nodes.size();
     if (nodeBase + O.nodes.size() >= (size_t)REF_LEAF) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced nodes for the 31-bit node reference");
     auto rebase = [&](uint32_t ref) -> uint32_t {
       if (ref == REF_EMPTY) return ref;
-      if (ref & REF_LEAF) return ref + (uint32_t)primBase; // first record in bits 0..25, guarded above
+      if (ref & REF_LEAF) return ref + (uint32_t)leafBase;
       return ref + (uint32_t)nodeBase;
     };
     for (QNode8 n : O.nodes) {
       for (uint32_t& c : n.child) c = rebase(c);
       A.nodes.push_back(n);
     }
-    A.prims.insert(A.prims.end(), O.prims.begin(), O.prims.end());
-    rootOf[sr.scene] = rebase(O.root);
     deepest = std::max(deepest, O.maxDepth);
+    return rebase(O.root);
+  };
+  for (const Src& sr : src) {
+    if (rootsOf.count(sr.scene)) continue;
+    Roots roots;
+    const Accel& O = sr.scene->triAccel;
+    const size_t primBase = A.prims.size();
+    if (primBase + O.prims.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced triangles for the 26-bit leaf reference");
+    roots.tri = append_tree(O, primBase);
+    if (O.traceable()) A.prims.insert(A.prims.end(), O.prims.begin(), O.prims.end());
+    roots.quad = REF_EMPTY;
+    const Accel& Q = sr.scene->quadAccel;
+    if (anyQuads && Q.traceable()) {
+      // quad leaves index `blobs` as one array of 64-byte records: the instance records, then every scene's quads
+      const size_t nq = Q.blobs.size() / sizeof(QuadRecord), quadBase = recs.size() + quadRecs.size();
+      if (quadBase + nq >= ((size_t)1 << TRI_START_BITS))
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances and instanced quads for the 26-bit leaf reference (quad records follow the instance records in one array)");
+      roots.quad = append_tree(Q, quadBase);
+      const QuadRecord* q = (const QuadRecord*)Q.blobs.data();
+      quadRecs.insert(quadRecs.end(), q, q + nq);
+    }
+    rootsOf[sr.scene] = roots;
   }
   for (size_t i = 0; i < order.size(); i++) {
     const Src& sr = src[order[i]];
@@ -648,14 +689,21 @@ static void build_instance_accel(Scene* s)
     memset(&rec, 0, sizeof(rec));
     if (!invert_affine(s->geometries[sr.geomID]->local2world, rec.world2local)) memset(rec.world2local, 0, sizeof(rec.world2local)); // singular: never hit
     rec.geomID = sr.geomID;
-    rec.root = rootOf[sr.scene];
+    rec.root = rootsOf[sr.scene].tri;
+    if (anyQuads) rec.pad[0] = rootsOf[sr.scene].quad;
   }
-  A.kind = kind == ACCEL_TRI_PLUECKER ? ACCEL_INST_TRI_PLUECKER : ACCEL_INST_TRI_MOELLER;
-  A.robust = kind == ACCEL_TRI_PLUECKER ? 1 : 0;
-  A.maxDepth = r.maxDepth + 1u + deepest; // top-level levels, the exit marker, the deepest instanced tree (launch_on's stack bound)
+  if (anyQuads) A.kind = pluecker ? ACCEL_INST_PLUECKER : ACCEL_INST_MOELLER;
+  else A.kind = pluecker ? ACCEL_INST_TRI_PLUECKER : ACCEL_INST_TRI_MOELLER;
+  A.robust = pluecker ? 1 : 0;
+  // launch_on's stack bound counts 7 entries per level.  Triangle-only: the top-level levels, the exit marker, the deepest instanced
+  // tree.  With quads a ray in a triangle tree has the marker of the pending quad tree stacked as well - one more entry, counted as a
+  // level - and the deepest tree is the deeper of all triangle and quad trees (the two trees of a scene are never stacked together:
+  // the quad marker is popped only when the triangle tree's entries are gone).
+  A.maxDepth = r.maxDepth + 1u + (anyQuads ? 1u : 0u) + deepest;
   A.blobStride = sizeof(InstanceRecord);
-  A.blobs.resize(recs.size() * sizeof(InstanceRecord));
-  memcpy(A.blobs.data(), recs.data(), A.blobs.size());
+  A.blobs.resize((recs.size() + quadRecs.size()) * sizeof(InstanceRecord));
+  memcpy(A.blobs.data(), recs.data(), recs.size() * sizeof(InstanceRecord));
+  if (!quadRecs.empty()) memcpy(A.blobs.data() + recs.size() * sizeof(InstanceRecord), quadRecs.data(), quadRecs.size() * sizeof(QuadRecord));
 }
 
 void Scene::commit()
@@ -707,8 +755,9 @@ void Scene::commit()
               quadMBAccel.nodes.size() * sizeof(QNode8), quadMBAccel.blobs.size() / sizeof(QuadMBRecord), quadMBAccel.blobs.size(), quadMBAccel.maxDepth);
   }
   if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
-    fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, depth %u\n", instAccel.kind, instAccel.nodes.size(),
-            instAccel.nodes.size() * sizeof(QNode8), instAccel.blobs.size() / sizeof(InstanceRecord), instAccel.prims.size(), instAccel.maxDepth);
+    fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, %zu instanced quads, depth %u\n", instAccel.kind,
+            instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),
+            instAccel.blobs.size() / sizeof(InstanceRecord) - instAccel.leafCount, instAccel.maxDepth);
   modified = false;
 }
 

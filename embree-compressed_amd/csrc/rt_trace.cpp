@@ -70,7 +70,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   p.poolKernel = dev->tunePoolKernel == 2u ? (poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel;
   if (A.kind == ACCEL_TRIMB_PLUECKER || A.kind == ACCEL_TRIMB_MOELLER || A.kind == ACCEL_QUADMB_PLUECKER || A.kind == ACCEL_QUADMB_MOELLER)
     p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip)
-  const bool instKernel = A.kind == ACCEL_INST_TRI_PLUECKER || A.kind == ACCEL_INST_TRI_MOELLER;
+  const bool instKernel = is_instance_kind(A.kind);
   if (instKernel) p.poolKernel = 0u; // the two-level kernel is a lane-per-ray kernel of its own (trace_instance.hip): no pool form, no root cull pre-pass
   // worst-case stack: 7 siblings per level plus the entry being expanded.  The overflow area is sized for it, so a push
   // can only be dropped if the tree is deeper than the builder reported; the kernels then raise `overflow` (below).

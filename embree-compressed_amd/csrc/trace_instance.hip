@@ -18,7 +18,19 @@
 // columns and the `overflow` word, TravRay, the QNode8 decode and slab test with the reference's child order, pluecker / moeller /
 // commit_hit, load_ray / store_hit.  No octet form, no ray-pool form, no root cull pre-pass, no service kernel, no instrumented twin
 // (rt_trace.cpp launch_on, rt_service.cpp; counted batches on scenes with instances are refused).
+//
+// QUADS (accel kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER): an instanced scene may hold a quad tree next to, or instead of, its
+// triangle tree.  Inside an instance the local ray traverses the triangle tree completely and then the quad tree, against the tfar the
+// triangles left (the instanced scene's AccelN, scene.cpp:650-654) - so a quad at a bit-identical t replaces the triangle:
+//   2'. entering an instance whose record has a quad root stacks a second marker (REF_INST_QUADS, the quad root in the entry's
+//       distance word) above the exit marker and continues at the triangle root; without a triangle tree it starts in the quad tree;
+//   3'. popping that marker sets the lane's ST_QUADS bit and continues at the quad root; with the bit set a leaf is the block loop of
+//       QuadLeaf::intersect (trace_quad.hip) restated over pluecker_quad / moeller_quad: 8 candidates per block of 4 records (A =
+//       (v0, v1, v3) in lanes 0-3, B = (v2, v1, v3) in lanes 4-7), all against the tfar at block entry, one minimum, the lowest lane
+//       wins ties, a later block replaces an equal t.  The QuadRecords lie behind the InstanceRecords in `blobs`, one 64-byte array;
+//   4'. the exit marker clears the bit.
 #include "trace_leaf.hip.h"
+#include "trace_quad_tests.hip.h"
 
 namespace rtamd {
 namespace dev {
@@ -34,11 +46,26 @@ namespace dev {
 #ifndef TRACE_INST_FETCH
 #define TRACE_INST_FETCH 2
 #endif
+// The QUADS instantiations carry the quad block loop (a record is four dwordx4, a block has 8 candidates) next to the triangle loop.
+// Three of the four compile without scratch at 4 waves per SIMD; closest-hit Pluecker does not (76 bytes of scratch with two QuadRecords
+// per round trip, 36 with one), as the static quad lane kernel's does not (trace_quad.hip): it alone is asked for 3 waves (<= 168 VGPRs).
+#ifndef TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST
+#define TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST 3
+#endif
+// QuadRecords requested per memory round trip inside a block of 4 (1 or 2)
+#ifndef TRACE_INST_QUAD_FETCH
+#define TRACE_INST_QUAD_FETCH 2
+#endif
+constexpr int inst_min_waves(bool pluecker, bool occluded, bool quads)
+{
+  return quads && pluecker && !occluded ? TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_MIN_WAVES;
+}
 
-template <bool PLUECKER, bool OCCLUDED, bool VEC>
-__global__ __launch_bounds__(TRACE_BLOCK, TRACE_INST_MIN_WAVES) void trace_instance_kernel(LaunchParams P)
+template <bool PLUECKER, bool OCCLUDED, bool VEC, bool QUADS>
+__global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUADS)) void trace_instance_kernel(LaunchParams P)
 {
   constexpr uint32_t FETCH = TRACE_INST_FETCH;
+  constexpr uint32_t QFETCH = TRACE_INST_QUAD_FETCH;
   constexpr bool ROBUST = PLUECKER; // Pluecker <-> robust traversal, Moeller <-> fast traversal, on both levels
   __shared__ uint2 ldsStack[TRACE_LDS_STACK + 1][TRACE_BLOCK]; // + one scratch row for the branch-free pushes
   const uint32_t tid = threadIdx.x;
@@ -69,8 +96,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_INST_MIN_WAVES) void trace_insta
   float travFar = 0.f;
   uint32_t sp = 0, cur = REF_EMPTY, rayIdx = 0;
   uint32_t curInst = 0xFFFFFFFFu, hitInst = 0xFFFFFFFFu; // geomID of the instance being traversed / of the hit's instance
-  // lane state bits (vector register, see RayState::hit): the lane owns a ray, its next event is a pop, it is inside an instance
-  enum : uint32_t { ST_ACTIVE = 1u, ST_POP = 2u, ST_INSIDE = 4u };
+  // lane state bits (vector register, see RayState::hit): the lane owns a ray, its next event is a pop, it is inside an instance,
+  // it is in the instanced scene's quad tree (QUADS only)
+  enum : uint32_t { ST_ACTIVE = 1u, ST_POP = 2u, ST_INSIDE = 4u, ST_QUADS = 8u };
   uint32_t st = 0u;
   r.hit = 0u;
 
@@ -256,53 +284,113 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_INST_MIN_WAVES) void trace_insta
       curInst = q3.x;
       cur = q3.y;
       st = ST_ACTIVE | ST_INSIDE;
+      if (QUADS) { // q3.z: the quad root (InstanceRecord::pad[0]), REF_EMPTY without quads; q3.y is REF_EMPTY without triangles
+        if (q3.z != REF_EMPTY) {
+          if (cur != REF_EMPTY) { // triangles first: the quad tree waits on the stack, its root in the distance word
+            push(REF_INST_QUADS, q3.z, sp);
+            sp++;
+          } else {
+            cur = q3.z;
+            st |= ST_QUADS;
+          }
+        } else if (cur == REF_EMPTY) st |= ST_POP; // neither tree (the builder leaves such instances out)
+      }
     }
 
-    // ---- triangle leaf inside an instance: run when enough lanes wait at one, or when nobody has node work -------------
-    const bool atLeaf = st == (ST_ACTIVE | ST_INSIDE) && (cur & REF_LEAF);
+    // ---- triangle / quad leaf inside an instance: run when enough lanes wait at one, or when nobody has node work -------
+    const bool atLeaf = (QUADS ? st & ~ST_QUADS : st) == (ST_ACTIVE | ST_INSIDE) && (cur & REF_LEAF);
     const uint64_t leafMask = __ballot(atLeaf);
     if (leafMask != 0ull) {
       const bool nodeWork = __ballot((st & ST_ACTIVE) && !(st & ST_POP) && !(cur & REF_LEAF)) != 0ull;
       if (((uint32_t)__popcll(leafMask) >= P.leafBatch || !nodeWork) && atLeaf) {
-        // the block loop of TriLeaf::intersect (trace_tri.hip; intersector_iterators.h:32-36, epilog intersector_epilog.h:226-307 / :388-450)
         uint32_t first, count;
         leaf_range(cur, first, count);
         bool occl = false;
-        for (uint32_t b = 0; b < count && !occl; b += 4) {
-          const float tfarBlock = r.tfar; // all records of a block see the tfar at block entry
-          const uint32_t nb = min(4u, count - b);
-          bool found = false;
-          TriHit best;
-          uint32_t bestPrim = 0, bestGeom = 0;
-          best.t = RT_INF;
-          // FETCH records are requested before the first one is used; slots past the leaf end re-read the last record and are skipped below
-          for (uint32_t g = 0; g < nb && !occl; g += FETCH) {
-            float4 A[FETCH], B[FETCH], C[FETCH];
+        if (QUADS && (st & ST_QUADS)) {
+          // the block loop of QuadLeaf::intersect (trace_quad.hip; quad_intersector_pluecker.h:264-299, quad_intersector_moeller.h:251-290)
+          const QuadRecord* __restrict__ quads = (const QuadRecord*)P.accel.blobs; // behind the InstanceRecords: the leaf references are rebased
+          for (uint32_t b = 0; b < count && !occl; b += 4) {
+            const float tfarBlock = r.tfar; // all 8 candidates of a block see the tfar at block entry
+            const uint32_t nb = min(4u, count - b);
+            bool found = false;
+            TriHit best;
+            uint32_t bestLane = 8u, bestPrim = 0, bestGeom = 0;
+            best.t = RT_INF;
+            // QFETCH records are requested before the first one is used; slots past the leaf end re-read the last record and are skipped below
+            for (uint32_t g = 0; g < nb && !occl; g += QFETCH) {
+              float4 V0[QFETCH], V1[QFETCH], V2[QFETCH], V3[QFETCH];
 #pragma unroll
-            for (uint32_t k = 0; k < FETCH; k++) {
-              const float4* tp = (const float4*)(prims + first + b + min(g + k, nb - 1u));
-              A[k] = tp[0]; B[k] = tp[1]; C[k] = tp[2];
-            }
+              for (uint32_t k = 0; k < QFETCH; k++) {
+                const float4* qp = (const float4*)(quads + first + b + min(g + k, nb - 1u));
+                V0[k] = qp[0]; V1[k] = qp[1]; V2[k] = qp[2]; V3[k] = qp[3];
+              }
 #pragma unroll
-            for (uint32_t k = 0; k < FETCH; k++) {
-              if (g + k >= nb) break;
-              TriHit h;
-              const bool ok = PLUECKER ? pluecker(r, A[k], B[k], C[k], tfarBlock, h) : moeller(r, A[k], B[k], C[k], tfarBlock, h);
-              if (ok) {
-                if (OCCLUDED) { occl = true; break; } // Occluded1EpilogM: any valid lane
-                // select_min over valid lanes, lowest lane wins ties (vfloat4_sse2.h:654-659)
-                if (!found || h.t < best.t) {
-                  best = h;
-                  bestGeom = __float_as_uint(A[k].w);
-                  bestPrim = __float_as_uint(B[k].w);
-                  found = true;
+              for (uint32_t k = 0; k < QFETCH; k++) {
+                if (g + k >= nb || occl) break;
+                const uint32_t gid = __float_as_uint(V0[k].w), pid = __float_as_uint(V1[k].w);
+#pragma unroll
+                for (uint32_t half = 0; half < 2; half++) { // A then B of this quad (lanes g+k and 4+g+k)
+                  TriHit h;
+                  const bool ok = PLUECKER ? pluecker_quad(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h)
+                                           : moeller_quad(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h);
+                  if (ok) {
+                    if (OCCLUDED) { occl = true; break; } // Occluded1EpilogM: any valid lane
+                    // select_min over the 8 lanes, lowest lane wins ties
+                    const uint32_t lane = half * 4u + g + k;
+                    if (!found || h.t < best.t || (h.t == best.t && lane < bestLane)) {
+                      best = h;
+                      bestLane = lane;
+                      bestGeom = gid;
+                      bestPrim = pid;
+                      found = true;
+                    }
+                  }
                 }
               }
             }
+            if (found) { // Intersect1EpilogM, intersector_epilog.h:293-305; instID: instance_intersector.cpp:57
+              commit_hit(r, best, bestGeom, bestPrim);
+              hitInst = curInst;
+            }
           }
-          if (found) { // Intersect1EpilogM, intersector_epilog.h:293-305; instID: instance_intersector.cpp:57
-            commit_hit(r, best, bestGeom, bestPrim);
-            hitInst = curInst;
+        } else {
+          // the block loop of TriLeaf::intersect (trace_tri.hip; intersector_iterators.h:32-36, epilog intersector_epilog.h:226-307 / :388-450)
+          for (uint32_t b = 0; b < count && !occl; b += 4) {
+            const float tfarBlock = r.tfar; // all records of a block see the tfar at block entry
+            const uint32_t nb = min(4u, count - b);
+            bool found = false;
+            TriHit best;
+            uint32_t bestPrim = 0, bestGeom = 0;
+            best.t = RT_INF;
+            // FETCH records are requested before the first one is used; slots past the leaf end re-read the last record and are skipped below
+            for (uint32_t g = 0; g < nb && !occl; g += FETCH) {
+              float4 A[FETCH], B[FETCH], C[FETCH];
+#pragma unroll
+              for (uint32_t k = 0; k < FETCH; k++) {
+                const float4* tp = (const float4*)(prims + first + b + min(g + k, nb - 1u));
+                A[k] = tp[0]; B[k] = tp[1]; C[k] = tp[2];
+              }
+#pragma unroll
+              for (uint32_t k = 0; k < FETCH; k++) {
+                if (g + k >= nb) break;
+                TriHit h;
+                const bool ok = PLUECKER ? pluecker(r, A[k], B[k], C[k], tfarBlock, h) : moeller(r, A[k], B[k], C[k], tfarBlock, h);
+                if (ok) {
+                  if (OCCLUDED) { occl = true; break; } // Occluded1EpilogM: any valid lane
+                  // select_min over valid lanes, lowest lane wins ties (vfloat4_sse2.h:654-659)
+                  if (!found || h.t < best.t) {
+                    best = h;
+                    bestGeom = __float_as_uint(A[k].w);
+                    bestPrim = __float_as_uint(B[k].w);
+                    found = true;
+                  }
+                }
+              }
+            }
+            if (found) { // Intersect1EpilogM, intersector_epilog.h:293-305; instID: instance_intersector.cpp:57
+              commit_hit(r, best, bestGeom, bestPrim);
+              hitInst = curInst;
+            }
           }
         }
         if (OCCLUDED && occl) {
@@ -333,8 +421,13 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_INST_MIN_WAVES) void trace_insta
           r.ox = w.ox; r.oy = w.oy; r.oz = w.oz;
           r.dx = w.dx; r.dy = w.dy; r.dz = w.dz;
           tr.init(r);
-          st &= ~ST_INSIDE;
+          st &= QUADS ? ~(ST_INSIDE | ST_QUADS) : ~ST_INSIDE;
           continue;
+        }
+        if (QUADS && e.x == REF_INST_QUADS) { // the triangle tree is done: on to the instanced scene's quad tree; before the distance cull
+          st |= ST_QUADS;
+          cur = e.y;
+          break;
         }
         if (!OCCLUDED && __uint_as_float(e.y) > r.tfar) continue; // bvh_intersector1.cpp:86
         cur = e.x;
@@ -353,7 +446,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_INST_MIN_WAVES) void trace_insta
   }
 }
 
-template <bool PLUECKER, bool OCCLUDED>
+template <bool PLUECKER, bool OCCLUDED, bool QUADS>
 inline hipError_t launch_instance_vec(const LaunchParams& p, hipStream_t stream)
 {
   const bool vec = (p.stride % 16 == 0) && (((uintptr_t)p.rays) % 16 == 0);
@@ -361,14 +454,14 @@ inline hipError_t launch_instance_vec(const LaunchParams& p, hipStream_t stream)
   static int occVec = 0, occGen = 0;
   int& occ = vec ? occVec : occGen;
   if (occ == 0) {
-    hipError_t e = vec ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_kernel<PLUECKER, OCCLUDED, true>, TRACE_BLOCK, 0)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_kernel<PLUECKER, OCCLUDED, false>, TRACE_BLOCK, 0);
+    hipError_t e = vec ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_kernel<PLUECKER, OCCLUDED, true, QUADS>, TRACE_BLOCK, 0)
+                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_kernel<PLUECKER, OCCLUDED, false, QUADS>, TRACE_BLOCK, 0);
     if (e != hipSuccess || occ <= 0) occ = 1;
   }
   uint32_t blocks = (p.blocksPerCU ? std::min<uint32_t>(p.blocksPerCU, (uint32_t)occ) : (uint32_t)occ) * p.numCUs;
   if (blocks > p.gridBlocks) blocks = p.gridBlocks;
-  if (vec) hipLaunchKernelGGL((trace_instance_kernel<PLUECKER, OCCLUDED, true>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
-  else hipLaunchKernelGGL((trace_instance_kernel<PLUECKER, OCCLUDED, false>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
+  if (vec) hipLaunchKernelGGL((trace_instance_kernel<PLUECKER, OCCLUDED, true, QUADS>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
+  else hipLaunchKernelGGL((trace_instance_kernel<PLUECKER, OCCLUDED, false, QUADS>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
   return hipGetLastError();
 }
 
@@ -377,8 +470,13 @@ inline hipError_t launch_instance_vec(const LaunchParams& p, hipStream_t stream)
 hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream)
 {
   if (p.counters) return hipErrorInvalidValue; // no instrumented twin (rt_trace.cpp refuses counted batches on scenes with instances)
-  if (p.accel.kind == ACCEL_INST_TRI_PLUECKER) return p.occluded ? dev::launch_instance_vec<true, true>(p, stream) : dev::launch_instance_vec<true, false>(p, stream);
-  return p.occluded ? dev::launch_instance_vec<false, true>(p, stream) : dev::launch_instance_vec<false, false>(p, stream);
+  switch (p.accel.kind) {
+  case ACCEL_INST_TRI_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, false>(p, stream) : dev::launch_instance_vec<true, false, false>(p, stream);
+  case ACCEL_INST_TRI_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, false>(p, stream) : dev::launch_instance_vec<false, false, false>(p, stream);
+  case ACCEL_INST_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, true>(p, stream) : dev::launch_instance_vec<true, false, true>(p, stream);
+  case ACCEL_INST_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, true>(p, stream) : dev::launch_instance_vec<false, false, true>(p, stream);
+  default: return hipErrorInvalidValue;
+  }
 }
 
 } // namespace rtamd

@@ -426,7 +426,7 @@ class Scene:
         return gid
 
     def add_instance(self, scene, xfm=None, geom_id=None):
-        """RTC_GEOMETRY_TYPE_INSTANCE of `scene` (a committed Scene of static triangle meshes on the same device).  xfm: the
+        """RTC_GEOMETRY_TYPE_INSTANCE of `scene` (a committed Scene of static triangle and / or quad meshes on the same device).  xfm: the
         local-to-world transform as a float32 [3,4] row-major matrix (None: identity)."""
         L = self.lib
         g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_INSTANCE)

@@ -14,10 +14,10 @@ for line in open('/tmp/kres.log'):
         cur = subprocess.run(['c++filt', m.group(1)], capture_output=True, text=True).stdout.strip()
         cur = cur.replace('rtamd::dev::', '').replace('(rtamd::LaunchParams)', '').replace('void ', '')
         vals = {}
-    for key in ('VGPRs', 'ScratchSize [bytes/lane]', 'LDS Size [bytes/block]', 'Occupancy [waves/SIMD]'):
+    for key in ('TotalSGPRs', 'VGPRs', 'ScratchSize [bytes/lane]', 'LDS Size [bytes/block]', 'Occupancy [waves/SIMD]'):
         m = re.search(re.escape(key) + r': (\d+)', line)
         if m and cur:
             vals[key] = m.group(1)
             if key == 'LDS Size [bytes/block]':
-                print('%-70s vgpr %3s scratch %4s occ %s lds %s' % (cur, vals.get('VGPRs'), vals.get('ScratchSize [bytes/lane]'), vals.get('Occupancy [waves/SIMD]'), vals[key]))
+                print('%-70s vgpr %3s sgpr %3s scratch %4s occ %s lds %s' % (cur, vals.get('VGPRs'), vals.get('TotalSGPRs'), vals.get('ScratchSize [bytes/lane]'), vals.get('Occupancy [waves/SIMD]'), vals[key]))
 PY

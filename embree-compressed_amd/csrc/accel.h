@@ -155,14 +155,33 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // A quad leaf reference is rebased by N + the scene's quad base, so that the kernel indexes `blobs` as ONE array of 64-byte records
 // (sizeof(InstanceRecord) == sizeof(QuadRecord)); the rebased first record must stay below 2^26.  `root` is REF_EMPTY for a scene
 // without triangles, pad[0] the rebased quad root, REF_EMPTY for a scene without quads.
+//
+// Kinds ACCEL_INSTMB_*: at least one enabled instance has more than one time step (instance motion blur).  The layout is that of the
+// static kind with the same triangle / quad content (ACCEL_INSTMB_TRI_* <-> ACCEL_INST_TRI_*, ACCEL_INSTMB_PLUECKER / _MOELLER <->
+// ACCEL_INST_PLUECKER / _MOELLER), with the moving instances' local-to-world transforms appended to `blobs`:
+//   blobs : the N InstanceRecords | the QuadRecords | instance a's InstanceSteps (one per time step) | instance b's | ...
+// A moving instance's record has pad[1] = (S << 24) | firstStep: S = time steps - 1 segments (1..128), firstStep the index of its
+// first InstanceStep in 64-byte units from the start of `blobs` (below 2^24, or the commit is refused).  A ray at `time` enters it
+// through world2local(time) = inverse(lerp(step[itime], step[itime + 1], ftime)) (instance_xfm.h; itime / ftime as in the motion-blur
+// records above); the record's world2local is the inverse of step 0 as the static path computes it and is not used by the kernel.
+// An instance with one time step in such a scene has pad[1] == 0 and is entered through its record exactly as in the static kinds.
+// The top-level box of a moving instance is the union over its steps of the transformed scene bounds.
 struct alignas(16) InstanceRecord
 {
   float world2local[12]; // vx.xyz, vy.xyz, vz.xyz, p.xyz
   uint32_t geomID;       // of the instance in the top scene: the hit's instID (instance_intersector.cpp:57)
   uint32_t root;         // rebased root reference of the instanced scene's triangle tree
-  uint32_t pad[2];       // pad[0]: rebased root reference of the instanced scene's quad tree (kinds ACCEL_INST_PLUECKER / _MOELLER only)
+  uint32_t pad[2];       // pad[0]: rebased root reference of the instanced scene's quad tree (kinds ACCEL_INST[MB]_PLUECKER / _MOELLER only)
+                         // pad[1]: (S << 24) | firstStep of a moving instance (kinds ACCEL_INSTMB_* only), else 0
 };
 static_assert(sizeof(InstanceRecord) == 64, "InstanceRecord must be 64 bytes");
+// One time step of a moving instance (kinds ACCEL_INSTMB_*), 64 bytes = 4 x dwordx4, of which the kernel loads three
+struct alignas(16) InstanceStep
+{
+  float local2world[12]; // vx.xyz, vy.xyz, vz.xyz, p.xyz
+  uint32_t pad[4];       // zero
+};
+static_assert(sizeof(InstanceStep) == sizeof(InstanceRecord), "the instance kernel indexes InstanceRecords and InstanceSteps as one array");
 // Marker on the traversal stack of the instance kernel (trace_instance.hip): popping it leaves the instance.  A leaf-flagged reference with
 // count 0, which make_tri_leaf never produces (counts are 1..28), and not REF_EMPTY.
 static const uint32_t REF_INST_EXIT = 0x80000000u;
@@ -258,9 +277,14 @@ enum AccelKind : uint32_t
   ACCEL_INST_TRI_PLUECKER = 14, // instances of scenes whose triangle accel is ACCEL_TRI_PLUECKER: robust traversal on both levels
   ACCEL_INST_TRI_MOELLER = 15,  // instances of scenes whose triangle accel is ACCEL_TRI_MOELLER: fast traversal on both levels
   ACCEL_INST_PLUECKER = 16,     // instances of scenes with triangles (Pluecker) and / or quads (Pluecker): robust traversal on both levels
-  ACCEL_INST_MOELLER = 17       // instances of scenes with triangles (Moeller) and / or quads (Moeller): fast traversal on both levels
+  ACCEL_INST_MOELLER = 17,      // instances of scenes with triangles (Moeller) and / or quads (Moeller): fast traversal on both levels
+  // instance motion blur: the four kinds above when at least one enabled instance has more than one time step (InstanceStep)
+  ACCEL_INSTMB_TRI_PLUECKER = 18,
+  ACCEL_INSTMB_TRI_MOELLER = 19,
+  ACCEL_INSTMB_PLUECKER = 20,
+  ACCEL_INSTMB_MOELLER = 21
 };
-inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INST_MOELLER; } // traced by trace_instance.hip
+inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTMB_MOELLER; } // traced by trace_instance.hip
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc

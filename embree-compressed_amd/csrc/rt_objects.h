@@ -215,6 +215,9 @@ struct Device : RefCounted
   // Quad meshes inside an instanced scene, the same rule with the key inst_accel=: a host-only device without it refuses them at the top
   // scene's commit, as before the instance accel took quads.
   bool inst_quads_enabled() const { return gpu >= 0 || instAccelNamed; }
+  // Instances with more than one time step, the same rule: a host-only device whose config does not name inst_accel= refuses them at
+  // commit, as before the instance accel took them.
+  bool inst_motion_enabled() const { return gpu >= 0 || instAccelNamed; }
   bool tuneBlocksAuto = true; // no RTAMD_BLOCKS_PER_CU given: 2 workgroups per CU, 1 when >= 2 batches run on other streams
   void memoryMonitor(ssize_t bytes, bool post);
 };
@@ -279,10 +282,19 @@ struct Geometry : RefCounted
   std::mutex interpMutex;
 
   // RTC_GEOMETRY_TYPE_INSTANCE (reference: Instance, kernels/common/scene_instance.h): the instanced scene (retained) and the
-  // local-to-world transform of time step 0 as the columns vx, vy, vz, p of an AffineSpace3f (identity by default)
+  // local-to-world transform of every time step as the columns vx, vy, vz, p of an AffineSpace3f (identity by default); an instance
+  // keeps `timeSteps` of them (setInstanceTimeSteps: Instance::setNumTimeSteps, scene_instance.cpp:50-67)
+  typedef std::array<float, 12> Xfm;
+  static constexpr Xfm identityXfm = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
   Scene* instScene = nullptr;
-  float local2world[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+  std::vector<Xfm> local2world{identityXfm};
   void setInstancedScene(Scene* s);
+  void setInstanceTimeSteps(unsigned n) { local2world.resize(n, identityXfm); } // existing steps are kept, new ones are the identity
+  // local-to-world at `time`: lerp(local2world[itime], local2world[itime + 1], ftime); the step itself with one time step
+  void local2worldAt(float time, float* out) const;
+  // the matrix the instance kernel uses for a ray at `time` (csrc/instance_xfm.h); with one time step the record's world2local of the
+  // static path (invert_affine).  false: singular - `out` is all zero then
+  bool world2localAt(float time, float* out) const;
 
   Geometry(Device* d, RTCGeometryType t);
   ~Geometry() override;

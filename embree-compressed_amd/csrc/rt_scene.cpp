@@ -3,6 +3,7 @@
 #include <map>
 
 #include "bvh8_builder.h"
+#include "instance_xfm.h"
 #include "rt_objects.h"
 #include "rt_trace.h"
 #include "subdiv_build.h"
@@ -550,6 +551,30 @@ static bool invert_affine(const float* m, float* out)
   return true;
 }
 
+void Geometry::local2worldAt(float time, float* out) const
+{
+  if (local2world.size() == 1) {
+    memcpy(out, local2world[0].data(), sizeof(Xfm));
+    return;
+  }
+  float f;
+  const uint32_t itime = instance_time_segment(time, (uint32_t)local2world.size() - 1u, f);
+  instance_lerp(local2world[itime].data(), local2world[itime + 1].data(), f, out);
+}
+
+bool Geometry::world2localAt(float time, float* out) const
+{
+  bool ok;
+  if (local2world.size() == 1) ok = invert_affine(local2world[0].data(), out);
+  else {
+    float f;
+    const uint32_t itime = instance_time_segment(time, (uint32_t)local2world.size() - 1u, f);
+    ok = instance_world2local(local2world[itime].data(), local2world[itime + 1].data(), f, out);
+  }
+  if (!ok) memset(out, 0, sizeof(Xfm));
+  return ok;
+}
+
 // xfmPoint (affinespace.h:110): madd(p.x, vx, madd(p.y, vy, madd(p.z, vz, p)))
 static V3 xfm_point(const float* m, V3 q)
 {
@@ -567,6 +592,14 @@ static V3 xfm_point(const float* m, V3 q)
 // trees behind the top-level tree, TriRecords, InstanceRecords, `pad` zero); otherwise it is the layout of accel.h InstanceRecord
 // (kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER).  A host-only device takes quads in an instanced scene only when its config names
 // inst_accel= (Device::inst_quads_enabled), as it takes quad meshes at all only with quad_accel=.
+// Instance motion blur: as soon as one enabled instance has more than one time step the kinds are ACCEL_INSTMB_* (chosen otherwise
+// exactly as ACCEL_INST_*) and the steps' local-to-world transforms follow the quad records in `blobs` as InstanceSteps (accel.h).  The
+// world box of a moving instance is the union over its steps of xfmBounds(local2world[i], scene bounds): the instanced scene is static
+// and the lerp of two affine maps sends a point to the lerp of its images, so the union of the steps' boxes holds the object at every
+// time - one box swept over the whole shutter, like the motion-blur mesh accels.  A host-only device takes
+// such instances under the rule of quads (Device::inst_motion_enabled).
+// First InstanceStep a record may name, in 64-byte units from the start of `blobs`, exclusive: 24 bits beside the segment count.
+static const size_t INSTANCE_FIRST_STEP_LIMIT = (size_t)1 << 24;
 static void build_instance_accel(Scene* s)
 {
   Accel& A = s->instAccel;
@@ -579,11 +612,11 @@ static void build_instance_accel(Scene* s)
   struct Src { unsigned geomID; Scene* scene; };
   std::vector<Src> src;
   std::vector<BuildPrim> bp;
-  bool haveKind = false, pluecker = false, anyQuads = false;
+  bool haveKind = false, pluecker = false, anyQuads = false, anyMotion = false;
   for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
     Geometry* g = s->geometries[gid];
     if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_INSTANCE) continue;
-    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instances with more than one time step are not supported");
+    if (g->timeSteps != 1 && !s->device->inst_motion_enabled()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instances with more than one time step are not supported");
     Scene* o = g->instScene;
     if (!o) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance without an instanced scene");
     if (o->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instanced scene got not committed");
@@ -611,9 +644,11 @@ static void build_instance_accel(Scene* s)
     haveKind = true;
     pluecker = pl;
     anyQuads |= quads;
+    anyMotion |= g->local2world.size() > 1;
     BuildPrim p;
     const V3 c[2] = {o->bounds.lo, o->bounds.hi};
-    for (int i = 0; i < 8; i++) p.box.extend(xfm_point(g->local2world, V3(c[i >> 2].x, c[(i >> 1) & 1].y, c[i & 1].z)));
+    for (const Geometry::Xfm& step : g->local2world) // one step: xfmBounds; more: the union over the steps
+      for (int i = 0; i < 8; i++) p.box.extend(xfm_point(step.data(), V3(c[i >> 2].x, c[(i >> 1) & 1].y, c[i & 1].z)));
     if (!(std::isfinite(p.box.lo.x) && std::isfinite(p.box.lo.y) && std::isfinite(p.box.lo.z) && std::isfinite(p.box.hi.x) && std::isfinite(p.box.hi.y) && std::isfinite(p.box.hi.z)))
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance transform yields bounds that are not finite");
     p.id = (uint32_t)src.size();
@@ -683,16 +718,31 @@ static void build_instance_accel(Scene* s)
     }
     rootsOf[sr.scene] = roots;
   }
+  std::vector<InstanceStep> steps; // of the moving instances, in record order, behind the quad records
   for (size_t i = 0; i < order.size(); i++) {
     const Src& sr = src[order[i]];
+    const Geometry* g = s->geometries[sr.geomID];
     InstanceRecord& rec = recs[i];
     memset(&rec, 0, sizeof(rec));
-    if (!invert_affine(s->geometries[sr.geomID]->local2world, rec.world2local)) memset(rec.world2local, 0, sizeof(rec.world2local)); // singular: never hit
+    if (!invert_affine(g->local2world[0].data(), rec.world2local)) memset(rec.world2local, 0, sizeof(rec.world2local)); // singular: never hit
     rec.geomID = sr.geomID;
     rec.root = rootsOf[sr.scene].tri;
     if (anyQuads) rec.pad[0] = rootsOf[sr.scene].quad;
+    if (g->local2world.size() > 1) {
+      const size_t firstStep = recs.size() + quadRecs.size() + steps.size();
+      if (firstStep >= INSTANCE_FIRST_STEP_LIMIT)
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances, instanced quads and instance time steps for the 24-bit step offset of an instance record");
+      rec.pad[1] = ((uint32_t)(g->local2world.size() - 1) << 24) | (uint32_t)firstStep;
+      for (const Geometry::Xfm& x : g->local2world) {
+        InstanceStep st;
+        memset(&st, 0, sizeof(st));
+        memcpy(st.local2world, x.data(), sizeof(st.local2world));
+        steps.push_back(st);
+      }
+    }
   }
-  if (anyQuads) A.kind = pluecker ? ACCEL_INST_PLUECKER : ACCEL_INST_MOELLER;
+  if (anyMotion) A.kind = anyQuads ? (pluecker ? ACCEL_INSTMB_PLUECKER : ACCEL_INSTMB_MOELLER) : (pluecker ? ACCEL_INSTMB_TRI_PLUECKER : ACCEL_INSTMB_TRI_MOELLER);
+  else if (anyQuads) A.kind = pluecker ? ACCEL_INST_PLUECKER : ACCEL_INST_MOELLER;
   else A.kind = pluecker ? ACCEL_INST_TRI_PLUECKER : ACCEL_INST_TRI_MOELLER;
   A.robust = pluecker ? 1 : 0;
   // launch_on's stack bound counts 7 entries per level.  Triangle-only: the top-level levels, the exit marker, the deepest instanced
@@ -701,9 +751,10 @@ static void build_instance_accel(Scene* s)
   // the quad marker is popped only when the triangle tree's entries are gone).
   A.maxDepth = r.maxDepth + 1u + (anyQuads ? 1u : 0u) + deepest;
   A.blobStride = sizeof(InstanceRecord);
-  A.blobs.resize((recs.size() + quadRecs.size()) * sizeof(InstanceRecord));
+  A.blobs.resize((recs.size() + quadRecs.size() + steps.size()) * sizeof(InstanceRecord));
   memcpy(A.blobs.data(), recs.data(), recs.size() * sizeof(InstanceRecord));
   if (!quadRecs.empty()) memcpy(A.blobs.data() + recs.size() * sizeof(InstanceRecord), quadRecs.data(), quadRecs.size() * sizeof(QuadRecord));
+  if (!steps.empty()) memcpy(A.blobs.data() + (recs.size() + quadRecs.size()) * sizeof(InstanceRecord), steps.data(), steps.size() * sizeof(InstanceStep));
 }
 
 void Scene::commit()
@@ -757,7 +808,7 @@ void Scene::commit()
   if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
     fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, %zu instanced quads, depth %u\n", instAccel.kind,
             instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),
-            instAccel.blobs.size() / sizeof(InstanceRecord) - instAccel.leafCount, instAccel.maxDepth);
+            instAccel.blobs.size() / sizeof(InstanceRecord) - instAccel.leafCount, instAccel.maxDepth); // (kinds ACCEL_INSTMB_*: quads and InstanceSteps)
   modified = false;
 }
 

@@ -191,6 +191,10 @@ API void rtcSetGeometryTimeStepCount(RTCGeometry h, unsigned int n)
   VERIFY(h);
   if (n == 0 || n > RTC_MAX_TIME_STEP_COUNT) RT_THROW(RTC_ERROR_INVALID_OPERATION, "number of time steps out of range");
   G(h)->timeSteps = n;
+  if (G(h)->type == RTC_GEOMETRY_TYPE_INSTANCE) { // Instance::setNumTimeSteps (scene_instance.cpp:50-67)
+    G(h)->setInstanceTimeSteps(n);
+    G(h)->committed = false;
+  }
   CATCH_END(devOf(h))
 }
 
@@ -338,24 +342,49 @@ API void rtcSetGeometryTransform(RTCGeometry h, unsigned int timeStep, enum RTCF
   VERIFY(xfm);
   if (G(h)->type != RTC_GEOMETRY_TYPE_INSTANCE) RT_THROW(RTC_ERROR_INVALID_OPERATION, "operation not supported for this geometry");
   if (transform_index(format, 0, 0) < 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid matrix format");
-  if (timeStep != 0) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instances with more than one time step are not supported: only time step 0 takes a transform");
+  if (timeStep >= G(h)->local2world.size()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid time step: the instance has fewer time steps (rtcSetGeometryTimeStepCount)");
   for (int col = 0; col < 4; col++)
-    for (int row = 0; row < 3; row++) G(h)->local2world[3 * col + row] = ((const float*)xfm)[transform_index(format, row, col)];
+    for (int row = 0; row < 3; row++) G(h)->local2world[timeStep][3 * col + row] = ((const float*)xfm)[transform_index(format, row, col)];
   G(h)->committed = false;
   CATCH_END(devOf(h))
 }
 
-API void rtcGetGeometryTransform(RTCGeometry h, float, enum RTCFormat format, void* xfm)
+// storeTransform (rtcore.cpp:916-943): the columns vx, vy, vz, p into a caller's array of `format`
+static void store_transform(const float* m, enum RTCFormat format, float* xfm)
+{
+  for (int col = 0; col < 4; col++)
+    for (int row = 0; row < 3; row++) xfm[transform_index(format, row, col)] = m[3 * col + row];
+  if (format == RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR) // the bottom row (storeTransform, rtcore.cpp:934-940)
+    for (int col = 0; col < 4; col++) xfm[4 * col + 3] = col == 3 ? 1.0f : 0.0f;
+}
+
+// The local-to-world transform at `time`: with one time step the transform set, with more lerp(local2world[itime],
+// local2world[itime + 1], ftime).  Deviation: the fork returns the INVERSE here for instances with time steps
+// (scene_instance.cpp:87-90); the inverse is rtcamdGetGeometryWorld2Local.
+API void rtcGetGeometryTransform(RTCGeometry h, float time, enum RTCFormat format, void* xfm)
 {
   CATCH_BEGIN
   VERIFY(h);
   VERIFY(xfm);
   if (G(h)->type != RTC_GEOMETRY_TYPE_INSTANCE) RT_THROW(RTC_ERROR_INVALID_OPERATION, "operation not supported for this geometry");
   if (transform_index(format, 0, 0) < 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid matrix format");
-  for (int col = 0; col < 4; col++)
-    for (int row = 0; row < 3; row++) ((float*)xfm)[transform_index(format, row, col)] = G(h)->local2world[3 * col + row];
-  if (format == RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR) // the bottom row (storeTransform, rtcore.cpp:934-940)
-    for (int col = 0; col < 4; col++) ((float*)xfm)[4 * col + 3] = col == 3 ? 1.0f : 0.0f;
+  float m[12];
+  G(h)->local2worldAt(time, m);
+  store_transform(m, format, (float*)xfm);
+  CATCH_END(devOf(h))
+}
+
+// Extension: the world-to-local matrix the traversal uses for a ray at `time` (rtcore_amd.h)
+API void rtcamdGetGeometryWorld2Local(RTCGeometry h, float time, enum RTCFormat format, void* xfm)
+{
+  CATCH_BEGIN
+  VERIFY(h);
+  VERIFY(xfm);
+  if (G(h)->type != RTC_GEOMETRY_TYPE_INSTANCE) RT_THROW(RTC_ERROR_INVALID_OPERATION, "operation not supported for this geometry");
+  if (transform_index(format, 0, 0) < 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid matrix format");
+  float m[12];
+  G(h)->world2localAt(time, m); // singular: all zero, the matrix under which nothing is hit
+  store_transform(m, format, (float*)xfm);
   CATCH_END(devOf(h))
 }
 

@@ -163,7 +163,11 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_INST_TRI_PLUECKER:
   case ACCEL_INST_TRI_MOELLER:
   case ACCEL_INST_PLUECKER:
-  case ACCEL_INST_MOELLER: return launch_trace_instance(p, stream);
+  case ACCEL_INST_MOELLER:
+  case ACCEL_INSTMB_TRI_PLUECKER:
+  case ACCEL_INSTMB_TRI_MOELLER:
+  case ACCEL_INSTMB_PLUECKER:
+  case ACCEL_INSTMB_MOELLER: return launch_trace_instance(p, stream);
   case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
 #ifdef TRACE_DEV_METRIC_ONLY
   case ACCEL_GRIDSOA:

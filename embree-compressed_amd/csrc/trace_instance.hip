@@ -29,8 +29,18 @@
 //       (v0, v1, v3) in lanes 0-3, B = (v2, v1, v3) in lanes 4-7), all against the tfar at block entry, one minimum, the lowest lane
 //       wins ties, a later block replaces an equal t.  The QuadRecords lie behind the InstanceRecords in `blobs`, one 64-byte array;
 //   4'. the exit marker clears the bit.
+//
+// XFMB (accel kinds ACCEL_INSTMB_*): instances may have time steps (instance motion blur, scene_instance.h:58-63,
+// instance_intersector.cpp:51-56).  Entering an instance whose record names InstanceSteps (pad[1] != 0) the lane reads its ray's time
+// through the ray's index, loads the two steps around it and computes world2local = inverse(lerp(step[itime], step[itime + 1], ftime))
+// with the function the host exports (instance_xfm.h), in place of the record's matrix; everything after that - the transform of org
+// and dir, the markers, the trees, leaving - is the static form.  A singular interpolated transform (det == 0 or a matrix that is
+// not finite) is not entered: the lane pops instead and pushes nothing, where the reference would trace NaNs.  An instance with one
+// time step in such a scene (pad[1] == 0) is entered through its record.
 #include "trace_leaf.hip.h"
 #include "trace_quad_tests.hip.h"
+#include "trace_mb.hip.h"
+#include "instance_xfm.h"
 
 namespace rtamd {
 namespace dev {
@@ -56,13 +66,13 @@ namespace dev {
 #ifndef TRACE_INST_QUAD_FETCH
 #define TRACE_INST_QUAD_FETCH 2
 #endif
-constexpr int inst_min_waves(bool pluecker, bool occluded, bool quads)
+constexpr int inst_min_waves(bool pluecker, bool occluded, bool quads, bool xfmb)
 {
   return quads && pluecker && !occluded ? TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_MIN_WAVES;
 }
 
-template <bool PLUECKER, bool OCCLUDED, bool VEC, bool QUADS>
-__global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUADS)) void trace_instance_kernel(LaunchParams P)
+template <bool PLUECKER, bool OCCLUDED, bool VEC, bool QUADS, bool XFMB>
+__global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUADS, XFMB)) void trace_instance_kernel(LaunchParams P)
 {
   constexpr uint32_t FETCH = TRACE_INST_FETCH;
   constexpr uint32_t QFETCH = TRACE_INST_QUAD_FETCH;
@@ -267,8 +277,26 @@ __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUA
     // ---- instance leaf: the ray enters the instance (no waiting: four loads, twelve FMAs, three divisions) -------------
     if (st == ST_ACTIVE && (cur & REF_LEAF)) {
       const float4* ip = (const float4*)(insts + (cur & ((1u << TRI_START_BITS) - 1u)));
-      const float4 q0 = ip[0], q1 = ip[1], q2 = ip[2]; // vx.xyz vy.x | vy.yz vz.xy | vz.z p.xyz
-      const uint4 q3 = ((const uint4*)ip)[3];          // geomID, root
+      float4 q0 = ip[0], q1 = ip[1], q2 = ip[2]; // vx.xyz vy.x | vy.yz vz.xy | vz.z p.xyz
+      const uint4 q3 = ((const uint4*)ip)[3];    // geomID, root, quad root, (S << 24) | firstStep
+      bool enter = true;
+      if (XFMB) {
+        if (q3.w != 0u) { // a moving instance: world2local at the ray's time replaces the record's (instance_xfm.h)
+          float f;
+          const uint32_t itime = instance_time_segment(ray_time(P, rayIdx), q3.w >> 24, f);
+          const float4* sp4 = (const float4*)(insts + (q3.w & 0xFFFFFFu) + itime); // InstanceStep[itime], [itime + 1]: 64 bytes each
+          const float4 a0 = sp4[0], a1 = sp4[1], a2 = sp4[2], b0 = sp4[4], b1 = sp4[5], b2 = sp4[6];
+          const float A[12] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w};
+          const float B[12] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w};
+          float W[12];
+          enter = instance_world2local(A, B, f, W);
+          q0 = make_float4(W[0], W[1], W[2], W[3]);
+          q1 = make_float4(W[4], W[5], W[6], W[7]);
+          q2 = make_float4(W[8], W[9], W[10], W[11]);
+        }
+      }
+      if (XFMB && !enter) st |= ST_POP; // singular interpolated transform: the ray does not enter, nothing is pushed
+      else {
       const float wox = r.ox, woy = r.oy, woz = r.oz, wdx = r.dx, wdy = r.dy, wdz = r.dz;
       // xfmPoint (affinespace.h:110): madd(p.x, vx, madd(p.y, vy, madd(p.z, vz, p)))
       r.ox = madd(wox, q0.x, madd(woy, q0.w, madd(woz, q1.z, q2.y)));
@@ -294,6 +322,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUA
             st |= ST_QUADS;
           }
         } else if (cur == REF_EMPTY) st |= ST_POP; // neither tree (the builder leaves such instances out)
+      }
       }
     }
 
@@ -446,7 +475,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUA
   }
 }
 
-template <bool PLUECKER, bool OCCLUDED, bool QUADS>
+template <bool PLUECKER, bool OCCLUDED, bool QUADS, bool XFMB>
 inline hipError_t launch_instance_vec(const LaunchParams& p, hipStream_t stream)
 {
   const bool vec = (p.stride % 16 == 0) && (((uintptr_t)p.rays) % 16 == 0);
@@ -454,14 +483,14 @@ inline hipError_t launch_instance_vec(const LaunchParams& p, hipStream_t stream)
   static int occVec = 0, occGen = 0;
   int& occ = vec ? occVec : occGen;
   if (occ == 0) {
-    hipError_t e = vec ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_kernel<PLUECKER, OCCLUDED, true, QUADS>, TRACE_BLOCK, 0)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_kernel<PLUECKER, OCCLUDED, false, QUADS>, TRACE_BLOCK, 0);
+    hipError_t e = vec ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_kernel<PLUECKER, OCCLUDED, true, QUADS, XFMB>, TRACE_BLOCK, 0)
+                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_kernel<PLUECKER, OCCLUDED, false, QUADS, XFMB>, TRACE_BLOCK, 0);
     if (e != hipSuccess || occ <= 0) occ = 1;
   }
   uint32_t blocks = (p.blocksPerCU ? std::min<uint32_t>(p.blocksPerCU, (uint32_t)occ) : (uint32_t)occ) * p.numCUs;
   if (blocks > p.gridBlocks) blocks = p.gridBlocks;
-  if (vec) hipLaunchKernelGGL((trace_instance_kernel<PLUECKER, OCCLUDED, true, QUADS>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
-  else hipLaunchKernelGGL((trace_instance_kernel<PLUECKER, OCCLUDED, false, QUADS>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
+  if (vec) hipLaunchKernelGGL((trace_instance_kernel<PLUECKER, OCCLUDED, true, QUADS, XFMB>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
+  else hipLaunchKernelGGL((trace_instance_kernel<PLUECKER, OCCLUDED, false, QUADS, XFMB>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
   return hipGetLastError();
 }
 
@@ -471,10 +500,14 @@ hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream)
 {
   if (p.counters) return hipErrorInvalidValue; // no instrumented twin (rt_trace.cpp refuses counted batches on scenes with instances)
   switch (p.accel.kind) {
-  case ACCEL_INST_TRI_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, false>(p, stream) : dev::launch_instance_vec<true, false, false>(p, stream);
-  case ACCEL_INST_TRI_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, false>(p, stream) : dev::launch_instance_vec<false, false, false>(p, stream);
-  case ACCEL_INST_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, true>(p, stream) : dev::launch_instance_vec<true, false, true>(p, stream);
-  case ACCEL_INST_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, true>(p, stream) : dev::launch_instance_vec<false, false, true>(p, stream);
+  case ACCEL_INST_TRI_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, false, false>(p, stream) : dev::launch_instance_vec<true, false, false, false>(p, stream);
+  case ACCEL_INST_TRI_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, false, false>(p, stream) : dev::launch_instance_vec<false, false, false, false>(p, stream);
+  case ACCEL_INST_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, true, false>(p, stream) : dev::launch_instance_vec<true, false, true, false>(p, stream);
+  case ACCEL_INST_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, true, false>(p, stream) : dev::launch_instance_vec<false, false, true, false>(p, stream);
+  case ACCEL_INSTMB_TRI_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, false, true>(p, stream) : dev::launch_instance_vec<true, false, false, true>(p, stream);
+  case ACCEL_INSTMB_TRI_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, false, true>(p, stream) : dev::launch_instance_vec<false, false, false, true>(p, stream);
+  case ACCEL_INSTMB_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, true, true>(p, stream) : dev::launch_instance_vec<true, false, true, true>(p, stream);
+  case ACCEL_INSTMB_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, true, true>(p, stream) : dev::launch_instance_vec<false, false, true, true>(p, stream);
   default: return hipErrorInvalidValue;
   }
 }

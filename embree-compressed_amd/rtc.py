@@ -186,14 +186,15 @@ def load_library(path=LIB_PATH):
         "rtcamdOccluded1MCounted": (None, [vp, C.POINTER(RTCIntersectContext), vp, u, sz, C.POINTER(RTCAMDTraceCounters)]),
         "rtcamdGetAccelData": (vp, [vp, u, C.POINTER(sz)]),
         "rtcamdGetAccelRoot": (u, [vp]),
+        "rtcamdGetGeometryWorld2Local": (None, [vp, C.c_float, C.c_int, vp]),
         "rtcamdDebugReadWaveLog": (C.c_size_t, [vp, vp, C.c_size_t]),
         "rtcamdDebugHoldCombiner": (None, [vp, C.c_int]),
         "rtcamdDebugCbvhLeafCodec": (None, [vp, vp, C.c_float, vp, C.POINTER(C.c_float)]),
         "rtcamdDebugHostPoolSelfTest": (C.c_ulonglong, [vp, u, u, u, u]),
     }
     for name, (res, args) in sig.items():
-        if name.startswith("rtcamdDebug") and not hasattr(lib, name):
-            continue  # development hooks: an older build of the library (RTAMD_LIB=... in an A/B sweep) may lack the newest one
+        if (name.startswith("rtcamdDebug") or name == "rtcamdGetGeometryWorld2Local") and not hasattr(lib, name):
+            continue  # development hooks and the newest extension: an older build of the library (RTAMD_LIB=... in an A/B sweep) may lack them
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -446,24 +447,60 @@ class Scene:
         self.device.check("add_instance")
         return gid
 
-    def set_instance_transform(self, geom_id, xfm, fmt=RTC_FORMAT_FLOAT3X4_ROW_MAJOR):
-        """Set the local-to-world transform of an attached instance and re-commit the geometry (the scene is committed by the caller).
-        xfm: float32 values in `fmt` (3x4 row-major by default; 3x4 or 4x4 column-major)."""
+    def add_instance_mb(self, scene, xfms, geom_id=None):
+        """An instance with time steps (instance motion blur): xfms is a sequence of N >= 1 local-to-world transforms, float32 [3,4]
+        row-major each, one per time step (rtcSetGeometryTimeStepCount, then rtcSetGeometryTransform per step).  A ray sees the
+        instance under lerp(xfms[itime], xfms[itime + 1], ftime) at its ray.time."""
+        L = self.lib
+        steps = [np.ascontiguousarray(x, dtype=np.float32).reshape(3, 4) for x in xfms]
+        g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_INSTANCE)
+        self.device.check("rtcNewGeometry(INSTANCE)")
+        L.rtcSetGeometryInstancedScene(g, scene.handle)
+        L.rtcSetGeometryTimeStepCount(g, len(steps))
+        for i, m in enumerate(steps):
+            L.rtcSetGeometryTransform(g, i, RTC_FORMAT_FLOAT3X4_ROW_MAJOR, m.ctypes.data)
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self._keep.append(scene)
+        self.device.check("add_instance_mb")
+        return gid
+
+    def set_instance_transform(self, geom_id, xfm, fmt=RTC_FORMAT_FLOAT3X4_ROW_MAJOR, time_step=0):
+        """Set the local-to-world transform of time step `time_step` of an attached instance and re-commit the geometry (the scene is
+        committed by the caller).  xfm: float32 values in `fmt` (3x4 row-major by default; 3x4 or 4x4 column-major)."""
         g = self.lib.rtcGetGeometry(self.handle, geom_id)
         m = np.ascontiguousarray(xfm, dtype=np.float32).reshape(-1)
-        self.lib.rtcSetGeometryTransform(g, 0, fmt, m.ctypes.data)
+        self.lib.rtcSetGeometryTransform(g, time_step, fmt, m.ctypes.data)
         self.lib.rtcCommitGeometry(g)
         self.device.check("set_instance_transform")
 
-    def get_instance_transform(self, geom_id, fmt=RTC_FORMAT_FLOAT3X4_ROW_MAJOR):
-        """The stored local-to-world transform in `fmt`: float32 [3,4] (row-major), [12] (3x4 column-major) or [16] (4x4 column-major)."""
-        g = self.lib.rtcGetGeometry(self.handle, geom_id)
-        out = np.zeros(16, np.float32)
-        self.lib.rtcGetGeometryTransform(g, 0.0, fmt, out.ctypes.data)
-        self.device.check("get_instance_transform")
+    @staticmethod
+    def _transform_out(out, fmt):
         if fmt == RTC_FORMAT_FLOAT3X4_ROW_MAJOR:
             return out[:12].reshape(3, 4).copy()
         return out[:16 if fmt == RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR else 12].copy()
+
+    def get_instance_transform(self, geom_id, fmt=RTC_FORMAT_FLOAT3X4_ROW_MAJOR, time=0.0):
+        """The local-to-world transform at `time` in `fmt`: float32 [3,4] (row-major), [12] (3x4 column-major) or [16] (4x4
+        column-major).  One time step: the stored transform; more: the lerp of the two steps around `time`."""
+        g = self.lib.rtcGetGeometry(self.handle, geom_id)
+        out = np.zeros(16, np.float32)
+        self.lib.rtcGetGeometryTransform(g, time, fmt, out.ctypes.data)
+        self.device.check("get_instance_transform")
+        return self._transform_out(out, fmt)
+
+    def instance_world2local(self, geom_id, time=0.0, fmt=RTC_FORMAT_FLOAT3X4_ROW_MAJOR):
+        """rtcamdGetGeometryWorld2Local: the world-to-local matrix the traversal uses for a ray at `time` (hits carry the LOCAL Ng)."""
+        g = self.lib.rtcGetGeometry(self.handle, geom_id)
+        out = np.zeros(16, np.float32)
+        self.lib.rtcamdGetGeometryWorld2Local(g, time, fmt, out.ctypes.data)
+        self.device.check("instance_world2local")
+        return self._transform_out(out, fmt)
 
     def set_filters(self, geom_id, intersect=None, occluded=None):
         """intersect / occluded: FILTER_FUNC objects (kept alive by the scene wrapper) or None."""

@@ -31,6 +31,16 @@ RTC_API void rtcamdSynchronizeDevice(RTCDevice device);
 /* HIP device ordinal the RTCDevice was created on (config key "gpu="). */
 RTC_API int rtcamdGetDeviceOrdinal(RTCDevice device);
 
+/* World-to-local transform of an RTC_GEOMETRY_TYPE_INSTANCE geometry at `time`, in `format` (one of the three transform
+ * formats of rtcSetGeometryTransform): exactly the matrix the traversal applies to a ray with that ray.time when it enters
+ * the instance.  Hits inside an instance carry Ng in the instance's LOCAL space; a world-space normal is the transposed
+ * linear part of this matrix applied to Ng.  With one time step it is the inverse of the transform set; with more it is
+ * inverse(lerp(step[itime], step[itime + 1], ftime)), where rtcGetGeometryTransform(time) returns the lerp itself.
+ * A singular transform gives an all-zero matrix (such an instance is not entered).  Errors: RTC_ERROR_INVALID_ARGUMENT for a
+ * null handle or pointer or a format that is no transform format, RTC_ERROR_INVALID_OPERATION for a geometry that is no
+ * instance. */
+RTC_API void rtcamdGetGeometryWorld2Local(RTCGeometry geometry, float time, enum RTCFormat format, void* xfm);
+
 /* Extra readable properties for rtcGetDeviceProperty (cast to enum RTCDeviceProperty; the values lie inside that
  * enum's range and above every value the reference defines): counters of the call
  * combiner.  Host-pointer calls of up to 1024 rays (rtcIntersect1, rtcOccluded1, short 1M streams) issued

@@ -8,7 +8,8 @@
 //                            or TriMBRecord[] (96-byte motion-blur triangle records, leaf-contiguous) for triangle meshes with time steps,
 //                            or QuadMBRecord[] (128-byte motion-blur quad records, leaf-contiguous) for quad meshes with time steps,
 //                            or InstanceRecord[] (64-byte instance records, one per top-level leaf) for instances, followed in
-//                            the kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER by the instanced scenes' QuadRecord[]
+//                            the kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER by the instanced scenes' QuadRecord[], in the kinds
+//                            ACCEL_INSTMESHMB_* also by InstanceSceneRecord[], TriMBRecord[] and QuadMBRecord[] (see InstanceRecord)
 // The reference keeps the same information behind 64-bit tagged pointers (kernels/bvh/bvh.h:150-396,
 // AlignedNode :433-594, QuantizedNode :1150-1324, Triangle4v kernels/geometry/trianglev.h:24-162).
 #pragma once
@@ -166,6 +167,21 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // records above); the record's world2local is the inverse of step 0 as the static path computes it and is not used by the kernel.
 // An instance with one time step in such a scene has pad[1] == 0 and is entered through its record exactly as in the static kinds.
 // The top-level box of a moving instance is the union over its steps of the transformed scene bounds.
+//
+// Kinds ACCEL_INSTMESHMB_PLUECKER / _MOELLER: at least one instanced scene has a motion-blur accel (triangle or quad meshes with time
+// steps).  One general layout, whatever else the scenes hold (quads and instance steps are always allowed).  Per distinct instanced
+// scene, stored once, in the order of first use, its up to four trees in Scene::commit's order:
+//   nodes : top-level tree | scene 0: triangle, MB triangle, quad, MB quad nodes | scene 1: ... | ...          (child indices rebased)
+//   prims : scene 0's TriRecords | scene 1's | ...
+//   blobs : the N InstanceRecords | the QuadRecords | the InstanceSteps | one InstanceSceneRecord per scene |
+//           zero padding to a multiple of 96 bytes | scene 0's TriMBRecords | scene 1's | ... |
+//           zero padding to a multiple of 128 bytes | scene 0's QuadMBRecords | scene 1's | ...
+// `root` of an InstanceRecord is the index, in 64-byte units from the start of `blobs`, of its scene's InstanceSceneRecord, which holds
+// the four rebased roots (REF_EMPTY for a tree the scene does not have); pad[0] is zero, pad[1] as in the kinds ACCEL_INSTMB_*.
+// A motion-blur triangle leaf is rebased by (byte offset of the TriMBRecord section) / 96 + the scene's base, a motion-blur quad leaf by
+// (byte offset of the QuadMBRecord section) / 128 + the scene's base: the kernel indexes `blobs` as ONE array of that record type.
+// Every rebased first record must stay below 2^26.  Inside an instance the trees are traversed one after the other, each against the
+// tfar the previous one left; while a tree is traversed the later ones wait on the stack as markers (REF_INST_TREE).
 struct alignas(16) InstanceRecord
 {
   float world2local[12]; // vx.xyz, vy.xyz, vz.xyz, p.xyz
@@ -189,6 +205,20 @@ static const uint32_t REF_INST_EXIT = 0x80000000u;
 // and quads, with the quad root in the entry's distance word; popping it continues in the quad tree.  Leaf-flagged with count 0 too.
 static const uint32_t REF_INST_QUADS = 0x80000001u;
 static_assert(sizeof(InstanceRecord) == sizeof(QuadRecord), "the instance kernel indexes InstanceRecords and QuadRecords as one array");
+// The roots of one instanced scene (kinds ACCEL_INSTMESHMB_*), 64 bytes, of which the kernel loads the first dwordx4.  INST_TREE_*: the
+// code of a tree = of the leaf kind the lane runs while it is in that tree; roots[] is in visiting order.
+enum : uint32_t { INST_TREE_TRI = 0, INST_TREE_QUAD = 1, INST_TREE_TRIMB = 2, INST_TREE_QUADMB = 3 };
+struct alignas(16) InstanceSceneRecord
+{
+  uint32_t triRoot, triMBRoot, quadRoot, quadMBRoot; // rebased root references, REF_EMPTY for a missing tree
+  uint32_t pad[12];                                  // zero
+};
+static_assert(sizeof(InstanceSceneRecord) == sizeof(InstanceRecord), "the instance kernel indexes InstanceRecords and InstanceSceneRecords as one array");
+// Markers of the kernel's MESHMB form, one value per pending tree: REF_INST_TREE(code), stacked above the exit marker in reverse
+// visiting order with the tree's root in the distance word; popping one switches the lane's leaf kind to `code` and continues at that
+// root.  REF_INST_TREE(INST_TREE_QUAD) is REF_INST_QUADS; the triangle tree is always the first one and never waits.
+inline constexpr uint32_t REF_INST_TREE(uint32_t code) { return 0x80000000u + code; }
+static_assert(REF_INST_TREE(INST_TREE_QUAD) == REF_INST_QUADS, "the quad tree's marker is the one of the QUADS form");
 
 // ---- eager subdivision leaf: one 3x3-vertex cell (2x2 quads = 8 triangles), 160 bytes = 10 x dwordx4 ------
 // Replaces the inner leaves of GridSOA (kernels/geometry/grid_soa.h:267-286, :85-90): the reference stores whole
@@ -282,16 +312,19 @@ enum AccelKind : uint32_t
   ACCEL_INSTMB_TRI_PLUECKER = 18,
   ACCEL_INSTMB_TRI_MOELLER = 19,
   ACCEL_INSTMB_PLUECKER = 20,
-  ACCEL_INSTMB_MOELLER = 21
+  ACCEL_INSTMB_MOELLER = 21,
+  // at least one instanced scene holds meshes with time steps: one general layout (quads and instance steps allowed), see InstanceRecord
+  ACCEL_INSTMESHMB_PLUECKER = 22,
+  ACCEL_INSTMESHMB_MOELLER = 23
 };
-inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTMB_MOELLER; } // traced by trace_instance.hip
+inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTMESHMB_MOELLER; } // traced by trace_instance.hip / trace_instance_mesh_mb.hip
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
 {
   const QNode8* nodes;
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[])
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind

@@ -38,7 +38,7 @@ void Device::parse(const std::string& cfg)
     if (key == "tri_accel" || key == "accel") tri_accel = val;
     else if (key == "subdiv_accel") subdiv_accel = val;
     else if (key == "quad_accel") { quad_accel = val; quadAccelNamed = true; }
-    else if (key == "tri_accel_mb") tri_accel_mb = val;
+    else if (key == "tri_accel_mb") { tri_accel_mb = val; triAccelMBNamed = true; }
     else if (key == "quad_accel_mb") { quad_accel_mb = val; quadAccelMBNamed = true; }
     else if (key == "inst_accel") { inst_accel = val; instAccelNamed = true; }
     else if (key == "verbose") verbose = atoi(val.c_str());

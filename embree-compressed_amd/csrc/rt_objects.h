@@ -33,6 +33,7 @@ struct Device : RefCounted
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
+  bool triAccelMBNamed = false; // "tri_accel_mb=" given (with inst_accel=: a host-only device takes motion-blur meshes inside an instanced scene, inst_mesh_motion_enabled())
   bool quadAccelNamed = false; // "quad_accel=" given (a host-only device takes quad geometry only then, quads_enabled())
   int verbose = 0;
   int gpu = 0;            // HIP device ordinal ("gpu=" key; falls back to env RTAMD_GPU, LOCAL_RANK is NOT read here)
@@ -218,6 +219,9 @@ struct Device : RefCounted
   // Instances with more than one time step, the same rule: a host-only device whose config does not name inst_accel= refuses them at
   // commit, as before the instance accel took them.
   bool inst_motion_enabled() const { return gpu >= 0 || instAccelNamed; }
+  // Triangle and quad meshes with time steps inside an instanced scene: a host-only device takes them only when its config names
+  // inst_accel= and at least one of tri_accel_mb= / quad_accel_mb=; under any other config it refuses them as before.
+  bool inst_mesh_motion_enabled() const { return gpu >= 0 || (instAccelNamed && (triAccelMBNamed || quadAccelMBNamed)); }
   bool tuneBlocksAuto = true; // no RTAMD_BLOCKS_PER_CU given: 2 workgroups per CU, 1 when >= 2 batches run on other streams
   void memoryMonitor(ssize_t bytes, bool post);
 };

@@ -598,6 +598,20 @@ static V3 xfm_point(const float* m, V3 q)
 // and the lerp of two affine maps sends a point to the lerp of its images, so the union of the steps' boxes holds the object at every
 // time - one box swept over the whole shutter, like the motion-blur mesh accels.  A host-only device takes
 // such instances under the rule of quads (Device::inst_motion_enabled).
+// Motion-blur meshes below an instance: as soon as one instanced scene has a traceable motion-blur accel (triangle or quad meshes with
+// time steps) the kinds are ACCEL_INSTMESHMB_* and the layout is the general one of accel.h InstanceRecord: all four trees of every
+// distinct scene behind the top-level tree, the roots in one InstanceSceneRecord per scene, the TriMBRecords and QuadMBRecords in
+// sections of their own at the end of `blobs`.  The instanced scenes' bounds cover their moving meshes at every time (build_mb_bvh8
+// extends them by the swept boxes).  A host-only device takes such scenes only when its config names inst_accel= and one of
+// tri_accel_mb= / quad_accel_mb= (Device::inst_mesh_motion_enabled); a top scene without a motion-blur accel below it keeps the kinds
+// 14..21 and their arrays.
+// maxDepth (launch_on reserves 7 * (maxDepth + 1) + 2 stack entries) =
+//     the top-level depth
+//   + 1 for the exit marker
+//   + the largest number of pending-tree markers any instanced scene can have stacked at once (its tree count - 1, at most 3; in the
+//     kinds 14..21: 1 as soon as any scene has quads)
+//   + the deepest of all instanced trees (the trees of a scene are never stacked together: a marker is popped only when the entries
+//     of the tree before it are gone).
 // First InstanceStep a record may name, in 64-byte units from the start of `blobs`, exclusive: 24 bits beside the segment count.
 static const size_t INSTANCE_FIRST_STEP_LIMIT = (size_t)1 << 24;
 static void build_instance_accel(Scene* s)
@@ -608,11 +622,16 @@ static void build_instance_accel(Scene* s)
   const bool quadsOk = s->device->inst_quads_enabled();
   const char* const onlyTris = "an instanced scene may hold static triangle meshes only (no quads, time steps, subdivision meshes or instances)";
   const char* const onlyStatic = "an instanced scene may hold static triangle and quad meshes only (no time steps, subdivision meshes or instances)";
-  const char* const only = quadsOk ? onlyStatic : onlyTris;
+  const bool meshMotionOk = s->device->inst_mesh_motion_enabled(); // implies quadsOk
+  const char* const onlyMeshes = "an instanced scene may hold triangle and quad meshes only (no subdivision meshes or instances)";
+  const char* const only = meshMotionOk ? onlyMeshes : quadsOk ? onlyStatic : onlyTris;
   struct Src { unsigned geomID; Scene* scene; };
   std::vector<Src> src;
   std::vector<BuildPrim> bp;
-  bool haveKind = false, pluecker = false, anyQuads = false, anyMotion = false;
+  bool haveKind = false, pluecker = false, anyQuads = false, anyMotion = false, anyMeshMotion = false;
+  uint32_t pendingMax = 0; // most trees of one instanced scene, minus one
+  unsigned kindGeom = 0;   // the instance whose scene fixed the arithmetic, and the accels that scene has: for the refusal below
+  std::string kindNames;
   for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
     Geometry* g = s->geometries[gid];
     if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_INSTANCE) continue;
@@ -623,23 +642,57 @@ static void build_instance_accel(Scene* s)
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
       const bool mesh = og->type == RTC_GEOMETRY_TYPE_TRIANGLE || (quadsOk && og->type == RTC_GEOMETRY_TYPE_QUAD);
-      if (!mesh || og->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
+      if (!mesh || (og->timeSteps != 1 && !meshMotionOk)) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
       if (og->intersectFilter || og->occludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
     }
     for (const Accel* oa : o->accels())
-      if (oa != &o->triAccel && !(quadsOk && oa == &o->quadAccel) && oa->kind != ACCEL_NONE) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
+      if (oa != &o->triAccel && !(quadsOk && oa == &o->quadAccel) && !(meshMotionOk && (oa == &o->triMBAccel || oa == &o->quadMBAccel)) && oa->kind != ACCEL_NONE)
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
     if (o->triIntersectFilter || o->triOccludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
     const bool tris = o->triAccel.traceable(), quads = o->quadAccel.traceable();
-    if (!tris && !quads) continue; // empty scene: nothing to hit
+    const bool trisMB = o->triMBAccel.traceable(), quadsMB = o->quadMBAccel.traceable();
+    if (!tris && !quads && !trisMB && !quadsMB) continue; // empty scene: nothing to hit
+    std::string names; // this scene's traceable accels
+    for (const char* nm : {tris ? "triangle" : "", trisMB ? "motion blur triangle" : "", quads ? "quad" : "", quadsMB ? "motion blur quad" : ""})
+      if (*nm) names += std::string(names.empty() ? "" : ", ") + nm;
+    // scenes that disagree while a motion-blur accel is involved: the message names the accels on either side
+    auto disagree = [&](bool thisPl) {
+      const char* const ar[2] = {"Moeller / fast", "Pluecker / robust"};
+      return "the instanced scenes of one scene disagree in accel kind (Pluecker / robust and Moeller / fast): the scene of instance " + std::to_string(gid) + " has " +
+             ar[thisPl] + " accels (" + names + "), the scene of instance " + std::to_string(kindGeom) + " " + ar[!thisPl] + " ones (" + kindNames + "): instances need one arithmetic";
+    };
+    if (trisMB || quadsMB) {
+      // one arithmetic per top scene, over all four trees of every instanced scene
+      struct { bool have, pl; const char* name; } const t[4] = {{tris, o->triAccel.kind == ACCEL_TRI_PLUECKER, "triangle"},
+                                                                {trisMB, o->triMBAccel.kind == ACCEL_TRIMB_PLUECKER, "motion blur triangle"},
+                                                                {quads, o->quadAccel.kind == ACCEL_QUAD_PLUECKER, "quad"},
+                                                                {quadsMB, o->quadMBAccel.kind == ACCEL_QUADMB_PLUECKER, "motion blur quad"}};
+      std::string pl, mo;
+      for (const auto& e : t)
+        if (e.have) (e.pl ? pl : mo) += std::string((e.pl ? pl : mo).empty() ? "" : ", ") + e.name;
+      if (!pl.empty() && !mo.empty())
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "the accels of an instanced scene disagree in kind (Pluecker / robust: " + pl + "; Moeller / fast: " + mo + "): instances need one arithmetic");
+      const bool scenePl = !pl.empty();
+      if (haveKind && scenePl != pluecker) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(scenePl));
+      anyMeshMotion = true;
+    }
+    pendingMax = std::max(pendingMax, (uint32_t)tris + (uint32_t)trisMB + (uint32_t)quads + (uint32_t)quadsMB - 1u);
     // the kernel runs ONE arithmetic on both levels and in both leaves: every accel below this scene is Pluecker / robust, or every one
     // Moeller / fast
     if (tris && quads && (o->triAccel.kind == ACCEL_TRI_PLUECKER) != (o->quadAccel.kind == ACCEL_QUAD_PLUECKER))
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "the triangle and quad accels of an instanced scene disagree in kind (Pluecker / robust triangles beside Moeller / fast quads, "
                                             "as a robust scene under quad_accel=bvh8.quad4v builds them): instances need one arithmetic");
-    const bool pl = tris ? o->triAccel.kind == ACCEL_TRI_PLUECKER : o->quadAccel.kind == ACCEL_QUAD_PLUECKER;
+    const bool pl = tris ? o->triAccel.kind == ACCEL_TRI_PLUECKER
+                  : quads ? o->quadAccel.kind == ACCEL_QUAD_PLUECKER
+                  : trisMB ? o->triMBAccel.kind == ACCEL_TRIMB_PLUECKER : o->quadMBAccel.kind == ACCEL_QUADMB_PLUECKER;
     if (haveKind && pl != pluecker) {
-      if (!anyQuads && !quads) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
+      if (!anyQuads && !quads && !anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
+      if (anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(pl));
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in accel kind (Pluecker / robust and Moeller / fast): instances need one arithmetic");
+    }
+    if (!haveKind) {
+      kindGeom = gid;
+      kindNames = names;
     }
     haveKind = true;
     pluecker = pl;
@@ -675,7 +728,8 @@ static void build_instance_accel(Scene* s)
   A.root = r.root;
   A.leafCount = r.leafCount;
 
-  // the distinct instanced scenes' trees behind it, rebased: the triangle tree, then (anyQuads) the quad tree
+  // the distinct instanced scenes' trees behind it, rebased: the triangle tree, then (anyQuads) the quad tree; with anyMeshMotion all
+  // four trees in Scene::commit's order
   struct Roots { uint32_t tri, quad; };
   std::map<Scene*, Roots> rootsOf;
   std::vector<QuadRecord> quadRecs;
@@ -697,17 +751,52 @@ static void build_instance_accel(Scene* s)
     deepest = std::max(deepest, O.maxDepth);
     return rebase(O.root);
   };
+  // ACCEL_INSTMESHMB_*: where the sections of `blobs` start follows from the counts of everything in front of them
+  std::vector<InstanceSceneRecord> sceneRecs;
+  std::map<Scene*, uint32_t> sceneRecOf; // -> index into sceneRecs
+  std::vector<TriMBRecord> triMBRecs;
+  std::vector<QuadMBRecord> quadMBRecs;
+  size_t numSteps = 0, sceneRecBase = 0, triMBOffset = 0, quadMBOffset = 0; // sceneRecBase in 64-byte units, the offsets in bytes
+  if (anyMeshMotion) {
+    size_t nQuads = 0, nTriMB = 0, nScenes = 0;
+    std::map<Scene*, int> seen;
+    for (const Src& sr : src) {
+      const size_t n = s->geometries[sr.geomID]->local2world.size();
+      if (n > 1) numSteps += n;
+      if (seen[sr.scene]++) continue;
+      nScenes++;
+      if (sr.scene->quadAccel.traceable()) nQuads += sr.scene->quadAccel.blobs.size() / sizeof(QuadRecord);
+      if (sr.scene->triMBAccel.traceable()) nTriMB += sr.scene->triMBAccel.blobs.size() / sizeof(TriMBRecord);
+    }
+    sceneRecBase = recs.size() + nQuads + numSteps;
+    triMBOffset = ((sceneRecBase + nScenes) * sizeof(InstanceRecord) + sizeof(TriMBRecord) - 1) / sizeof(TriMBRecord) * sizeof(TriMBRecord);
+    quadMBOffset = (triMBOffset + nTriMB * sizeof(TriMBRecord) + sizeof(QuadMBRecord) - 1) / sizeof(QuadMBRecord) * sizeof(QuadMBRecord);
+  }
   for (const Src& sr : src) {
     if (rootsOf.count(sr.scene)) continue;
     Roots roots;
+    InstanceSceneRecord sc;
+    memset(&sc, 0, sizeof(sc));
     const Accel& O = sr.scene->triAccel;
     const size_t primBase = A.prims.size();
     if (primBase + O.prims.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced triangles for the 26-bit leaf reference");
     roots.tri = append_tree(O, primBase);
     if (O.traceable()) A.prims.insert(A.prims.end(), O.prims.begin(), O.prims.end());
+    sc.triMBRoot = REF_EMPTY;
+    const Accel& TM = sr.scene->triMBAccel;
+    if (anyMeshMotion && TM.traceable()) {
+      // motion-blur triangle leaves index `blobs` as one array of 96-byte records
+      const size_t n = TM.blobs.size() / sizeof(TriMBRecord), base = triMBOffset / sizeof(TriMBRecord) + triMBRecs.size();
+      if (base + n >= ((size_t)1 << TRI_START_BITS))
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced motion blur triangle segments for the 26-bit leaf reference (their records follow the instance, quad, step and "
+                                              "scene records in one array)");
+      sc.triMBRoot = append_tree(TM, base);
+      const TriMBRecord* t = (const TriMBRecord*)TM.blobs.data();
+      triMBRecs.insert(triMBRecs.end(), t, t + n);
+    }
     roots.quad = REF_EMPTY;
     const Accel& Q = sr.scene->quadAccel;
-    if (anyQuads && Q.traceable()) {
+    if ((anyQuads || anyMeshMotion) && Q.traceable()) {
       // quad leaves index `blobs` as one array of 64-byte records: the instance records, then every scene's quads
       const size_t nq = Q.blobs.size() / sizeof(QuadRecord), quadBase = recs.size() + quadRecs.size();
       if (quadBase + nq >= ((size_t)1 << TRI_START_BITS))
@@ -716,7 +805,24 @@ static void build_instance_accel(Scene* s)
       const QuadRecord* q = (const QuadRecord*)Q.blobs.data();
       quadRecs.insert(quadRecs.end(), q, q + nq);
     }
+    sc.quadMBRoot = REF_EMPTY;
+    const Accel& QM = sr.scene->quadMBAccel;
+    if (anyMeshMotion && QM.traceable()) {
+      // motion-blur quad leaves index `blobs` as one array of 128-byte records
+      const size_t n = QM.blobs.size() / sizeof(QuadMBRecord), base = quadMBOffset / sizeof(QuadMBRecord) + quadMBRecs.size();
+      if (base + n >= ((size_t)1 << TRI_START_BITS))
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced motion blur quad segments for the 26-bit leaf reference (their records follow all other records in one array)");
+      sc.quadMBRoot = append_tree(QM, base);
+      const QuadMBRecord* q = (const QuadMBRecord*)QM.blobs.data();
+      quadMBRecs.insert(quadMBRecs.end(), q, q + n);
+    }
     rootsOf[sr.scene] = roots;
+    if (anyMeshMotion) {
+      sc.triRoot = roots.tri;
+      sc.quadRoot = roots.quad;
+      sceneRecOf[sr.scene] = (uint32_t)sceneRecs.size();
+      sceneRecs.push_back(sc);
+    }
   }
   std::vector<InstanceStep> steps; // of the moving instances, in record order, behind the quad records
   for (size_t i = 0; i < order.size(); i++) {
@@ -727,7 +833,8 @@ static void build_instance_accel(Scene* s)
     if (!invert_affine(g->local2world[0].data(), rec.world2local)) memset(rec.world2local, 0, sizeof(rec.world2local)); // singular: never hit
     rec.geomID = sr.geomID;
     rec.root = rootsOf[sr.scene].tri;
-    if (anyQuads) rec.pad[0] = rootsOf[sr.scene].quad;
+    if (anyMeshMotion) rec.root = (uint32_t)sceneRecBase + sceneRecOf[sr.scene]; // its InstanceSceneRecord, in 64-byte units from the start of `blobs`
+    else if (anyQuads) rec.pad[0] = rootsOf[sr.scene].quad;
     if (g->local2world.size() > 1) {
       const size_t firstStep = recs.size() + quadRecs.size() + steps.size();
       if (firstStep >= INSTANCE_FIRST_STEP_LIMIT)
@@ -741,7 +848,8 @@ static void build_instance_accel(Scene* s)
       }
     }
   }
-  if (anyMotion) A.kind = anyQuads ? (pluecker ? ACCEL_INSTMB_PLUECKER : ACCEL_INSTMB_MOELLER) : (pluecker ? ACCEL_INSTMB_TRI_PLUECKER : ACCEL_INSTMB_TRI_MOELLER);
+  if (anyMeshMotion) A.kind = pluecker ? ACCEL_INSTMESHMB_PLUECKER : ACCEL_INSTMESHMB_MOELLER;
+  else if (anyMotion) A.kind = anyQuads ? (pluecker ? ACCEL_INSTMB_PLUECKER : ACCEL_INSTMB_MOELLER) : (pluecker ? ACCEL_INSTMB_TRI_PLUECKER : ACCEL_INSTMB_TRI_MOELLER);
   else if (anyQuads) A.kind = pluecker ? ACCEL_INST_PLUECKER : ACCEL_INST_MOELLER;
   else A.kind = pluecker ? ACCEL_INST_TRI_PLUECKER : ACCEL_INST_TRI_MOELLER;
   A.robust = pluecker ? 1 : 0;
@@ -749,9 +857,15 @@ static void build_instance_accel(Scene* s)
   // tree.  With quads a ray in a triangle tree has the marker of the pending quad tree stacked as well - one more entry, counted as a
   // level - and the deepest tree is the deeper of all triangle and quad trees (the two trees of a scene are never stacked together:
   // the quad marker is popped only when the triangle tree's entries are gone).
-  A.maxDepth = r.maxDepth + 1u + (anyQuads ? 1u : 0u) + deepest;
+  A.maxDepth = r.maxDepth + 1u + (anyMeshMotion ? pendingMax : anyQuads ? 1u : 0u) + deepest;
   A.blobStride = sizeof(InstanceRecord);
-  A.blobs.resize((recs.size() + quadRecs.size() + steps.size()) * sizeof(InstanceRecord));
+  A.blobs.assign(anyMeshMotion ? quadMBOffset + quadMBRecs.size() * sizeof(QuadMBRecord) : (recs.size() + quadRecs.size() + steps.size()) * sizeof(InstanceRecord), 0);
+  if (anyMeshMotion) {
+    if (recs.size() + quadRecs.size() + steps.size() != sceneRecBase) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: record counts");
+    memcpy(A.blobs.data() + sceneRecBase * sizeof(InstanceRecord), sceneRecs.data(), sceneRecs.size() * sizeof(InstanceSceneRecord));
+    if (!triMBRecs.empty()) memcpy(A.blobs.data() + triMBOffset, triMBRecs.data(), triMBRecs.size() * sizeof(TriMBRecord));
+    if (!quadMBRecs.empty()) memcpy(A.blobs.data() + quadMBOffset, quadMBRecs.data(), quadMBRecs.size() * sizeof(QuadMBRecord));
+  }
   memcpy(A.blobs.data(), recs.data(), recs.size() * sizeof(InstanceRecord));
   if (!quadRecs.empty()) memcpy(A.blobs.data() + recs.size() * sizeof(InstanceRecord), quadRecs.data(), quadRecs.size() * sizeof(QuadRecord));
   if (!steps.empty()) memcpy(A.blobs.data() + (recs.size() + quadRecs.size()) * sizeof(InstanceRecord), steps.data(), steps.size() * sizeof(InstanceStep));
@@ -806,9 +920,24 @@ void Scene::commit()
               quadMBAccel.nodes.size() * sizeof(QNode8), quadMBAccel.blobs.size() / sizeof(QuadMBRecord), quadMBAccel.blobs.size(), quadMBAccel.maxDepth);
   }
   if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
-    fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, %zu instanced quads, depth %u\n", instAccel.kind,
+  {
+    size_t nTriMB = 0, nQuadMB = 0, nQuads = instAccel.blobs.size() / sizeof(InstanceRecord) - instAccel.leafCount; // (kinds ACCEL_INSTMB_*: quads and InstanceSteps)
+    // kinds ACCEL_INSTMESHMB_*: `blobs` holds more kinds of records and padding, so the records of the distinct instanced scenes are counted
+    if (instAccel.kind == ACCEL_INSTMESHMB_PLUECKER || instAccel.kind == ACCEL_INSTMESHMB_MOELLER) {
+      std::map<Scene*, int> seen;
+      nQuads = 0;
+      for (Geometry* geo : geometries)
+        if (geo && geo->enabled && geo->type == RTC_GEOMETRY_TYPE_INSTANCE && geo->instScene && !seen[geo->instScene]++) {
+          if (geo->instScene->quadAccel.traceable()) nQuads += geo->instScene->quadAccel.blobs.size() / sizeof(QuadRecord);
+          if (geo->instScene->triMBAccel.traceable()) nTriMB += geo->instScene->triMBAccel.blobs.size() / sizeof(TriMBRecord);
+          if (geo->instScene->quadMBAccel.traceable()) nQuadMB += geo->instScene->quadMBAccel.blobs.size() / sizeof(QuadMBRecord);
+        }
+    }
+    fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, %zu instanced quads, %zu instanced motion blur triangle "
+                    "segment records, %zu instanced motion blur quad segment records, depth %u\n", instAccel.kind,
             instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),
-            instAccel.blobs.size() / sizeof(InstanceRecord) - instAccel.leafCount, instAccel.maxDepth); // (kinds ACCEL_INSTMB_*: quads and InstanceSteps)
+            nQuads, nTriMB, nQuadMB, instAccel.maxDepth);
+  }
   modified = false;
 }
 

@@ -1,0 +1,51 @@
+// Motion-blur triangle and quad meshes below an instance (accel kinds ACCEL_INSTMESHMB_PLUECKER / ACCEL_INSTMESHMB_MOELLER): the MESHMB
+// form of the two-level kernel of trace_instance.hip, in a unit of its own so that its eight instantiations compile beside the others.
+// An instanced scene may hold up to four trees - static triangles, motion-blur triangles, static quads, motion-blur quads - which the
+// local ray traverses completely, one after the other, in Scene::commit's order, each against the tfar the one before left (the
+// instanced scene's AccelN, scene.cpp:650-654; instance_intersector.cpp:51-62 passes ray.time on unchanged), so a later tree's hit at a
+// bit-identical t replaces the earlier one:
+//   2". the instance's record names the scene's InstanceSceneRecord (accel.h) with the four roots.  Above the exit marker the lane
+//       stacks one marker per pending tree, REF_INST_TREE(code) with the tree's root in the distance word, in reverse visiting order,
+//       and continues at the root of the first tree the scene has; two state bits hold the code of the tree it is in;
+//   3". popping such a marker - recognised before the distance cull - sets the two bits to its code and continues at its root.  A
+//       leaf is then, by the code, the block loop of TriLeaf / QuadLeaf (as in the QUADS form) or that of TriMBLeaf::intersect /
+//       QuadMBLeaf::intersect (trace_tri_mb.hip, trace_quad_mb.hip) restated over time_segment, lerp_vertex and the static tests: the
+//       ray's time is read from the ray record through the ray's index (the same value in world and local space), a record is tested
+//       only when its segment is the ray's itime, blocks are 4 records, all candidates of a block see the tfar at block entry, the
+//       lowest lane wins ties, a later block replaces an equal t, quads split into A = (v0, v1, v3) and B = (v2, v1, v3).  The
+//       TriMBRecords and QuadMBRecords lie in sections of `blobs` that start at multiples of their sizes; the leaf references are
+//       rebased so that `blobs` is indexed as one array of that record type;
+//   4". the exit marker clears the bits.
+// Instance steps (XFMB) and the leaf-batching rule (leafBatch / nodeWork, over all four leaf kinds together) are those of the other forms.
+// Node boxes of the motion-blur trees are the swept boxes of the motion-blur accels.
+#include "trace_instance.hip.h"
+
+namespace rtamd {
+namespace dev {
+
+template <bool PLUECKER, bool OCCLUDED, bool VEC>
+__global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, true, true, true)) void trace_instance_mesh_mb_kernel(LaunchParams P)
+{
+  constexpr bool QUADS = true, XFMB = true, MESHMB = true; // always the general layout: quads and instance steps allowed
+#include "trace_instance_body.hip.h"
+}
+
+template <bool PLUECKER, bool OCCLUDED>
+inline hipError_t launch_instance_mesh_mb_vec(const LaunchParams& p, hipStream_t stream)
+{
+  return launch_instance_pair<trace_instance_mesh_mb_kernel<PLUECKER, OCCLUDED, true>, trace_instance_mesh_mb_kernel<PLUECKER, OCCLUDED, false>>(p, stream);
+}
+
+} // namespace dev
+
+hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream)
+{
+  if (p.counters) return hipErrorInvalidValue; // no instrumented twin (rt_trace.cpp refuses counted batches on scenes with instances)
+  switch (p.accel.kind) {
+  case ACCEL_INSTMESHMB_PLUECKER: return p.occluded ? dev::launch_instance_mesh_mb_vec<true, true>(p, stream) : dev::launch_instance_mesh_mb_vec<true, false>(p, stream);
+  case ACCEL_INSTMESHMB_MOELLER: return p.occluded ? dev::launch_instance_mesh_mb_vec<false, true>(p, stream) : dev::launch_instance_mesh_mb_vec<false, false>(p, stream);
+  default: return hipErrorInvalidValue;
+  }
+}
+
+} // namespace rtamd

@@ -36,6 +36,9 @@ RTC_FORMAT_FLOAT3 = 0x9003
 RTC_FORMAT_FLOAT3X4_ROW_MAJOR = 0x9134
 RTC_FORMAT_FLOAT3X4_COLUMN_MAJOR = 0x9234
 RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR = 0x9244
+# accel kinds of instance accels over scenes that hold meshes with time steps (csrc/accel.h AccelKind, RTCAMDSceneStats::accelKind)
+ACCEL_INSTMESHMB_PLUECKER = 22
+ACCEL_INSTMESHMB_MOELLER = 23
 RTC_SCENE_FLAG_NONE = 0
 RTC_SCENE_FLAG_ROBUST = 4
 RTC_ERROR_NONE, RTC_ERROR_UNKNOWN, RTC_ERROR_INVALID_ARGUMENT, RTC_ERROR_INVALID_OPERATION = 0, 1, 2, 3

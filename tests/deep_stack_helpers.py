@@ -351,10 +351,13 @@ def oracle_per_time(rtc, po, steps, idx, rays, mode, nthreads=8):
     return want, isb
 
 
-def quad_allowances(got, want, isb, mode, quad_gids=None):
+def quad_allowances(got, want, isb, mode, quad_gids=None, nonplanar=None):
     """The two allowances of test_bomberman_quads_1m_parity, applied to `want` in place before helpers.compare_hits: Moeller B-lane u / v
     within 4e-7 (the oracle maps after the division, the kernel before), and - capped at fewer than 1 % of the hits - the kernel's
-    normal for hits within 1e-4 of the v1-v3 diagonal, where A and B are hit within ulps and may be ranked the other way."""
+    normal for hits within 1e-4 of the v1-v3 diagonal, where A and B are hit within ulps and may be ranked the other way.
+    nonplanar: a mask of the non-planar quads, indexed by primID, or {geomID: such a mask} - the normal allowance (and its cap) then
+    covers hits on those quads only: the two split normals of a planar quad agree, whichever triangle wins.  Returns the number of
+    hits the normal allowance was applied to."""
     hit = want["geomID"] != INVALID
     if mode == 1:
         b = isb & hit & (got["geomID"] != INVALID)
@@ -364,6 +367,13 @@ def quad_allowances(got, want, isb, mode, quad_gids=None):
     diag = hit & (np.abs(want["u"].astype(np.float64) + want["v"] - 1.0) < 1e-4)
     if quad_gids is not None:
         diag &= np.isin(want["geomID"], np.asarray(quad_gids, np.uint32))
+    if nonplanar is not None:
+        masks = nonplanar if isinstance(nonplanar, dict) else {int(g): nonplanar for g in np.unique(want["geomID"][hit])}
+        bent = np.zeros(len(want), bool)
+        for g, mask in masks.items():
+            on = hit & (want["geomID"] == np.uint32(g))
+            bent[on] = np.asarray(mask, bool)[want["primID"][on]]
+        diag &= bent
     assert int(diag.sum()) < int(hit.sum()) // 100, int(diag.sum())
     for f in ("Ng_x", "Ng_y", "Ng_z"):
         want[f][diag] = got[f][diag]

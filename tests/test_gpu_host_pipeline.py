@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+import edge_rays_helpers as er
+
 pytestmark = pytest.mark.gpu
 
 
@@ -14,6 +16,8 @@ def _scene(rtc, cfg, bomberman, kind, env):
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)  # the knobs are read when the device is created
     try:
+        if kind in er.HOST_KINDS:
+            return er.host_scene(rtc, cfg, bomberman, kind)
         dev = rtc.Device(cfg + (",tri_accel=bvh8.triangle4v" if kind == "tri" else ",subdiv_accel=bvh4.compressed.leaf"))
     finally:
         for k, v in old.items():
@@ -35,7 +39,7 @@ def _scene(rtc, cfg, bomberman, kind, env):
 UNPIPELINED = {"RTAMD_PIPE_MIN": "2000000000"}
 
 
-@pytest.mark.parametrize("kind", ["tri", "cbvh.leaf"])
+@pytest.mark.parametrize("kind", ["tri", "cbvh.leaf", "quad.mb", "inst.meshmb"])
 @pytest.mark.parametrize("cfg,env", [("gpu=0", {"RTAMD_PIPE_MIN": "1", "RTAMD_PIPE_CHUNK": "4096"}),          # many small chunks
                                      ("gpu=0", {"RTAMD_PIPE_MIN": "1", "RTAMD_PIPE_CHUNK": "70000", "RTAMD_HOST_THREADS": "1"}),  # ragged last chunk, no helpers
                                      ("gpus=0:0:0", {"RTAMD_PIPE_MIN": "1", "RTAMD_PIPE_CHUNK": "30000", "RTAMD_HOST_THREADS": "5"}),  # three shards
@@ -43,12 +47,11 @@ UNPIPELINED = {"RTAMD_PIPE_MIN": "2000000000"}
 def test_pipelined_host_batches_equal_the_unpipelined_path(rtc, po, bomberman, kind, cfg, env):
     import torch
 
-    verts = bomberman[0]
-    lo, hi = verts.min(0), verts.max(0)
+    lo, hi = er.host_bounds(bomberman, kind)
     d0, s0 = _scene(rtc, "gpu=0", bomberman, kind, UNPIPELINED)
     d1, s1 = _scene(rtc, cfg, bomberman, kind, env)
     for n in (400_003, 4097, 3):
-        a = po.make_random_rays(n, lo, hi, seed=31)
+        a = er.host_rays(po, kind, n, lo, hi, seed=31)
         a["tnear"][::7] = 5.0
         a["tfar"][::7] = 1.0  # skipped rays (tnear > tfar) stay untouched
         b = a.copy()
@@ -61,7 +64,7 @@ def test_pipelined_host_batches_equal_the_unpipelined_path(rtc, po, bomberman, k
         if n > 100:
             assert int((a["geomID"] != 0xFFFFFFFF).sum()) > 0.08 * n
         # any hit, RTCRay records at a 96-byte pitch: the bytes between the records must not be touched
-        src = po.make_random_rays(n, lo, hi, seed=32)
+        src = er.host_rays(po, kind, n, lo, hi, seed=32)
         raw0 = np.full((n, 96), 0xA5, np.uint8)
         raw0[:, :48] = src.view(np.uint8).reshape(n, 80)[:, :48]
         raw1 = raw0.copy()

@@ -10,10 +10,14 @@ import threading
 import numpy as np
 import pytest
 
+import edge_rays_helpers as er
+
 pytestmark = pytest.mark.gpu
 
 
 def _scene(rtc, cfg, bomberman, kind):
+    if kind in er.HOST_KINDS:
+        return er.host_scene(rtc, cfg, bomberman, kind)
     verts, fs, fi = bomberman
     dev = rtc.Device(cfg + (",tri_accel=bvh8.triangle4v" if kind == "tri" else ",subdiv_accel=bvh4.compressed.leaf"))
     sc = rtc.Scene(dev)
@@ -26,15 +30,14 @@ def _scene(rtc, cfg, bomberman, kind):
     return dev, sc
 
 
-@pytest.mark.parametrize("kind", ["tri", "cbvh.leaf"])
+@pytest.mark.parametrize("kind", ["tri", "cbvh.leaf", "quad.mb", "inst.meshmb"])
 @pytest.mark.parametrize("gpus", ["gpus=0:0", "gpus=0:0:0"])
 def test_sharded_host_batch_matches_one_shard(rtc, po, bomberman, kind, gpus):
-    verts = bomberman[0]
-    lo, hi = verts.min(0), verts.max(0)
+    lo, hi = er.host_bounds(bomberman, kind)
     d1, s1 = _scene(rtc, "gpu=0", bomberman, kind)
     dn, sn = _scene(rtc, gpus, bomberman, kind)
     for n in (300_001, 5, 1):  # uneven split; fewer rays than 2 per shard -> one shard
-        a = po.make_random_rays(n, lo, hi, seed=21)
+        a = er.host_rays(po, kind, n, lo, hi, seed=21)
         b = a.copy()
         s1.intersect1M(a)
         sn.intersect1M(b)
@@ -42,7 +45,7 @@ def test_sharded_host_batch_matches_one_shard(rtc, po, bomberman, kind, gpus):
         if n > 100:
             assert int((a["geomID"] != 0xFFFFFFFF).sum()) > 0.1 * n
         # any hit, RTCRay records, strided (96-byte pitch)
-        src = po.make_random_rays(n, lo, hi, seed=22)
+        src = er.host_rays(po, kind, n, lo, hi, seed=22)
         raw1 = np.zeros((n, 96), np.uint8)
         raw1[:, :48] = src.view(np.uint8).reshape(n, 80)[:, :48]
         raw2 = raw1.copy()

@@ -182,6 +182,19 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // (byte offset of the QuadMBRecord section) / 128 + the scene's base: the kernel indexes `blobs` as ONE array of that record type.
 // Every rebased first record must stay below 2^26.  Inside an instance the trees are traversed one after the other, each against the
 // tfar the previous one left; while a tree is traversed the later ones wait on the stack as markers (REF_INST_TREE).
+//
+// Kinds ACCEL_INSTSUBDIV_GRID / ACCEL_INSTSUBDIV_CBVH_LEAF (Scene::instSubdivAccel, an accel of its own beside the one above): instances
+// of scenes that hold subdivision meshes only, all with the eager accel or all with bvh4.compressed.leaf at one compression level C.  Per
+// distinct instanced scene, stored once, in the order of first use:
+//   nodes : top-level tree | scene 0's subdivision BVH8 | scene 1's | ...                                   (child indices rebased)
+//   prims : empty
+//   blobs : the N InstanceRecords | the InstanceSteps | zero padding to a multiple of the blob stride | scene 0's leaf blobs | scene 1's | ...
+// The leaf blobs are GridCells (stride 160) or cBVH blobs (stride cbvh_stride(C, leaf mode), a multiple of 128); AccelDesc::blobStride is
+// that stride.  A subdivision leaf reference (REF_LEAF | blob index) is rebased by (byte offset of the blob section) / stride + the
+// scene's base, so that the leaf functions' own addressing, blobs + index * stride, finds the blob; the rebased index is at least 1 (the
+// records come first), so no leaf reference equals REF_INST_EXIT, and stays below 2^26.  `root` of an InstanceRecord is the rebased root
+// of its scene's tree, pad[0] is zero, pad[1] as in the kinds ACCEL_INSTMB_* (firstStep counts the InstanceRecords in front).
+// blobOffsets holds two words for inspection: the number of leaf blobs and the index of the first one.
 struct alignas(16) InstanceRecord
 {
   float world2local[12]; // vx.xyz, vy.xyz, vz.xyz, p.xyz
@@ -315,9 +328,13 @@ enum AccelKind : uint32_t
   ACCEL_INSTMB_MOELLER = 21,
   // at least one instanced scene holds meshes with time steps: one general layout (quads and instance steps allowed), see InstanceRecord
   ACCEL_INSTMESHMB_PLUECKER = 22,
-  ACCEL_INSTMESHMB_MOELLER = 23
+  ACCEL_INSTMESHMB_MOELLER = 23,
+  // instances of scenes that hold subdivision meshes only (Scene::instSubdivAccel, see InstanceRecord): one kind per leaf family; the
+  // compression level C of the cBVH blobs travels beside the accel (Accel::cbvhLevels -> LaunchParams::cbvhLevels)
+  ACCEL_INSTSUBDIV_GRID = 24,     // instanced scenes whose subdivision accel is ACCEL_GRIDSOA (eager): GridCells below the instances
+  ACCEL_INSTSUBDIV_CBVH_LEAF = 25 // instanced scenes whose subdivision accel is ACCEL_CBVH_LEAF, all at one C: cBVH blobs below the instances
 };
-inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTMESHMB_MOELLER; } // traced by trace_instance.hip / trace_instance_mesh_mb.hip
+inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF; } // traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc

@@ -36,7 +36,7 @@ void Device::parse(const std::string& cfg)
     }
     if (key.empty()) continue;
     if (key == "tri_accel" || key == "accel") tri_accel = val;
-    else if (key == "subdiv_accel") subdiv_accel = val;
+    else if (key == "subdiv_accel") { subdiv_accel = val; subdivAccelNamed = true; }
     else if (key == "quad_accel") { quad_accel = val; quadAccelNamed = true; }
     else if (key == "tri_accel_mb") { tri_accel_mb = val; triAccelMBNamed = true; }
     else if (key == "quad_accel_mb") { quad_accel_mb = val; quadAccelMBNamed = true; }

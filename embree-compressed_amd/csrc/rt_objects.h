@@ -35,6 +35,7 @@ struct Device : RefCounted
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
   bool triAccelMBNamed = false; // "tri_accel_mb=" given (with inst_accel=: a host-only device takes motion-blur meshes inside an instanced scene, inst_mesh_motion_enabled())
   bool quadAccelNamed = false; // "quad_accel=" given (a host-only device takes quad geometry only then, quads_enabled())
+  bool subdivAccelNamed = false; // "subdiv_accel=" given (with inst_accel=: a host-only device takes instances of subdivision scenes, inst_subdiv_enabled())
   int verbose = 0;
   int gpu = 0;            // HIP device ordinal ("gpu=" key; falls back to env RTAMD_GPU, LOCAL_RANK is NOT read here)
   int numThreads = 0;     // accepted, used only for host-side builders
@@ -222,6 +223,9 @@ struct Device : RefCounted
   // Triangle and quad meshes with time steps inside an instanced scene: a host-only device takes them only when its config names
   // inst_accel= and at least one of tri_accel_mb= / quad_accel_mb=; under any other config it refuses them as before.
   bool inst_mesh_motion_enabled() const { return gpu >= 0 || (instAccelNamed && (triAccelMBNamed || quadAccelMBNamed)); }
+  // Instances of scenes that hold subdivision meshes: a host-only device takes them only when its config names inst_accel= and
+  // subdiv_accel=; under any other config it refuses them as before.
+  bool inst_subdiv_enabled() const { return gpu >= 0 || (instAccelNamed && subdivAccelNamed); }
   bool tuneBlocksAuto = true; // no RTAMD_BLOCKS_PER_CU given: 2 workgroups per CU, 1 when >= 2 batches run on other streams
   void memoryMonitor(ssize_t bytes, bool post);
 };
@@ -334,6 +338,7 @@ struct Accel
   uint32_t robust = 0;
   uint32_t maxDepth = 0;
   uint32_t blobStride = 0;
+  uint32_t cbvhLevels = 0; // ACCEL_INSTSUBDIV_CBVH_LEAF: the compression level C of the instanced scenes' blobs (0: the scene's own level applies)
   size_t leafCount = 0;
   // device copies, one set per shard of the device (replicated accel)
   struct DevCopy
@@ -378,10 +383,11 @@ struct Scene : RefCounted
   Accel quadMBAccel; // quads with several time steps (QuadMBRecord[] in `blobs`); traced after the static quads, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
   Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle and quad trees behind the top-level tree); traced last (scene.cpp:661-665)
-  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / INST index whatever a path keeps per accel
-  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, INST = 5, NUM_ACCELS = 6 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &instAccel}; }
-  bool hasInstances() const { return instAccel.kind != ACCEL_NONE; }
+  Accel instSubdivAccel; // instances of scenes that hold subdivision meshes only (InstanceRecord[] and the instanced scenes' leaf blobs in `blobs`, their BVH8s behind the top-level tree); traced after the mesh instances
+  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / INST / INSTSUBDIV index whatever a path keeps per accel
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, INST = 5, INSTSUBDIV = 6, NUM_ACCELS = 7 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &instAccel, &instSubdivAccel}; }
+  bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
 
   explicit Scene(Device* d);
   ~Scene() override;

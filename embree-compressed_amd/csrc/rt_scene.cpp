@@ -189,6 +189,7 @@ void Accel::clear()
   root = REF_EMPTY;
   kind = ACCEL_NONE;
   maxDepth = 0;
+  cbvhLevels = 0;
   leafCount = 0;
 }
 
@@ -605,6 +606,9 @@ static V3 xfm_point(const float* m, V3 q)
 // extends them by the swept boxes).  A host-only device takes such scenes only when its config names inst_accel= and one of
 // tri_accel_mb= / quad_accel_mb= (Device::inst_mesh_motion_enabled); a top scene without a motion-blur accel below it keeps the kinds
 // 14..21 and their arrays.
+// Subdivision scenes below an instance: an instanced scene that enables a subdivision mesh is left to build_instance_subdiv_accel (a
+// second accel of the top scene; this one and its kinds stay what they are) when the device takes such scenes
+// (Device::inst_subdiv_enabled); otherwise it is refused here with the message of the config, as before.
 // maxDepth (launch_on reserves 7 * (maxDepth + 1) + 2 stack entries) =
 //     the top-level depth
 //   + 1 for the exit marker
@@ -614,16 +618,27 @@ static V3 xfm_point(const float* m, V3 q)
 //     of the tree before it are gone).
 // First InstanceStep a record may name, in 64-byte units from the start of `blobs`, exclusive: 24 bits beside the segment count.
 static const size_t INSTANCE_FIRST_STEP_LIMIT = (size_t)1 << 24;
+// The class of an instanced scene: a subdivision scene as soon as it enables a subdivision mesh (build_instance_subdiv_accel refuses
+// anything beside it), a mesh scene otherwise.
+static bool is_subdivision_scene(const Scene* o)
+{
+  for (const Geometry* og : o->geometries)
+    if (og && og->enabled && og->type == RTC_GEOMETRY_TYPE_SUBDIVISION) return true;
+  return false;
+}
 static void build_instance_accel(Scene* s)
 {
   Accel& A = s->instAccel;
   A.clear();
   if (s->device->inst_accel != "default") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown instance acceleration structure " + s->device->inst_accel);
   const bool quadsOk = s->device->inst_quads_enabled();
+  const bool subdivOk = s->device->inst_subdiv_enabled(); // implies quadsOk; scenes of subdivision meshes go to the second instance accel
   const char* const onlyTris = "an instanced scene may hold static triangle meshes only (no quads, time steps, subdivision meshes or instances)";
   const char* const onlyStatic = "an instanced scene may hold static triangle and quad meshes only (no time steps, subdivision meshes or instances)";
   const bool meshMotionOk = s->device->inst_mesh_motion_enabled(); // implies quadsOk
   const char* const onlyMeshes = "an instanced scene may hold triangle and quad meshes only (no subdivision meshes or instances)";
+  // (the wording is from before subdivision scenes could be instanced and is kept: on a device that takes them, "no subdivision meshes"
+  // reads "not beside meshes in one instanced scene" - a scene of subdivision meshes only never gets here)
   const char* const only = meshMotionOk ? onlyMeshes : quadsOk ? onlyStatic : onlyTris;
   struct Src { unsigned geomID; Scene* scene; };
   std::vector<Src> src;
@@ -639,6 +654,7 @@ static void build_instance_accel(Scene* s)
     Scene* o = g->instScene;
     if (!o) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance without an instanced scene");
     if (o->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instanced scene got not committed");
+    if (subdivOk && is_subdivision_scene(o)) continue; // build_instance_subdiv_accel places it
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
       const bool mesh = og->type == RTC_GEOMETRY_TYPE_TRIANGLE || (quadsOk && og->type == RTC_GEOMETRY_TYPE_QUAD);
@@ -871,6 +887,169 @@ static void build_instance_accel(Scene* s)
   if (!steps.empty()) memcpy(A.blobs.data() + (recs.size() + quadRecs.size()) * sizeof(InstanceRecord), steps.data(), steps.size() * sizeof(InstanceStep));
 }
 
+// Instances of subdivision scenes: the second instance accel of a scene (accel.h InstanceRecord, kinds ACCEL_INSTSUBDIV_*), laid out
+// like the first.  One node array holds the top-level BVH8 over the instances' world boxes (one instance per leaf; the box is the union
+// over the transform's time steps of xfmBounds(local2world, scene bounds), as above) and behind it the rebased subdivision BVH8 of every
+// distinct instanced scene; `blobs` holds the InstanceRecords, the InstanceSteps of moving instances, and - from a multiple of the blob
+// stride on - the leaf blobs of all instanced scenes, so that a rebased leaf reference indexes `blobs` the way the leaf functions of
+// the subdivision kernels do (GridCellLeaf::intersect, CbvhLeaf::intersect).  Two subdivision accels are placed: the eager default
+// (ACCEL_GRIDSOA) and bvh4.compressed.leaf at every compression level; the kernel is instantiated per leaf family and level, so all
+// instanced subdivision scenes of one top scene must agree in both (their tessellation levels may differ).  A host-only device takes
+// such instances only when its config names inst_accel= and subdiv_accel= (Device::inst_subdiv_enabled); otherwise
+// build_instance_accel refuses them as it always did.
+// maxDepth = the top-level depth + 1 for the exit marker + the deepest instanced tree.
+static void build_instance_subdiv_accel(Scene* s)
+{
+  Accel& A = s->instSubdivAccel;
+  A.clear();
+  A.robust = 1; // the subdivision accels traverse robustly, on both levels here
+  if (!s->device->inst_subdiv_enabled()) return;
+  struct Src { unsigned geomID; Scene* scene; };
+  std::vector<Src> src;
+  std::vector<BuildPrim> bp;
+  bool haveKind = false;
+  uint32_t leafKind = ACCEL_NONE, levels = 0;
+  unsigned kindGeom = 0;
+  auto type_name = [](RTCGeometryType t) -> const char* {
+    return t == RTC_GEOMETRY_TYPE_TRIANGLE ? "triangle mesh" : t == RTC_GEOMETRY_TYPE_QUAD ? "quad mesh" : t == RTC_GEOMETRY_TYPE_INSTANCE ? "instance" : "geometry of another type";
+  };
+  auto accel_name = [](uint32_t kind, uint32_t C) -> std::string {
+    return kind == ACCEL_GRIDSOA ? std::string("the eager accel") : "bvh4.compressed.leaf at compression level " + std::to_string(C);
+  };
+  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
+    Geometry* g = s->geometries[gid];
+    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_INSTANCE) continue;
+    Scene* o = g->instScene; // present and committed: build_instance_accel has looked at every instance
+    if (!o || !is_subdivision_scene(o)) continue;
+    for (const Geometry* og : o->geometries) {
+      if (!og || !og->enabled) continue;
+      if (og->type == RTC_GEOMETRY_TYPE_INSTANCE)
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene that enables subdivision meshes may hold nothing else: the scene of instance " + std::to_string(gid) +
+                                              " also enables an instance (instances below instances are not supported)");
+      if (og->type != RTC_GEOMETRY_TYPE_SUBDIVISION)
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene that enables subdivision meshes may hold nothing else: the scene of instance " + std::to_string(gid) +
+                                              " also enables a " + type_name(og->type));
+      if (og->intersectFilter || og->occludedFilter)
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "subdivision geometry with a filter function inside an instanced scene is not supported (instance " + std::to_string(gid) + ")");
+    }
+    const Accel& O = o->subdivAccel;
+    if (O.kind == ACCEL_CBVH_BOX || O.kind == ACCEL_CBVH_GRID || O.kind == ACCEL_CBVH_FULL)
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, std::string("subdiv_accel=bvh4.compressed.") + (O.kind == ACCEL_CBVH_BOX ? "box" : O.kind == ACCEL_CBVH_GRID ? "grid" : "full") +
+                                            " below an instance is not supported (the eager accel and bvh4.compressed.leaf are)");
+    if (!O.traceable()) continue; // nothing to hit
+    if (O.kind != ACCEL_GRIDSOA && O.kind != ACCEL_CBVH_LEAF) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: unknown subdivision accel kind");
+    const uint32_t C = O.kind == ACCEL_CBVH_LEAF ? o->compressionLevel : 0u;
+    if (haveKind && (O.kind != leafKind || C != levels))
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced subdivision scenes of one scene disagree in accel kind or compression level: the scene of instance " + std::to_string(gid) + " has " +
+                                            accel_name(O.kind, C) + ", the scene of instance " + std::to_string(kindGeom) + " " + accel_name(leafKind, levels) +
+                                            ": the instance kernel is instantiated per leaf kind and level");
+    if (!haveKind) kindGeom = gid;
+    haveKind = true;
+    leafKind = O.kind;
+    levels = C;
+    BuildPrim p;
+    const V3 c[2] = {o->bounds.lo, o->bounds.hi};
+    for (const Geometry::Xfm& step : g->local2world) // one step: xfmBounds; more: the union over the steps
+      for (int i = 0; i < 8; i++) p.box.extend(xfm_point(step.data(), V3(c[i >> 2].x, c[(i >> 1) & 1].y, c[i & 1].z)));
+    if (!(std::isfinite(p.box.lo.x) && std::isfinite(p.box.lo.y) && std::isfinite(p.box.lo.z) && std::isfinite(p.box.hi.x) && std::isfinite(p.box.hi.y) && std::isfinite(p.box.hi.z)))
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance transform yields bounds that are not finite");
+    p.id = (uint32_t)src.size();
+    src.push_back({gid, o});
+    bp.push_back(p);
+  }
+  if (bp.empty()) return;
+  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances for the 26-bit leaf reference");
+
+  // top-level tree, one instance per leaf: leaf reference = record index, count 1
+  std::vector<InstanceRecord> recs(bp.size());
+  std::vector<uint32_t> order; // record index -> src index, leaf order
+  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
+    if (end - begin != 1) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: a leaf must hold one instance");
+    order.push_back(prims[begin].id);
+    return make_tri_leaf((uint32_t)order.size() - 1u, 1u);
+  };
+  BuildSettings cfg;
+  cfg.blockSize = 1; cfg.minLeaf = 1; cfg.maxLeaf = 1;
+  cfg.threads = 1; // the leaf callback appends in leaf order
+  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
+  A.nodes = std::move(r.nodes);
+  A.root = r.root;
+  A.leafCount = r.leafCount;
+
+  // where the blob section starts follows from the counts in front of it
+  const size_t stride = src[0].scene->subdivAccel.blobStride;
+  size_t numSteps = 0;
+  for (const Src& sr : src) {
+    const size_t n = s->geometries[sr.geomID]->local2world.size();
+    if (n > 1) numSteps += n;
+  }
+  const size_t blobBase = ((recs.size() + numSteps) * sizeof(InstanceRecord) + stride - 1) / stride; // index of the first leaf blob
+  std::map<Scene*, uint32_t> rootOf;
+  std::vector<const Accel*> placed; // the distinct scenes' accels, in the order of their blobs
+  size_t numBlobs = 0;
+  uint32_t deepest = 0;
+  for (const Src& sr : src) {
+    if (rootOf.count(sr.scene)) continue;
+    const Accel& O = sr.scene->subdivAccel;
+    if (O.blobStride != stride || O.blobs.size() % stride != 0) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: blob strides");
+    const size_t n = O.blobs.size() / stride, leafBase = blobBase + numBlobs;
+    if (leafBase + n >= ((size_t)1 << TRI_START_BITS))
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced subdivision leaf blobs for the 26-bit leaf reference (the blobs follow the instance and step records in one array)");
+    const size_t nodeBase = A.nodes.size();
+    if (nodeBase + O.nodes.size() >= (size_t)REF_LEAF) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced nodes for the 31-bit node reference");
+    auto rebase = [&](uint32_t ref) -> uint32_t {
+      if (ref == REF_EMPTY) return ref;
+      if (ref & REF_LEAF) return ref + (uint32_t)leafBase;
+      return ref + (uint32_t)nodeBase;
+    };
+    for (QNode8 n8 : O.nodes) {
+      for (uint32_t& c : n8.child) c = rebase(c);
+      A.nodes.push_back(n8);
+    }
+    deepest = std::max(deepest, O.maxDepth);
+    rootOf[sr.scene] = rebase(O.root);
+    placed.push_back(&O);
+    numBlobs += n;
+  }
+  std::vector<InstanceStep> steps; // of the moving instances, in record order, behind the instance records
+  for (size_t i = 0; i < order.size(); i++) {
+    const Src& sr = src[order[i]];
+    const Geometry* g = s->geometries[sr.geomID];
+    InstanceRecord& rec = recs[i];
+    memset(&rec, 0, sizeof(rec));
+    if (!invert_affine(g->local2world[0].data(), rec.world2local)) memset(rec.world2local, 0, sizeof(rec.world2local)); // singular: never hit
+    rec.geomID = sr.geomID;
+    rec.root = rootOf[sr.scene];
+    if (g->local2world.size() > 1) {
+      const size_t firstStep = recs.size() + steps.size();
+      if (firstStep >= INSTANCE_FIRST_STEP_LIMIT)
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances and instance time steps for the 24-bit step offset of an instance record");
+      rec.pad[1] = ((uint32_t)(g->local2world.size() - 1) << 24) | (uint32_t)firstStep;
+      for (const Geometry::Xfm& x : g->local2world) {
+        InstanceStep st;
+        memset(&st, 0, sizeof(st));
+        memcpy(st.local2world, x.data(), sizeof(st.local2world));
+        steps.push_back(st);
+      }
+    }
+  }
+  if (steps.size() != numSteps) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: record counts");
+  A.kind = leafKind == ACCEL_GRIDSOA ? ACCEL_INSTSUBDIV_GRID : ACCEL_INSTSUBDIV_CBVH_LEAF;
+  A.cbvhLevels = levels;
+  A.maxDepth = r.maxDepth + 1u + deepest;
+  A.blobStride = (uint32_t)stride;
+  A.blobs.assign((blobBase + numBlobs) * stride, 0);
+  memcpy(A.blobs.data(), recs.data(), recs.size() * sizeof(InstanceRecord));
+  if (!steps.empty()) memcpy(A.blobs.data() + recs.size() * sizeof(InstanceRecord), steps.data(), steps.size() * sizeof(InstanceStep));
+  size_t at = blobBase * stride;
+  for (const Accel* O : placed) {
+    memcpy(A.blobs.data() + at, O->blobs.data(), O->blobs.size());
+    at += O->blobs.size();
+  }
+  A.blobOffsets = {(uint32_t)numBlobs, (uint32_t)blobBase};
+}
+
 void Scene::commit()
 {
   std::lock_guard<std::mutex> g(buildMutex);
@@ -903,6 +1082,7 @@ void Scene::commit()
   build_quadmb_accel(this);
   build_subdiv_accel(this);
   build_instance_accel(this);
+  build_instance_subdiv_accel(this);
   for (Accel* a : accels()) a->upload(device);
   if (progressFn) progressFn(progressUser, 1.0);
   if (device->verbose >= 2) {
@@ -938,6 +1118,10 @@ void Scene::commit()
             instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),
             nQuads, nTriMB, nQuadMB, instAccel.maxDepth);
   }
+  if (instSubdivAccel.kind != ACCEL_NONE && device->verbose >= 2)
+    fprintf(stderr, "embree3-amd: subdivision instance accel kind %u (C %u): %zu nodes (%zu B), %zu instances, %u instanced leaf blobs of %u B from blob index %u, depth %u\n",
+            instSubdivAccel.kind, instSubdivAccel.cbvhLevels, instSubdivAccel.nodes.size(), instSubdivAccel.nodes.size() * sizeof(QNode8), instSubdivAccel.leafCount,
+            instSubdivAccel.blobOffsets[0], instSubdivAccel.blobStride, instSubdivAccel.blobOffsets[1], instSubdivAccel.maxDepth);
   modified = false;
 }
 

@@ -827,9 +827,12 @@ API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 
 // the accel the inspection calls describe: the subdivision accel if there is one, else the triangle accel, else the motion-blur triangle
 // accel, else the quad accel, else (a scene of nothing but quads with time steps) the motion-blur quad accel, else (a scene of nothing
-// but instances) the instance accel
+// but instances) the instance accel, else (nothing but instances of subdivision scenes) the subdivision instance accel
 static const Accel& exported_accel(const Scene* s)
 {
+  if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
+      s->quadMBAccel.kind == ACCEL_NONE && s->instAccel.kind == ACCEL_NONE && s->instSubdivAccel.kind != ACCEL_NONE)
+    return s->instSubdivAccel;
   if (s->subdivAccel.kind != ACCEL_NONE) return s->subdivAccel;
   if (s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind != ACCEL_NONE) return s->triMBAccel;
   if (s->triAccel.kind == ACCEL_NONE && s->quadAccel.kind != ACCEL_NONE) return s->quadAccel;
@@ -887,7 +890,10 @@ API const void* rtcamdGetAccelData(RTCScene h, unsigned int kind, size_t* byteSi
   CATCH_BEGIN
   VERIFY(h);
   if (S(h)->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "scene got not committed");
-  const Accel& A = exported_accel(S(h));
+  // kinds 16..19: the arrays 0..3 of the subdivision instance accel, whatever else the scene holds
+  const bool instSubdiv = kind >= 16 && kind < 20;
+  const Accel& A = instSubdiv ? S(h)->instSubdivAccel : exported_accel(S(h));
+  if (instSubdiv) kind -= 16;
   const void* p = nullptr;
   size_t n = 0;
   switch (kind) {

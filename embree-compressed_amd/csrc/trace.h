@@ -18,7 +18,7 @@ struct LaunchParams
   void* spill;         // HBM overflow area of the per-lane LDS stacks
   uint32_t spillDepth; // entries per lane available in `spill`
   uint32_t gridBlocks; // persistent grid size the spill area was sized for
-  uint32_t cbvhLevels; // fork: depth C of every cBVH blob of the scene (rtcSetSceneLevels)
+  uint32_t cbvhLevels; // fork: depth C of every cBVH blob of the scene (rtcSetSceneLevels; ACCEL_INSTSUBDIV_CBVH_LEAF: of the instanced scenes)
   uint32_t cbvhLaneForm; // fork, lane kernel: 1 = walk blobs one ray per lane (coherent batches), 0 = quad form (trace_cbvh.hip.h)
   WaveRecord* counters;    // non-null selects the instrumented kernel twin; one record per wavefront
   uint32_t numCUs;         // compute units of the device (persistent grid sizing)
@@ -131,6 +131,7 @@ hipError_t launch_trace_cbvh_grid(const LaunchParams& p, hipStream_t stream); //
 hipError_t launch_trace_cbvh_full(const LaunchParams& p, hipStream_t stream); // trace_cbvh_full.hip
 hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  // trace_instance.hip
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb.hip
+hipError_t launch_trace_instance_subdiv(const LaunchParams& p, hipStream_t stream);  // trace_instance_subdiv.hip
 // Development builds (-DTRACE_DEV_METRIC_ONLY, tools/README.md): of the subdivision accels only the metric's kind is dispatched (the
 // others fail with hipErrorInvalidValue, so that only trace_cbvh_leaf.hip has to be rebuilt), and launch_service serves no other kind.
 inline hipError_t launch_service(const ServiceParams& s, hipStream_t stream)
@@ -171,6 +172,8 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_INSTMB_MOELLER: return launch_trace_instance(p, stream);
   case ACCEL_INSTMESHMB_PLUECKER:
   case ACCEL_INSTMESHMB_MOELLER: return launch_trace_instance_mesh_mb(p, stream);
+  case ACCEL_INSTSUBDIV_GRID:
+  case ACCEL_INSTSUBDIV_CBVH_LEAF: return launch_trace_instance_subdiv(p, stream);
   case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
 #ifdef TRACE_DEV_METRIC_ONLY
   case ACCEL_GRIDSOA:

@@ -6,6 +6,8 @@
 // What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and six `bool`
 // constants.  Everything else the text uses comes from the headers trace_instance.hip.h includes and from the TRACE_INST_* macros it
 // defines; the text declares only locals of its own and ends with the traversal loop.
+// trace_instance_subdiv.hip restates the refill, node step, ranking, instance entry and pop of this text for subdivision leaves: a fix to
+// the stack, queue or ranking code here belongs there too.
   static_assert(std::is_same<decltype(P), LaunchParams>::value, "trace_instance_body.hip.h: `LaunchParams P` must be the kernel's parameter");
 #define TRACE_INSTANCE_BODY_BOOL(x) std::is_same<typename std::remove_const<decltype(x)>::type, bool>::value
   static_assert(TRACE_INSTANCE_BODY_BOOL(PLUECKER) && TRACE_INSTANCE_BODY_BOOL(OCCLUDED) && TRACE_INSTANCE_BODY_BOOL(VEC) && TRACE_INSTANCE_BODY_BOOL(QUADS) &&

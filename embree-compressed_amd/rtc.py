@@ -39,6 +39,12 @@ RTC_FORMAT_FLOAT4X4_COLUMN_MAJOR = 0x9244
 # accel kinds of instance accels over scenes that hold meshes with time steps (csrc/accel.h AccelKind, RTCAMDSceneStats::accelKind)
 ACCEL_INSTMESHMB_PLUECKER = 22
 ACCEL_INSTMESHMB_MOELLER = 23
+# accel kinds of the second instance accel of a scene, over scenes that hold subdivision meshes only: eager grid cells / cBVH blobs of
+# bvh4.compressed.leaf below the instances
+ACCEL_INSTSUBDIV_GRID = 24
+ACCEL_INSTSUBDIV_CBVH_LEAF = 25
+# Scene.accel_data(kind + ACCEL_DATA_INSTSUBDIV): the arrays of that second instance accel, whatever else the scene holds
+ACCEL_DATA_INSTSUBDIV = 16
 RTC_SCENE_FLAG_NONE = 0
 RTC_SCENE_FLAG_ROBUST = 4
 RTC_ERROR_NONE, RTC_ERROR_UNKNOWN, RTC_ERROR_INVALID_ARGUMENT, RTC_ERROR_INVALID_OPERATION = 0, 1, 2, 3
@@ -430,7 +436,8 @@ class Scene:
         return gid
 
     def add_instance(self, scene, xfm=None, geom_id=None):
-        """RTC_GEOMETRY_TYPE_INSTANCE of `scene` (a committed Scene of static triangle and / or quad meshes on the same device).  xfm: the
+        """RTC_GEOMETRY_TYPE_INSTANCE of `scene` (a committed Scene on the same device that holds triangle and / or quad meshes, or
+        subdivision meshes only).  xfm: the
         local-to-world transform as a float32 [3,4] row-major matrix (None: identity)."""
         L = self.lib
         g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_INSTANCE)
@@ -641,6 +648,9 @@ class Scene:
         return {n: getattr(st, n) for n, _ in RTCAMDSceneStats._fields_}
 
     def accel_data(self, kind):
+        """0 nodes, 1 triangle records, 2 blobs, 3 blob offsets, 4 kept grids of the accel the inspection calls describe (the subdivision
+        accel, else the first mesh accel, else the instance accel, else the subdivision instance accel); kind + ACCEL_DATA_INSTSUBDIV
+        (kinds 0..3): of the subdivision instance accel."""
         n = C.c_size_t(0)
         p = self.lib.rtcamdGetAccelData(self.handle, kind, C.byref(n))
         self.device.check("rtcamdGetAccelData")

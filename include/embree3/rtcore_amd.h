@@ -111,7 +111,8 @@ RTC_API void rtcamdOccluded1MCounted(RTCScene scene, struct RTCIntersectContext*
 
 /* Read-only views of the host copy of the committed accel (valid until the next commit / release).
  * Test infrastructure: lets an external checker walk the exact structure the kernels traverse.
- * kind: 0 = BVH8 nodes, 1 = primitive records, 2 = subdiv leaf blobs, 3 = blob offset table. */
+ * kind: 0 = BVH8 nodes, 1 = primitive records, 2 = subdiv leaf blobs, 3 = blob offset table; 16 + these: the same arrays of the
+ * scene's subdivision instance accel (instances of scenes that hold subdivision meshes), whatever else the scene holds. */
 RTC_API const void* rtcamdGetAccelData(RTCScene scene, unsigned int kind, size_t* byteSize);
 /* Test hook: the encoder's restatement of the fork's leaf quantiser (quantTris<4>::setZ / estimateExtent,
  * kernels/geometry/compressed_leaf.h:193-251) on caller-supplied inputs: box = lower xyz, upper xyz of the parent box,

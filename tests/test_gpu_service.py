@@ -9,6 +9,8 @@ import time
 import numpy as np
 import pytest
 
+import cbvh_forms_helpers as cf
+
 pytestmark = pytest.mark.gpu
 INVALID = 0xFFFFFFFF
 
@@ -119,3 +121,64 @@ def test_service_follows_a_recommitted_scene(rtc, po, bomberman):
     b.release()
     dev.release()
     dev2.release()
+
+
+# (mode, L, C, served by the resident kernel): launch_service_cbvh (csrc/trace_cbvh.hip.h) instantiates the quad form of every mode at C = 2, 3, 4;
+# at C = 1 and 5 it reports "no such kernel", the service marks itself failed and the call combiner answers (rt_service.cpp service_trace)
+SERVICE_LEVELS = [("box", 3, 2, True), ("full", 4, 3, True), ("leaf", 5, 4, True), ("grid", 5, 4, True), ("leaf", 2, 1, False), ("leaf", 5, 5, False)]
+
+
+@pytest.mark.parametrize("mode,L,C,served", SERVICE_LEVELS)
+def test_service_at_the_other_levels_and_modes(rtc, po, bomberman, monkeypatch, mode, L, C, served):
+    """The service kernels of the cBVH modes beyond leaf / grid at C = 3, on the 32-face mesh of the form matrix (tests/cbvh_forms_helpers.py):
+    512 rays in calls of 1, 7, 33 and 64 rays from two threads, rtcIntersect1 / rtcOccluded1 in between, are byte-identical to ONE rtcIntersect1M /
+    rtcOccluded1M on a device without the service.  Where a service kernel exists the calls went through it (SERVICE_CALLS > 0); at C = 1 and 5
+    none exists: the documented fall-back to the call combiner gives the same bytes, SERVICE_CALLS stays 0 and the device reports no error."""
+    accel = "bvh4.compressed." + mode
+    m = cf.mesh(bomberman)
+    dev0, sc0 = cf.build(rtc, monkeypatch, accel, L, C, "quad", m)
+    dev, sc = cf.build(rtc, monkeypatch, accel, L, C, "quad", m, cfg="service=1")
+    n = 512
+    src = cf.make_rays(po, m[0], n)
+    want = rtc.aligned_rayhits(n)
+    want[:] = src
+    sc0.intersect1M(want)
+    wocc = cf.occ_of(rtc, src)
+    occ = wocc.copy()
+    sc0.occluded1M(wocc)
+    got = rtc.aligned_rayhits(n)
+    got[:] = src
+    T, errors = 2, []
+
+    def worker(t):
+        try:
+            lo, hi = t * n // T, (t + 1) * n // T
+            i, k = lo, t
+            while i < hi:
+                c = min((1, 7, 33, 64)[k % 4], hi - i)
+                k += 1
+                if c == 1:
+                    sc.intersect1(got[i:i + 1])
+                    sc.occluded1(occ[i:i + 1])
+                else:
+                    sc.intersect1M(got[i:i + c])
+                    sc.occluded1M(occ[i:i + c])
+                i += c
+        except Exception as e:  # noqa: BLE001
+            errors.append(e)
+
+    threads = [threading.Thread(target=worker, args=(t,)) for t in range(T)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors[0]
+    calls = dev.get_property(rtc.RTCAMD_DEVICE_PROPERTY_SERVICE_CALLS)
+    assert (calls > 0) if served else (calls == 0), calls
+    assert got.tobytes() == want.tobytes(), f"{cf.differing(got, want)} closest-hit records differ"
+    assert occ.tobytes() == wocc.tobytes(), f"{cf.differing(occ, wocc)} any-hit records differ"
+    assert cf.hits_of(got) > 30 and cf.occluded_of(occ) >= cf.hits_of(got)
+    assert dev.error() == rtc.RTC_ERROR_NONE and dev0.error() == rtc.RTC_ERROR_NONE
+    for s_, d_ in ((sc, dev), (sc0, dev0)):
+        s_.release()
+        d_.release()

@@ -159,7 +159,24 @@ def cubes():
         orc.free(); orc_t.free(); sc.release(); dev.release()
 
 
+def cbvh_forms():
+    """the 28 cases of the cBVH form matrix (tests/cbvh_forms_helpers.py: 32-face mesh, 20 000 rays, every C, L == C): the classified figures
+    the parity leg of tests/test_gpu_cbvh_forms.py will see, with the counts tests/test_host_cbvh_forms.py pins"""
+    import cbvh_forms_helpers as cf
+    m = cf.mesh((V, FS, FI))
+    src = cf.make_rays(po, m[0])
+    for accel in cf.MODES:
+        for L, C in cf.PAIRS:
+            dev, sc, orc, _ = scene(accel, *m, L, C)
+            orc.free()
+            a, b, occ = cf.expected(po, sc, accel, C, src)
+            report(f"cbvh forms {accel} L{L} C{C} ({cf.hits_of(a)} hits, {cf.occluded_of(occ)} occluded on the oracle's tree, {cf.differing(a, b)} records differ in bytes)",
+                   accel, a, b, 2.0 ** -L)
+            sc.release(); dev.release()
+
+
 if __name__ == "__main__":
+    cbvh_forms()
     bomberman_random(3, 2, 100_000, 0)
     bomberman_random(6, 3, 1_000_000, 0)
     if not QUICK:

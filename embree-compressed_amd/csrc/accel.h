@@ -1,7 +1,8 @@
 // Device-resident acceleration-structure records shared by the host builders and the HIP kernels.
 //
 // Everything the kernels read lives in four flat HBM arrays per committed scene:
-//   nodes   : QNode8[]       96-byte quantized BVH8 nodes, index 0 = root (if the root is inner)
+//   nodes   : QNode8[]       96-byte quantized BVH8 nodes, index 0 = root (if the root is inner);
+//                            QNodeMB8[] (144-byte time-dependent nodes) in the motion-blur accels built with mb_bounds=linear
 //   prims   : TriRecord[]    48-byte triangle records (v0,v1,v2 or v0,e1,e2 + ids), leaf-contiguous
 //   blobs   : bytes          cBVH / GridSOA leaf blobs for subdivision geometry (16-byte aligned each),
 //                            or QuadRecord[] (64-byte quad records, leaf-contiguous) for quad geometry,
@@ -53,6 +54,42 @@ struct alignas(16) QNode8
   uint8_t q[6][8]; // lo_x, hi_x, lo_y, hi_y, lo_z, hi_z  (same plane order as AlignedNode, bvh.h:588-593)
 };
 static_assert(sizeof(QNode8) == 96, "QNode8 must be 96 bytes");
+
+// ---- time-dependent quantized BVH8 node (linear bounds), 144 bytes = 9 x dwordx4 ------------------------------
+// The node of the motion-blur accels built with mb_bounds=linear (kinds ACCEL_*MB_LINEAR_*): the 96 bytes of a QNode8 - whose plane
+// block q holds the children's boxes at time 0 - followed by a second plane block q1 with their boxes at time 1, both on ONE origin /
+// exponent grid (the reference keeps a float box and its change over the shutter per child, AlignedNodeMB, bvh.h:597-835).  Child i's plane p at ray time t, with
+// t the ray's time on the global [0, 1] axis (NOT a per-mesh segment time), is interpolated in grid units and decoded once:
+//   tc = fminf(fmaxf(t, 0), 1)
+//   qf = fmaf(tc, float(q1[p][i]) - float(q[p][i]), float(q[p][i]))          (the difference of two bytes is exact)
+//   plane = fmaf(qf, scale[a], origin[a])                                    (scale[a] as in QNode8, never 0.0 here: exp >= 1)
+// Guarantee (quantize_node_mb): for every t in [0, 1] the box so decoded holds every vertex that any record below the child produces
+// for a ray at time t that the record accepts - time_segment() is true and the vertices go through lerp_vertex() (trace_mb.hip.h) -
+// under exactly these fp32 formulas.  The argument:
+//  * In real arithmetic the plane is lerp(P0, P1, t) of the two decoded end planes.  The builder hands over end boxes B(0), B(1)
+//    whose real lerp holds every record at both global ends of its segment, hence (both sides are linear) at every time of it, and
+//    the quantizer moves every end plane outward by at least ONE grid step s beyond B: lower planes lie in (lo - 2 s, lo - s], upper
+//    planes in [hi + s, hi + 2 s).  The real interpolated plane is therefore at least s outside the real interpolated vertex.
+//  * What fp32 adds, with R the largest magnitude on the node's grid (all planes and all vertices below lie on it, so |x| <= R and
+//    |p1 - p0| <= 255 s for a record's two ends): the plane's two roundings are at most 2^-17 s + 2^-24 R; lerp_vertex's three at
+//    most 3 * 2^-24 R; time_segment's product time * S is off by at most 2^-24 S, which moves the vertex by at most 255 s * 2^-24 S
+//    <= 2^-9 s for the at most 128 segments of a mesh (the same bound holds for a ray whose product rounds onto the next segment's
+//    first instant).  The quantizer picks the exponent so that s >= 2^-21 R, and the origin as a multiple of s; the sum is then
+//    below s / 2 + s / 256 < s.
+// At t = 0 and t = 1 the decode is exact (origin and planes are multiples of s below 2^24 s), so the box there exceeds B by at least
+// one and by less than two grid steps per side.  Times outside [0, 1] are clamped: the box stays the one of the nearer end while a
+// record extrapolates, so such rays are no more conservative than under swept boxes - and never fault.
+// Empty children have child == REF_EMPTY and inverted boxes in both blocks.
+struct alignas(16) QNodeMB8
+{
+  float origin[3];
+  uint8_t exp[3];
+  uint8_t pad;
+  uint32_t child[8];
+  uint8_t q[6][8];  // time 0: lo_x, hi_x, lo_y, hi_y, lo_z, hi_z
+  uint8_t q1[6][8]; // time 1, same order
+};
+static_assert(sizeof(QNodeMB8) == 144, "QNodeMB8 must be 144 bytes");
 
 // ---- triangle record, 48 bytes = 3 x dwordx4 ----------------------------------------------------------
 // Pluecker accel (robust):  a = v0, b = v1, c = v2            (TriangleMv, trianglev.h:156-161)
@@ -332,14 +369,23 @@ enum AccelKind : uint32_t
   // instances of scenes that hold subdivision meshes only (Scene::instSubdivAccel, see InstanceRecord): one kind per leaf family; the
   // compression level C of the cBVH blobs travels beside the accel (Accel::cbvhLevels -> LaunchParams::cbvhLevels)
   ACCEL_INSTSUBDIV_GRID = 24,     // instanced scenes whose subdivision accel is ACCEL_GRIDSOA (eager): GridCells below the instances
-  ACCEL_INSTSUBDIV_CBVH_LEAF = 25 // instanced scenes whose subdivision accel is ACCEL_CBVH_LEAF, all at one C: cBVH blobs below the instances
+  ACCEL_INSTSUBDIV_CBVH_LEAF = 25, // instanced scenes whose subdivision accel is ACCEL_CBVH_LEAF, all at one C: cBVH blobs below the instances
+  // mb_bounds=linear: the four motion-blur mesh accels over time-dependent nodes (QNodeMB8[] in `nodes`, 144-byte stride); records,
+  // leaves and the Pluecker / Moeller choice are those of the kinds 10..13.  NOT instance kinds.
+  ACCEL_TRIMB_LINEAR_PLUECKER = 26,
+  ACCEL_TRIMB_LINEAR_MOELLER = 27,
+  ACCEL_QUADMB_LINEAR_PLUECKER = 28,
+  ACCEL_QUADMB_LINEAR_MOELLER = 29
 };
 inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF; } // traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip
+
+inline bool is_mb_linear_kind(uint32_t kind) { return kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER; } // nodes are QNodeMB8
+inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKER && kind <= ACCEL_QUADMB_MOELLER) || is_mb_linear_kind(kind); } // lane kernel only, no service kernel
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
 {
-  const QNode8* nodes;
+  const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*
   const TriRecord* prims;
   const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16

@@ -1,6 +1,7 @@
 #include "bvh8_builder.h"
 
 #include <algorithm>
+#include <type_traits>
 #include <thread>
 
 namespace rtamd {
@@ -139,12 +140,14 @@ struct Binner
   }
 };
 
-struct Collapser
+// Node: QNode8 (boxes of the binary tree, quantize_node) or QNodeMB8 (end boxes from `linearBounds`, quantize_node_mb)
+template <class Result> struct Collapser
 {
   const std::vector<BinNode>& tree;
   const std::vector<BuildPrim>& prims;
   const MakeLeafFn& makeLeaf;
-  BuildResult& out;
+  Result& out;
+  const LinearBoundsFn* linearBounds = nullptr;
 
   uint32_t emit(int bn, uint32_t depth)
   {
@@ -176,16 +179,24 @@ struct Collapser
       kids[nk++] = tree[open].right;
     }
     uint32_t me = (uint32_t)out.nodes.size();
-    out.nodes.push_back(QNode8());
+    out.nodes.emplace_back();
     Box3 boxes[8];
     uint32_t refs[8];
     for (int i = 0; i < nk; i++) {
       boxes[i] = tree[kids[i]].box;
       refs[i] = emit(kids[i], depth + 1);
     }
-    QNode8 q;
-    quantize_node(boxes, refs, nk, q);
-    out.nodes[me] = q;
+    if constexpr (std::is_same<Result, BuildResultMB>::value) {
+      Box3 boxes1[8];
+      for (int i = 0; i < nk; i++) (*linearBounds)(prims.data(), tree[kids[i]].begin, tree[kids[i]].end, boxes[i], boxes1[i]);
+      QNodeMB8 q;
+      quantize_node_mb(boxes, boxes1, refs, nk, q);
+      out.nodes[me] = q;
+    } else {
+      QNode8 q;
+      quantize_node(boxes, refs, nk, q);
+      out.nodes[me] = q;
+    }
     return me;
   }
 };
@@ -267,10 +278,90 @@ BuildResult build_bvh8(std::vector<BuildPrim>& prims, const BuildSettings& setti
   Binner binner(prims, settings, prims.size());
   for (unsigned t = settings.threads; t > 1; t >>= 1) binner.forks++;
   int root = binner.build(0, prims.size());
-  Collapser c{binner.tree, prims, makeLeaf, out};
+  Collapser<BuildResult> c{binner.tree, prims, makeLeaf, out};
   out.nodes.reserve(prims.size() / 8 + 8);
   out.root = c.emit(root, 0);
   return out;
+}
+
+BuildResultMB build_bvh8_mb(std::vector<BuildPrim>& prims, const BuildSettings& settings, const MakeLeafFn& makeLeaf, const LinearBoundsFn& linearBounds)
+{
+  BuildResultMB out;
+  if (prims.empty()) return out;
+  Binner binner(prims, settings, prims.size());
+  for (unsigned t = settings.threads; t > 1; t >>= 1) binner.forks++;
+  int root = binner.build(0, prims.size());
+  Collapser<BuildResultMB> c{binner.tree, prims, makeLeaf, out, &linearBounds};
+  out.nodes.reserve(prims.size() / 8 + 8);
+  out.root = c.emit(root, 0);
+  return out;
+}
+
+Box3 dequantize_child_mb(const QNodeMB8& n, int i, float t)
+{
+  const float tc = fminf(fmaxf(t, 0.0f), 1.0f);
+  Box3 b;
+  for (int a = 0; a < 3; a++) {
+    const float s = scale_from_exp(n.exp[a]);
+    const float l0 = float(n.q[2 * a + 0][i]), l1 = float(n.q1[2 * a + 0][i]);
+    const float h0 = float(n.q[2 * a + 1][i]), h1 = float(n.q1[2 * a + 1][i]);
+    b.lo[a] = fmaf(fmaf(tc, l1 - l0, l0), s, n.origin[a]);
+    b.hi[a] = fmaf(fmaf(tc, h1 - h0, h0), s, n.origin[a]);
+  }
+  return b;
+}
+
+// Per axis: the smallest grid step s = 2^(e - 127), e in 1..254, with
+//   (1) an origin o = s * floor((lo - s) / s) below the lowest plane by at least one step that fp32 holds exactly (|o| / s < 2^24),
+//   (2) s >= 2^-21 R, R = the largest magnitude on the grid [o, o + 255 s]  (accel.h QNodeMB8: what makes one step of padding enough),
+//   (3) every plane, moved outward by one whole step beyond its box, within 0..255:  qlo = floor((lo - o) / s) - 1,
+//       qhi = ceil((hi - o) / s) + 1.
+// All quotients are formed in double from fp32 inputs and a power of two; under (2) they are exact.
+void quantize_node_mb(const Box3* b0, const Box3* b1, const uint32_t* refs, int n, QNodeMB8& out)
+{
+  memset(&out, 0, sizeof(out));
+  for (int i = 0; i < 8; i++) out.child[i] = i < n ? refs[i] : REF_EMPTY;
+  for (int a = 0; a < 3; a++) {
+    double lo = std::numeric_limits<double>::infinity(), hi = -lo;
+    for (int i = 0; i < n; i++) {
+      lo = std::min(lo, (double)std::min(b0[i].lo[a], b1[i].lo[a]));
+      hi = std::max(hi, (double)std::max(b0[i].hi[a], b1[i].hi[a]));
+    }
+    if (!(std::isfinite(lo) && std::isfinite(hi))) RT_THROW(RTC_ERROR_UNKNOWN, "bvh8 quantizer: bounds are not finite");
+    int e = 1;
+    {
+      int ex;
+      frexp(std::max((hi - lo) / 253.0, std::max(fabs(lo), fabs(hi)) * 0x1p-21), &ex);
+      e = std::min(std::max(ex + 127 - 2, 1), 254); // a little below the estimate: the loop finds the smallest that fits
+    }
+    for (;; e++) {
+      if (e > 254) RT_THROW(RTC_ERROR_UNKNOWN, "bvh8 quantizer: extent not representable");
+      const double s = (double)scale_from_exp((uint8_t)e);
+      const double o = s * floor((lo - s) / s);
+      const double R = std::max(fabs(o), fabs(o + 255.0 * s));
+      if (!(s >= R * 0x1p-21) || !(fabs(o) / s < 0x1p24) || (double)(float)o != o) continue;
+      bool ok = true;
+      for (int i = 0; i < n && ok; i++)
+        for (int k = 0; k < 2 && ok; k++) {
+          const Box3& b = k ? b1[i] : b0[i];
+          const double qlo = floor(((double)b.lo[a] - o) / s) - 1.0;
+          const double qhi = ceil(((double)b.hi[a] - o) / s) + 1.0;
+          if (qlo < 0.0 || qhi > 255.0) ok = false;
+          else {
+            (k ? out.q1 : out.q)[2 * a + 0][i] = (uint8_t)qlo;
+            (k ? out.q1 : out.q)[2 * a + 1][i] = (uint8_t)qhi;
+          }
+        }
+      if (!ok) continue;
+      out.origin[a] = (float)o;
+      out.exp[a] = (uint8_t)e;
+      break;
+    }
+    for (int i = n; i < 8; i++) { // inverted boxes for empty slots
+      out.q[2 * a + 0][i] = out.q1[2 * a + 0][i] = 255;
+      out.q[2 * a + 1][i] = out.q1[2 * a + 1][i] = 0;
+    }
+  }
 }
 
 } // namespace rtamd

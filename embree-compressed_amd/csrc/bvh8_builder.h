@@ -48,4 +48,26 @@ void quantize_node(const Box3* childBoxes, const uint32_t* childRefs, int n, QNo
 // Decode child i of a node with exactly the arithmetic the kernels use.
 Box3 dequantize_child(const QNode8& node, int i);
 
+
+// ---- time-dependent nodes (mb_bounds=linear, accel.h QNodeMB8) ----------------------------------------------------------------------
+// The same binned-SAH build and collapse over the boxes the caller put into `prims` (for the motion-blur accels: every record's box at
+// the midpoint of its time segment); the boxes stored in the nodes do not come from `prims` but from linearBounds(prims, begin, end,
+// b0, b1), called once per child of every node with the child's final, contiguous range of `prims`: two boxes, at time 0 and at time 1,
+// whose linear interpolation holds everything below the child at every time the records below are valid.
+struct BuildResultMB
+{
+  std::vector<QNodeMB8> nodes;
+  uint32_t root = REF_EMPTY;
+  uint32_t maxDepth = 0;
+  size_t leafCount = 0;
+};
+using LinearBoundsFn = std::function<void(const BuildPrim* prims, size_t begin, size_t end, Box3& b0, Box3& b1)>;
+BuildResultMB build_bvh8_mb(std::vector<BuildPrim>& prims, const BuildSettings& settings, const MakeLeafFn& makeLeaf, const LinearBoundsFn& linearBounds);
+
+// Quantize the end boxes (time 0, time 1) of up to 8 children into one node, every plane at least one and less than two grid steps
+// outside its box (the guarantee and its argument: accel.h QNodeMB8); exported for the unit tests of the codec.
+void quantize_node_mb(const Box3* childBoxes0, const Box3* childBoxes1, const uint32_t* childRefs, int n, QNodeMB8& out);
+// Decode child i of a node at ray time t with exactly the arithmetic the kernels use.
+Box3 dequantize_child_mb(const QNodeMB8& node, int i, float t);
+
 } // namespace rtamd

@@ -41,6 +41,10 @@ void Device::parse(const std::string& cfg)
     else if (key == "tri_accel_mb") { tri_accel_mb = val; triAccelMBNamed = true; }
     else if (key == "quad_accel_mb") { quad_accel_mb = val; quadAccelMBNamed = true; }
     else if (key == "inst_accel") { inst_accel = val; instAccelNamed = true; }
+    else if (key == "mb_bounds") {
+      if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "mb_bounds=: unknown value '" + val + "' (swept or linear)");
+      mb_bounds = val;
+    }
     else if (key == "verbose") verbose = atoi(val.c_str());
     else if (key == "gpu" || key == "device") { gpu = (val == "none") ? -1 : atoi(val.c_str()); gpuList.clear(); }
     else if (key == "gpus") {

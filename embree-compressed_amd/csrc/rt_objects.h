@@ -30,6 +30,7 @@ struct Device : RefCounted
   std::string quad_accel = "default";
   std::string tri_accel_mb = "default"; // triangle meshes with more than one time step
   std::string quad_accel_mb = "default"; // quad meshes with more than one time step
+  std::string mb_bounds = "swept"; // node boxes of the motion-blur mesh accels: "swept" (one box over the whole shutter, QNode8) or "linear" (time-dependent, QNodeMB8)
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
@@ -330,6 +331,7 @@ struct Geometry : RefCounted
 struct Accel
 {
   std::vector<QNode8> nodes;
+  std::vector<QNodeMB8> nodesMB; // the kinds ACCEL_*MB_LINEAR_* (mb_bounds=linear): their time-dependent nodes, `nodes` is empty then
   std::vector<TriRecord> prims;
   std::vector<uint8_t> blobs;
   std::vector<uint32_t> blobOffsets;
@@ -351,6 +353,10 @@ struct Accel
   std::vector<DevCopy> dev;
   std::vector<int> devOrdinals; // ordinal each copy lives on (for freeDevice)
   AccelDesc desc(size_t shard = 0) const;
+  // the node array whichever of the two it is: what is uploaded, counted and handed out for inspection
+  size_t nodeCount() const { return is_mb_linear_kind(kind) ? nodesMB.size() : nodes.size(); }
+  size_t nodeStride() const { return is_mb_linear_kind(kind) ? sizeof(QNodeMB8) : sizeof(QNode8); }
+  const void* nodeData() const { return is_mb_linear_kind(kind) ? (const void*)nodesMB.data() : (const void*)nodes.data(); }
   bool traceable() const { return kind != ACCEL_NONE && root != REF_EMPTY; } // a launch on anything else returns before it touches the GPU
   size_t deviceBytes() const;
   void upload(Device* dev);

@@ -162,7 +162,7 @@ AccelDesc Accel::desc(size_t shard) const
 
 size_t Accel::deviceBytes() const
 {
-  return nodes.size() * sizeof(QNode8) + prims.size() * sizeof(TriRecord) + blobs.size() + blobOffsets.size() * 4;
+  return nodeCount() * nodeStride() + prims.size() * sizeof(TriRecord) + blobs.size() + blobOffsets.size() * 4;
 }
 
 void Accel::freeDevice()
@@ -183,6 +183,7 @@ void Accel::freeDevice()
 void Accel::clear()
 {
   nodes.clear();
+  nodesMB.clear();
   prims.clear();
   blobs.clear();
   blobOffsets.clear();
@@ -215,7 +216,7 @@ void Accel::upload(Device* device)
     sh.use();
     devOrdinals[i] = sh.ordinal;
     DevCopy& c = dev[i];
-    c.dNodes = upload_array(sh.stream, nodes.data(), nodes.size() * sizeof(QNode8));
+    c.dNodes = upload_array(sh.stream, nodeData(), nodeCount() * nodeStride());
     c.dPrims = upload_array(sh.stream, prims.data(), prims.size() * sizeof(TriRecord));
     c.dBlobs = upload_array(sh.stream, blobs.data(), blobs.size());
     c.dBlobOffsets = upload_array(sh.stream, blobOffsets.data(), blobOffsets.size() * 4);
@@ -396,12 +397,27 @@ static void build_quad_accel(Scene* s)
 // the first / last segment only where it still is inside its box).  A pair gets a record only when the primitive is valid at both ends.
 // fill(rec, v) writes the 2 * NV vertices (segment start, then segment end) into a zeroed record; the four id words are set here.
 // false (and `A` untouched): no record.
+// mb_bounds=linear (Device::mb_bounds): the same pairs, records and leaf conventions under time-dependent nodes (accel.h QNodeMB8, `A.nodesMB`).
+//  * Topology: the SAH build runs over every pair's box at ONE instant, the midpoint of its segment (the box of the vertices'
+//    midpoints) - not over the swept unions, whose overlap is what stops the swept build early on anything that really moves.
+//  * Bounds, per child of every node, over the pairs below it (linear_bounds): two boxes B(0), B(1) whose interpolation holds every
+//    pair at both ends of its segment, at the global times seg / S and (seg + 1) / S.  First guess: the union of the start boxes of
+//    the pairs of segment 0 and the union of the end boxes of the pairs of the last segment (of all pairs when there is none); then
+//    both ends are widened, per plane, by the largest amount any pair end sticks out of the interpolated guess (the reference's
+//    linearBounds, kernels/common/scene_triangle_mesh.h).  For meshes with two time steps every end lies at time 0 or 1, nothing
+//    sticks out, and the result is exactly the bounds at step 0 and at step 1.  Computed in double and rounded outward to fp32; what
+//    double loses is covered, far over, by the quantizer's one-step padding.
+//  * Scene::bounds is extended by the swept boxes, as in the swept build.
 template <int NV, class Rec, class Fill>
 static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* tooMany, std::vector<Rec>& recs, const Fill& fill)
 {
+  const bool linear = s->device->mb_bounds == "linear";
   struct Src { unsigned geomID, primID, segment; };
+  struct Ends { Box3 a, b; double ta, tb; }; // linear: a pair's boxes at the start / end of its segment and their global times
   std::vector<Src> src;
+  std::vector<Ends> ends;
   std::vector<BuildPrim> bp;
+  Box3 swept;
   auto vertices = [](const Geometry* g, size_t i, unsigned slot, V3* v) {
     const unsigned* idx = (const unsigned*)g->view(RTC_BUFFER_TYPE_INDEX, 0)->at(i);
     for (int k = 0; k < NV; k++) v[k] = g->vertex(idx[k], slot);
@@ -423,7 +439,21 @@ static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* 
         vertices(g, i, seg, v);
         vertices(g, i, seg + 1, v + NV);
         BuildPrim p;
-        for (int k = 0; k < 2 * NV; k++) p.box.extend(v[k]);
+        if (linear) {
+          Ends e;
+          for (int k = 0; k < NV; k++) {
+            e.a.extend(v[k]);
+            e.b.extend(v[NV + k]);
+            p.box.extend((v[k] + v[NV + k]) * 0.5f);
+          }
+          const double S = (double)(g->timeSteps - 1);
+          e.ta = (double)seg / S;
+          e.tb = (double)(seg + 1) / S;
+          swept.extend(e.a);
+          swept.extend(e.b);
+          ends.push_back(e);
+        } else
+          for (int k = 0; k < 2 * NV; k++) p.box.extend(v[k]);
         p.id = (uint32_t)src.size();
         src.push_back({gid, (unsigned)i, seg});
         bp.push_back(p);
@@ -455,12 +485,51 @@ static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* 
   };
   BuildSettings cfg;
   cfg.threads = host_threads(s->device);
-  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
-  A.nodes = std::move(r.nodes);
-  A.root = r.root;
-  A.maxDepth = r.maxDepth;
-  A.leafCount = r.leafCount;
-  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  if (linear) {
+    auto linear_bounds = [&](const BuildPrim* prims, size_t begin, size_t end, Box3& b0, Box3& b1) {
+      const double inf = std::numeric_limits<double>::infinity();
+      double lo0[3], hi0[3], lo1[3], hi1[3];
+      for (int pass = 0; pass < 2; pass++) { // pass 0: the pairs of segment 0 / of the last segment; pass 1 (none there): all pairs
+        for (int a = 0; a < 3; a++) { lo0[a] = lo1[a] = inf; hi0[a] = hi1[a] = -inf; }
+        bool any0 = false, any1 = false;
+        for (size_t i = begin; i < end; i++) {
+          const Ends& e = ends[prims[i].id];
+          if (pass == 1 || e.ta == 0.0) { any0 = true; for (int a = 0; a < 3; a++) { lo0[a] = std::min(lo0[a], (double)e.a.lo[a]); hi0[a] = std::max(hi0[a], (double)e.a.hi[a]); } }
+          if (pass == 1 || e.tb == 1.0) { any1 = true; for (int a = 0; a < 3; a++) { lo1[a] = std::min(lo1[a], (double)e.b.lo[a]); hi1[a] = std::max(hi1[a], (double)e.b.hi[a]); } }
+        }
+        if (any0 && any1) break;
+      }
+      for (int a = 0; a < 3; a++) {
+        double dlo = 0.0, dhi = 0.0; // how far any pair end sticks out of the interpolated guess
+        for (size_t i = begin; i < end; i++) {
+          const Ends& e = ends[prims[i].id];
+          for (int k = 0; k < 2; k++) {
+            const double t = k ? e.tb : e.ta;
+            const Box3& b = k ? e.b : e.a;
+            dlo = std::max(dlo, ((1.0 - t) * lo0[a] + t * lo1[a]) - (double)b.lo[a]);
+            dhi = std::max(dhi, (double)b.hi[a] - ((1.0 - t) * hi0[a] + t * hi1[a]));
+          }
+        }
+        auto down = [](double x) { float f = (float)x; return (double)f > x ? nextafterf(f, -std::numeric_limits<float>::infinity()) : f; };
+        auto up = [](double x) { float f = (float)x; return (double)f < x ? nextafterf(f, std::numeric_limits<float>::infinity()) : f; };
+        b0.lo[a] = down(lo0[a] - dlo); b1.lo[a] = down(lo1[a] - dlo);
+        b0.hi[a] = up(hi0[a] + dhi); b1.hi[a] = up(hi1[a] + dhi);
+      }
+    };
+    BuildResultMB r = build_bvh8_mb(bp, cfg, makeLeaf, linear_bounds);
+    A.nodesMB = std::move(r.nodes);
+    A.root = r.root;
+    A.maxDepth = r.maxDepth;
+    A.leafCount = r.leafCount;
+    s->bounds.extend(swept);
+  } else {
+    BuildResult r = build_bvh8(bp, cfg, makeLeaf);
+    A.nodes = std::move(r.nodes);
+    A.root = r.root;
+    A.maxDepth = r.maxDepth;
+    A.leafCount = r.leafCount;
+    for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  }
   A.blobStride = sizeof(Rec);
   A.blobs.resize(recs.size() * sizeof(Rec));
   memcpy(A.blobs.data(), recs.data(), A.blobs.size());
@@ -491,6 +560,7 @@ static void build_trimb_accel(Scene* s)
   };
   if (!build_mb_bvh8<3>(s, A, RTC_GEOMETRY_TYPE_TRIANGLE, "too many motion blur triangle segments for the 26-bit leaf reference", recs, fill)) return;
   A.kind = pluecker ? ACCEL_TRIMB_PLUECKER : ACCEL_TRIMB_MOELLER; // only once there are records
+  if (s->device->mb_bounds == "linear") A.kind = pluecker ? ACCEL_TRIMB_LINEAR_PLUECKER : ACCEL_TRIMB_LINEAR_MOELLER;
   A.robust = pluecker ? 1 : 0;
 }
 
@@ -520,6 +590,7 @@ static void build_quadmb_accel(Scene* s)
   };
   if (!build_mb_bvh8<4>(s, A, RTC_GEOMETRY_TYPE_QUAD, "too many motion blur quad segments for the 26-bit leaf reference", recs, fill)) return;
   A.kind = pluecker ? ACCEL_QUADMB_PLUECKER : ACCEL_QUADMB_MOELLER; // only once there are records
+  if (s->device->mb_bounds == "linear") A.kind = pluecker ? ACCEL_QUADMB_LINEAR_PLUECKER : ACCEL_QUADMB_LINEAR_MOELLER;
   A.robust = pluecker ? 1 : 0;
 }
 
@@ -655,6 +726,9 @@ static void build_instance_accel(Scene* s)
     if (!o) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance without an instanced scene");
     if (o->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instanced scene got not committed");
     if (subdivOk && is_subdivision_scene(o)) continue; // build_instance_subdiv_accel places it
+    // the instanced scenes' trees are copied behind the top-level tree as QNode8s: time-dependent nodes have no place there
+    if (is_mb_linear_kind(o->triMBAccel.kind) || is_mb_linear_kind(o->quadMBAccel.kind))
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene with a motion blur accel built under mb_bounds=linear is not supported (instance accels hold swept node boxes: use mb_bounds=swept)");
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
       const bool mesh = og->type == RTC_GEOMETRY_TYPE_TRIANGLE || (quadsOk && og->type == RTC_GEOMETRY_TYPE_QUAD);
@@ -1090,14 +1164,14 @@ void Scene::commit()
             triAccel.kind, triAccel.nodes.size(), triAccel.nodes.size() * sizeof(QNode8), triAccel.prims.size(), triAccel.maxDepth,
             subdivAccel.kind, subdivAccel.nodes.size(), subdivAccel.blobOffsets.size(), subdivAccel.blobs.size());
     if (triMBAccel.kind != ACCEL_NONE)
-      fprintf(stderr, "embree3-amd: motion blur triangle accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", triMBAccel.kind, triMBAccel.nodes.size(),
-              triMBAccel.nodes.size() * sizeof(QNode8), triMBAccel.blobs.size() / sizeof(TriMBRecord), triMBAccel.blobs.size(), triMBAccel.maxDepth);
+      fprintf(stderr, "embree3-amd: motion blur triangle accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", triMBAccel.kind, triMBAccel.nodeCount(),
+              triMBAccel.nodeCount() * triMBAccel.nodeStride(), triMBAccel.blobs.size() / sizeof(TriMBRecord), triMBAccel.blobs.size(), triMBAccel.maxDepth);
     if (quadAccel.kind != ACCEL_NONE)
       fprintf(stderr, "embree3-amd: quad accel kind %u: %zu nodes (%zu B), %zu quads (%zu B), depth %u\n", quadAccel.kind, quadAccel.nodes.size(),
               quadAccel.nodes.size() * sizeof(QNode8), quadAccel.blobs.size() / sizeof(QuadRecord), quadAccel.blobs.size(), quadAccel.maxDepth);
     if (quadMBAccel.kind != ACCEL_NONE)
-      fprintf(stderr, "embree3-amd: motion blur quad accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", quadMBAccel.kind, quadMBAccel.nodes.size(),
-              quadMBAccel.nodes.size() * sizeof(QNode8), quadMBAccel.blobs.size() / sizeof(QuadMBRecord), quadMBAccel.blobs.size(), quadMBAccel.maxDepth);
+      fprintf(stderr, "embree3-amd: motion blur quad accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", quadMBAccel.kind, quadMBAccel.nodeCount(),
+              quadMBAccel.nodeCount() * quadMBAccel.nodeStride(), quadMBAccel.blobs.size() / sizeof(QuadMBRecord), quadMBAccel.blobs.size(), quadMBAccel.maxDepth);
   }
   if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
   {

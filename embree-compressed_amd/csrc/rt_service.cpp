@@ -115,7 +115,7 @@ static bool service_trace(Scene* s, char* rays, uint32_t M, size_t byteStride, b
     if (a->traceable()) { if (only) return false; only = a; } // several accels (AccelN): the general path
   if (!only) return false;
   const Accel& A = *only;
-  if (A.kind == ACCEL_TRIMB_PLUECKER || A.kind == ACCEL_TRIMB_MOELLER || A.kind == ACCEL_QUADMB_PLUECKER || A.kind == ACCEL_QUADMB_MOELLER) return false; // no service kernel for motion blur: the combiner traces these calls with the batch kernels
+  if (is_mb_mesh_kind(A.kind)) return false; // no service kernel for motion blur: the combiner traces these calls with the batch kernels
   if (is_instance_kind(A.kind)) return false; // nor for instances (trace_instance.hip)
   const uint32_t worst = 7u * (A.maxDepth + 1u) + 2u;
   const uint32_t need = worst > (uint32_t)TRACE_LDS_STACK ? worst - TRACE_LDS_STACK : 0u;

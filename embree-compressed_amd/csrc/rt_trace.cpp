@@ -68,8 +68,8 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   // (quad leaves stay on the lane kernel unless RTAMD_KERNEL=pool: not measured)
   const bool poolPays = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER || A.kind == ACCEL_CBVH_GRID;
   p.poolKernel = dev->tunePoolKernel == 2u ? (poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel;
-  if (A.kind == ACCEL_TRIMB_PLUECKER || A.kind == ACCEL_TRIMB_MOELLER || A.kind == ACCEL_QUADMB_PLUECKER || A.kind == ACCEL_QUADMB_MOELLER)
-    p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip)
+  if (is_mb_mesh_kind(A.kind))
+    p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip), under swept and under linear bounds
   const bool instKernel = is_instance_kind(A.kind);
   if (instKernel) p.poolKernel = 0u; // the two-level kernel is a lane-per-ray kernel of its own (trace_instance.hip, trace_instance_subdiv.hip): no pool form, no root cull pre-pass
   // worst-case stack: 7 siblings per level plus the entry being expanded.  The overflow area is sized for it, so a push
@@ -140,7 +140,9 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   // Root cull pre-pass (trace_cull.hip.h): large batches on the lane kernel whose root is an inner node.  Filter re-traces
   // (exclusion lists) are small and skip it.
   p.survivors = nullptr;
-  if (dev->tuneCull && !p.poolKernel && !instKernel && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
+  // (never on the kinds of mb_bounds=linear: the pre-pass decodes a QNode8 root, and a root of time-dependent boxes would have to be
+  // culled per ray time)
+  if (dev->tuneCull && !p.poolKernel && !instKernel && !is_mb_linear_kind(A.kind) && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
     const size_t need = ((size_t)(M + TRACE_QUEUES - 1) / TRACE_QUEUES) * TRACE_QUEUES * 4u;
     if (need > ctx.survivorsBytes) { // first batch of this size on this context (an allocation synchronises the device)
       HIP_CHECK(hipStreamSynchronize(stream));

@@ -851,8 +851,8 @@ API void rtcamdGetSceneStats(RTCScene h, struct RTCAMDSceneStats* st)
   const Accel& A = exported_accel(S(h));
   st->accelKind = A.kind;
   st->branching = 8;
-  st->nodeCount = A.nodes.size();
-  st->nodeBytes = sizeof(QNode8);
+  st->nodeCount = A.nodeCount();
+  st->nodeBytes = A.nodeStride(); // QNode8, or QNodeMB8 in the kinds 26..29
   const bool tri = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER;
   st->primCount = tri ? A.prims.size() : (A.blobStride ? A.blobs.size() / A.blobStride : 0);
   st->primBytes = tri ? sizeof(TriRecord) : A.blobStride;
@@ -897,7 +897,7 @@ API const void* rtcamdGetAccelData(RTCScene h, unsigned int kind, size_t* byteSi
   const void* p = nullptr;
   size_t n = 0;
   switch (kind) {
-  case 0: p = A.nodes.data(); n = A.nodes.size() * sizeof(QNode8); break;
+  case 0: p = A.nodeData(); n = A.nodeCount() * A.nodeStride(); break;
   case 1: p = A.prims.data(); n = A.prims.size() * sizeof(TriRecord); break;
   case 2: p = A.blobs.data(); n = A.blobs.size(); break;
   case 3: p = A.blobOffsets.data(); n = A.blobOffsets.size() * 4; break;

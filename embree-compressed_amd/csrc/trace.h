@@ -122,8 +122,8 @@ uint32_t trace_grid_blocks(uint32_t count, int numCUs, uint32_t rayChunk);
 hipError_t launch_trace_tri(const LaunchParams& p, hipStream_t stream);       // trace_tri.hip
 hipError_t launch_cull(const LaunchParams& p, hipStream_t stream);            // trace_tri.hip (trace_cull.hip.h): root cull pre-pass
 hipError_t launch_trace_quad(const LaunchParams& p, hipStream_t stream);      // trace_quad.hip
-hipError_t launch_trace_trimb(const LaunchParams& p, hipStream_t stream);     // trace_tri_mb.hip
-hipError_t launch_trace_quadmb(const LaunchParams& p, hipStream_t stream);    // trace_quad_mb.hip
+hipError_t launch_trace_trimb(const LaunchParams& p, hipStream_t stream);     // trace_tri_mb.hip (swept and linear-bounds kinds)
+hipError_t launch_trace_quadmb(const LaunchParams& p, hipStream_t stream);    // trace_quad_mb.hip (swept and linear-bounds kinds)
 hipError_t launch_trace_grid(const LaunchParams& p, hipStream_t stream);      // trace_grid.hip
 hipError_t launch_trace_cbvh_box(const LaunchParams& p, hipStream_t stream);  // trace_cbvh_box.hip
 hipError_t launch_trace_cbvh_leaf(const LaunchParams& p, hipStream_t stream); // trace_cbvh_leaf.hip
@@ -159,9 +159,13 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_QUAD_PLUECKER:
   case ACCEL_QUAD_MOELLER: return launch_trace_quad(p, stream);
   case ACCEL_TRIMB_PLUECKER:
-  case ACCEL_TRIMB_MOELLER: return launch_trace_trimb(p, stream);
+  case ACCEL_TRIMB_MOELLER:
+  case ACCEL_TRIMB_LINEAR_PLUECKER:
+  case ACCEL_TRIMB_LINEAR_MOELLER: return launch_trace_trimb(p, stream);
   case ACCEL_QUADMB_PLUECKER:
-  case ACCEL_QUADMB_MOELLER: return launch_trace_quadmb(p, stream);
+  case ACCEL_QUADMB_MOELLER:
+  case ACCEL_QUADMB_LINEAR_PLUECKER:
+  case ACCEL_QUADMB_LINEAR_MOELLER: return launch_trace_quadmb(p, stream);
   case ACCEL_INST_TRI_PLUECKER:
   case ACCEL_INST_TRI_MOELLER:
   case ACCEL_INST_PLUECKER:

@@ -82,6 +82,17 @@ enum : int { DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_XOR3 = 0x1B, DPP_HALF_MIRROR 
 template <typename Leaf, typename = void> struct leaf_two_stage { static constexpr bool value = false; };
 template <typename Leaf> struct leaf_two_stage<Leaf, decltype((void)Leaf::TWO_STAGE)> { static constexpr bool value = Leaf::TWO_STAGE; };
 
+// leaves of accels whose nodes are time-dependent (accel.h QNodeMB8, mb_bounds=linear) declare `static constexpr bool NODE_MB = true`: both
+// forms of the node step then load a 144-byte node and interpolate every plane, in grid units, to the ray's time before the one decode:
+//   plane = madd(madd(t, float(q1) - float(q0), float(q0)), scale, origin),   t = the ray's time clamped to [0, 1]
+// (three more VALU instructions per plane than the static decode: one byte conversion, one subtraction, one madd; a box-plus-delta
+// layout would need a ninth bit per plane and save only the subtraction).  The slab test, the ranking, the tie rules, push and pop are
+// the code below, untouched; every other instantiation compiles to the instructions it had (tools/kernel_metadata.py --digest).
+// The time is one VGPR per lane, read with the ray and clamped once; the octet form fetches it from the owning lane's register with
+// one ds_bpermute per pass (the exchange rows are full, and another word per row would take the workgroup past 40 960 B of LDS).
+template <typename Leaf, typename = void> struct leaf_node_mb { static constexpr bool value = false; };
+template <typename Leaf> struct leaf_node_mb<Leaf, decltype((void)Leaf::NODE_MB)> { static constexpr bool value = Leaf::NODE_MB; };
+
 template <int CTRL> __device__ __forceinline__ uint32_t dpp_u32(uint32_t v)
 {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
@@ -174,10 +185,17 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
     __syncthreads(); // the only workgroup barrier: the waves leave the loop below at different times
   }
 
+  constexpr bool NODE_MB = leaf_node_mb<Leaf>::value;
   WorkCounters wc;
   RayState r;
   TravRay<ROBUST> tr;
   float travFar = 0.f;
+  float nodeTime = 0.f; // NODE_MB: the ray's time, clamped to [0, 1] (a NaN becomes 0)
+  // plane of a child from its byte at time 0 (word w0) and at time 1 (word w1, NODE_MB only), byte kk of the word
+  auto plane = [&](uint32_t w0, uint32_t w1, int kk, float s, float o) -> float {
+    if constexpr (NODE_MB) return madd(madd(nodeTime, q2f(w1, kk) - q2f(w0, kk), q2f(w0, kk)), s, o);
+    else return madd(q2f(w0, kk), s, o);
+  };
   uint32_t sp = 0, cur = REF_EMPTY, rayIdx = 0;
   // lane state bits (vector register, see RayState::hit): ST_ACTIVE = the lane owns a ray, ST_POP = its next event is a pop
   // ST_WALK (two-stage leaves): the ray passed the cheap first stage of its leaf and waits for the walk
@@ -340,6 +358,7 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
             r.dx = x[4]; r.dy = x[5]; r.dz = x[6]; r.tfar = x[7];
           } else
             load_ray<VEC>(rp, r);
+          if constexpr (NODE_MB) nodeTime = fminf(fmaxf(((const float*)rp)[7], 0.0f), 1.0f);
           r.hit = 0u;
           // stream front-end: rays with tnear > tfar are skipped (bvh_intersector_stream_filters.cpp:156);
           // occluded: already-occluded rays return early (bvh_intersector1.cpp:132-134)
@@ -412,13 +431,17 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
           uint32_t oSp = __float_as_uint(x[9]);
           const uint32_t oTid = __float_as_uint(x[10]);
           const float rTfar = x[11]; // ray.tfar, for the distance cull of popped entries
+          float oTime = 0.f; // NODE_MB: the time of the octet's ray, from the owning lane (all 64 lanes are in here: the loop is wave-uniform)
+          if constexpr (NODE_MB) oTime = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)((oTid & 63u) << 2), (int)__float_as_uint(nodeTime)));
           const bool ngx = t.negx(), ngy = t.negy(), ngz = t.negz();
           bool done = !(row < nNode); // uniform within an octet
           uint32_t steps = 0;
           while (__ballot(!done) != 0ull) {
             if (!done) {
               if (COUNT && k == 0u) wc.nodes++;
-              const unsigned char* nb = (const unsigned char*)(nodes + oCur);
+              const unsigned char* nb;
+              if constexpr (NODE_MB) nb = (const unsigned char*)((const QNodeMB8*)nodes + oCur);
+              else nb = (const unsigned char*)(nodes + oCur);
               const uint4 n0 = *(const uint4*)nb;
               const uint32_t cref = ((const uint32_t*)nb)[4u + k];
               // plane bytes: lower[0..7] at 48/64/80, upper[0..7] eight bytes further (x / y / z)
@@ -429,8 +452,22 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
               const float sx = __uint_as_float((n0.w & 0xffu) << 23);
               const float sy = __uint_as_float(((n0.w >> 8) & 0xffu) << 23);
               const float sz = __uint_as_float(((n0.w >> 16) & 0xffu) << 23);
-              const float npx = madd((float)qnx, sx, ox), npy = madd((float)qny, sy, oy), npz = madd((float)qnz, sz, oz);
-              const float fpx = madd((float)qfx, sx, ox), fpy = madd((float)qfy, sy, oy), fpz = madd((float)qfz, sz, oz);
+              float npx, npy, npz, fpx, fpy, fpz;
+              if constexpr (NODE_MB) {
+                // the same bytes of the second plane block, 48 bytes further (QNodeMB8::q1)
+                const uint32_t rnx = nb[96u + (ngx ? 8u : 0u) + k], rfx = nb[96u + (ngx ? 0u : 8u) + k];
+                const uint32_t rny = nb[112u + (ngy ? 8u : 0u) + k], rfy = nb[112u + (ngy ? 0u : 8u) + k];
+                const uint32_t rnz = nb[128u + (ngz ? 8u : 0u) + k], rfz = nb[128u + (ngz ? 0u : 8u) + k];
+                npx = madd(madd(oTime, (float)rnx - (float)qnx, (float)qnx), sx, ox);
+                npy = madd(madd(oTime, (float)rny - (float)qny, (float)qny), sy, oy);
+                npz = madd(madd(oTime, (float)rnz - (float)qnz, (float)qnz), sz, oz);
+                fpx = madd(madd(oTime, (float)rfx - (float)qfx, (float)qfx), sx, ox);
+                fpy = madd(madd(oTime, (float)rfy - (float)qfy, (float)qfy), sy, oy);
+                fpz = madd(madd(oTime, (float)rfz - (float)qfz, (float)qfz), sz, oz);
+              } else {
+                npx = madd((float)qnx, sx, ox), npy = madd((float)qny, sy, oy), npz = madd((float)qnz, sz, oz);
+                fpx = madd((float)qfx, sx, ox), fpy = madd((float)qfy, sy, oy), fpz = madd((float)qfz, sz, oz);
+              }
               const float tN = fmaxf(t.nearT(npx, npy, npz), t.tnear);
               const float tF = fminf(t.farT(fpx, fpy, fpz), oFar);
               const bool h = (tN <= tF) & (cref != REF_EMPTY);
@@ -519,8 +556,12 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
     }
     else if (atNode) {
       if (COUNT) wc.nodes++;
-      const uint4* np = (const uint4*)(nodes + cur);
+      const uint4* np;
+      if constexpr (NODE_MB) np = (const uint4*)((const QNodeMB8*)nodes + cur);
+      else np = (const uint4*)(nodes + cur);
       const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3], n4 = np[4], n5 = np[5];
+      uint4 n6 = n3, n7 = n4, n8 = n5; // NODE_MB: the plane block of time 1 (otherwise unused)
+      if constexpr (NODE_MB) { n6 = np[6]; n7 = np[7]; n8 = np[8]; }
       const float ox = __uint_as_float(n0.x), oy = __uint_as_float(n0.y), oz = __uint_as_float(n0.z);
       const float sx = __uint_as_float((n0.w & 0xffu) << 23);
       const float sy = __uint_as_float(((n0.w >> 8) & 0xffu) << 23);
@@ -533,6 +574,13 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
       const uint32_t fy0 = ngy ? n4.x : n4.z, fy1 = ngy ? n4.y : n4.w;
       const uint32_t nz0 = ngz ? n5.z : n5.x, nz1 = ngz ? n5.w : n5.y;
       const uint32_t fz0 = ngz ? n5.x : n5.z, fz1 = ngz ? n5.y : n5.w;
+      // the same selection in the block of time 1 (used by plane() under NODE_MB only)
+      const uint32_t rnx0 = ngx ? n6.z : n6.x, rnx1 = ngx ? n6.w : n6.y;
+      const uint32_t rfx0 = ngx ? n6.x : n6.z, rfx1 = ngx ? n6.y : n6.w;
+      const uint32_t rny0 = ngy ? n7.z : n7.x, rny1 = ngy ? n7.w : n7.y;
+      const uint32_t rfy0 = ngy ? n7.x : n7.z, rfy1 = ngy ? n7.y : n7.w;
+      const uint32_t rnz0 = ngz ? n8.z : n8.x, rnz1 = ngz ? n8.w : n8.y;
+      const uint32_t rfz0 = ngz ? n8.x : n8.z, rfz1 = ngz ? n8.y : n8.w;
       const uint32_t cref[8] = {n1.x, n1.y, n1.z, n1.w, n2.x, n2.y, n2.z, n2.w};
 
       uint32_t dist[8];
@@ -540,12 +588,12 @@ __device__ __forceinline__ void trace_body(const LaunchParams& P, uint2 (*ldsSta
 #pragma unroll
       for (int k = 0; k < 8; k++) {
         const int kk = k & 3;
-        const float npx = madd(q2f(k < 4 ? nx0 : nx1, kk), sx, ox);
-        const float npy = madd(q2f(k < 4 ? ny0 : ny1, kk), sy, oy);
-        const float npz = madd(q2f(k < 4 ? nz0 : nz1, kk), sz, oz);
-        const float fpx = madd(q2f(k < 4 ? fx0 : fx1, kk), sx, ox);
-        const float fpy = madd(q2f(k < 4 ? fy0 : fy1, kk), sy, oy);
-        const float fpz = madd(q2f(k < 4 ? fz0 : fz1, kk), sz, oz);
+        const float npx = plane(k < 4 ? nx0 : nx1, k < 4 ? rnx0 : rnx1, kk, sx, ox);
+        const float npy = plane(k < 4 ? ny0 : ny1, k < 4 ? rny0 : rny1, kk, sy, oy);
+        const float npz = plane(k < 4 ? nz0 : nz1, k < 4 ? rnz0 : rnz1, kk, sz, oz);
+        const float fpx = plane(k < 4 ? fx0 : fx1, k < 4 ? rfx0 : rfx1, kk, sx, ox);
+        const float fpy = plane(k < 4 ? fy0 : fy1, k < 4 ? rfy0 : rfy1, kk, sy, oy);
+        const float fpz = plane(k < 4 ? fz0 : fz1, k < 4 ? rfz0 : rfz1, kk, sz, oz);
         const float tN = fmaxf(tr.nearT(npx, npy, npz), tr.tnear);
         const float tF = fminf(tr.farT(fpx, fpy, fpz), travFar);
         const bool h = (tN <= tF) & (cref[k] != REF_EMPTY);

@@ -141,12 +141,20 @@ template <bool PLUECKER> struct QuadMBLeaf : LeafTraits
   }
 };
 
+// The same leaf under time-dependent nodes (mb_bounds=linear, accel.h QNodeMB8): only the node step of trace_loop.hip.h differs.
+template <bool PLUECKER> struct QuadMBLeafLinear : QuadMBLeaf<PLUECKER>
+{
+  static constexpr bool NODE_MB = true;
+};
+
 } // namespace dev
 
 hipError_t launch_trace_quadmb(const LaunchParams& p, hipStream_t stream)
 {
   // Pluecker <-> robust traversal, Moeller <-> fast traversal, as for the static quads; lane kernel only (rt_trace.cpp launch_on
   // never asks for the ray-pool skeleton on this accel)
+  if (p.accel.kind == ACCEL_QUADMB_LINEAR_PLUECKER) return dev::launch_leaf<dev::QuadMBLeafLinear<true>, true>(p, stream);
+  if (p.accel.kind == ACCEL_QUADMB_LINEAR_MOELLER) return dev::launch_leaf<dev::QuadMBLeafLinear<false>, false>(p, stream);
   if (p.accel.kind == ACCEL_QUADMB_PLUECKER) return dev::launch_leaf<dev::QuadMBLeaf<true>, true>(p, stream);
   return dev::launch_leaf<dev::QuadMBLeaf<false>, false>(p, stream);
 }

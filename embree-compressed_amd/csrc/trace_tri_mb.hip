@@ -158,12 +158,20 @@ template <bool PLUECKER> struct TriMBLeaf : LeafTraits
   }
 };
 
+// The same leaf under time-dependent nodes (mb_bounds=linear, accel.h QNodeMB8): only the node step of trace_loop.hip.h differs.
+template <bool PLUECKER> struct TriMBLeafLinear : TriMBLeaf<PLUECKER>
+{
+  static constexpr bool NODE_MB = true;
+};
+
 } // namespace dev
 
 hipError_t launch_trace_trimb(const LaunchParams& p, hipStream_t stream)
 {
   // Pluecker <-> robust traversal, Moeller <-> fast traversal, as for the static triangles; lane kernel only (rt_trace.cpp launch_on
   // never asks for the ray-pool skeleton on this accel)
+  if (p.accel.kind == ACCEL_TRIMB_LINEAR_PLUECKER) return dev::launch_leaf<dev::TriMBLeafLinear<true>, true>(p, stream);
+  if (p.accel.kind == ACCEL_TRIMB_LINEAR_MOELLER) return dev::launch_leaf<dev::TriMBLeafLinear<false>, false>(p, stream);
   if (p.accel.kind == ACCEL_TRIMB_PLUECKER) return dev::launch_leaf<dev::TriMBLeaf<true>, true>(p, stream);
   return dev::launch_leaf<dev::TriMBLeaf<false>, false>(p, stream);
 }

@@ -43,6 +43,12 @@ ACCEL_INSTMESHMB_MOELLER = 23
 # bvh4.compressed.leaf below the instances
 ACCEL_INSTSUBDIV_GRID = 24
 ACCEL_INSTSUBDIV_CBVH_LEAF = 25
+# accel kinds of the motion-blur mesh accels built by a device with mb_bounds=linear: the twins of the kinds 10..13 over time-dependent
+# nodes (csrc/accel.h QNodeMB8, 144 bytes: RTCAMDSceneStats::nodeBytes)
+ACCEL_TRIMB_LINEAR_PLUECKER = 26
+ACCEL_TRIMB_LINEAR_MOELLER = 27
+ACCEL_QUADMB_LINEAR_PLUECKER = 28
+ACCEL_QUADMB_LINEAR_MOELLER = 29
 # Scene.accel_data(kind + ACCEL_DATA_INSTSUBDIV): the arrays of that second instance accel, whatever else the scene holds
 ACCEL_DATA_INSTSUBDIV = 16
 RTC_SCENE_FLAG_NONE = 0

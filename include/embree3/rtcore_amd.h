@@ -61,10 +61,13 @@ struct RTCAMDSceneStats
   size_t byteSize;          /* sizeof(struct RTCAMDSceneStats), set by the caller */
   unsigned int accelKind;   /* 0 none, 1 bvh8.triangle4v (Pluecker), 2 bvh8.triangle4 (Moeller),
                                3 cbvh.box, 4 cbvh.leaf, 5 cbvh.grid, 6 gridsoa (eager), 7 cbvh.full,
-                               8 quads (Pluecker), 9 quads (Moeller) */
+                               8 quads (Pluecker), 9 quads (Moeller),
+                               10 / 11 motion blur triangles (Pluecker / Moeller), 12 / 13 motion blur quads, 14..25 instance accels,
+                               26 / 27 motion blur triangles and 28 / 29 motion blur quads over time-dependent node boxes
+                               (device config mb_bounds=linear; nodeBytes is 144 there) */
   unsigned int branching;   /* 8 */
   size_t nodeCount;         /* quantized BVH8 nodes */
-  size_t nodeBytes;         /* bytes per node record (96) */
+  size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29) */
   size_t primCount;         /* triangles, quads, or cBVH / GridSOA leaves */
   size_t primBytes;         /* bytes per triangle record (48), per quad record (64) or mean bytes per subdiv leaf blob */
   size_t leafCount;         /* BVH8 leaves */

@@ -6,7 +6,9 @@ events around every step (the batch is restored from a pristine copy before each
   (c) at-rest  2 steps with step 1 = step 0 (96-byte records + interpolation, boxes as tight as the static ones); the same ray times
 (c) / (b) = price of the records and the interpolation, (a) / (c) = price of the swept boxes.  Both variants (Pluecker / Moeller).
 RTAMD_LIB=<other build of the library> measures (b) with that build (it need not know motion blur: pass `static` as the third argument).
-usage: motion_blur_rates.py [steps] [repeats] [static]"""
+`linear` as the third argument: the device is created with mb_bounds=linear (time-dependent node boxes, accel kinds 26 / 27) and only (a)
+and (c) are measured - linear (a) against swept (a) is what the boxes buy, linear (c) against swept (c) what the costlier node step costs.
+usage: motion_blur_rates.py [steps] [repeats] [static|linear]"""
 import importlib
 import os
 import sys
@@ -22,6 +24,7 @@ d = np.load(os.path.join(root, 'assets/bomberman.mesh.npz'))
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 only_static = len(sys.argv) > 3 and sys.argv[3] == 'static'
+linear = len(sys.argv) > 3 and sys.argv[3] == 'linear'
 n = 1 << 20
 
 
@@ -49,7 +52,7 @@ pristine = torch.from_numpy(rays.view(np.uint8).reshape(n, 80).copy()).cuda()
 
 
 def measure(kind, variant):
-    dev = rtc.Device('gpu=0')
+    dev = rtc.Device('gpu=0,mb_bounds=linear' if linear else 'gpu=0')
     sc = rtc.Scene(dev, rtc.RTC_SCENE_FLAG_ROBUST if variant == 'pluecker' else 0)
     if kind == 'static':
         sc.add_triangles(s0, tris)
@@ -84,7 +87,7 @@ def measure(kind, variant):
     dev.release()
 
 
-print(f'library: {rtc.LIB_PATH}', flush=True)
+print(f'library: {rtc.LIB_PATH}; mb_bounds={"linear" if linear else "swept"}', flush=True)
 for variant in ('pluecker', 'moeller'):
-    for kind in (('static',) if only_static else ('moving', 'static', 'at-rest')):
+    for kind in (('static',) if only_static else (('moving', 'at-rest') if linear else ('moving', 'static', 'at-rest'))):
         measure(kind, variant)

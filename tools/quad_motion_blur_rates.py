@@ -6,7 +6,9 @@ stream, kernel time by HIP events around every step (the batch is restored from 
   (c) moving   2 steps: step 1 = step 0 rotated by 20 degrees about y and moved by 0.3 x extent along x
 b / a = price of the records and the interpolation, c / b = price of the swept boxes.  Both variants (Pluecker / Moeller).
 The triangle counterpart is motion_blur_rates.py.
-usage: quad_motion_blur_rates.py [steps] [repeats]"""
+`linear` as the third argument: the device is created with mb_bounds=linear (time-dependent node boxes, accel kinds 28 / 29) and only (b)
+and (c) are measured.
+usage: quad_motion_blur_rates.py [steps] [repeats] [linear]"""
 import importlib
 import os
 import sys
@@ -21,6 +23,7 @@ root = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 d = np.load(os.path.join(root, 'assets/bomberman.mesh.npz'))
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+linear = len(sys.argv) > 3 and sys.argv[3] == 'linear'
 n = 1 << 20
 
 
@@ -49,7 +52,7 @@ pristine = torch.from_numpy(rays.view(np.uint8).reshape(n, 80).copy()).cuda()
 
 
 def measure(kind, variant):
-    dev = rtc.Device('gpu=0')
+    dev = rtc.Device('gpu=0,mb_bounds=linear' if linear else 'gpu=0')
     sc = rtc.Scene(dev, rtc.RTC_SCENE_FLAG_ROBUST if variant == 'pluecker' else 0)
     if kind == 'static':
         sc.add_quads(s0, quads)
@@ -85,7 +88,11 @@ def measure(kind, variant):
     return med
 
 
-print(f'library: {rtc.LIB_PATH}', flush=True)
+print(f'library: {rtc.LIB_PATH}; mb_bounds={"linear" if linear else "swept"}', flush=True)
 for variant in ('pluecker', 'moeller'):
+    if linear:
+        b, c = (measure(kind, variant) for kind in ('at-rest', 'moving'))
+        print(f'{variant}: c/b (linear boxes) = {c / b:.2f}', flush=True)
+        continue
     a, b, c = (measure(kind, variant) for kind in ('static', 'at-rest', 'moving'))
     print(f'{variant}: b/a (records + interpolation) = {b / a:.3f}, c/b (swept boxes) = {c / b:.2f}', flush=True)

@@ -220,6 +220,19 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // Every rebased first record must stay below 2^26.  Inside an instance the trees are traversed one after the other, each against the
 // tfar the previous one left; while a tree is traversed the later ones wait on the stack as markers (REF_INST_TREE).
 //
+// Kinds ACCEL_INSTMESHMB_LINEAR_PLUECKER / _MOELLER (inst_mb_bounds=linear over scenes built under mb_bounds=linear): `prims` and `blobs`
+// are those of the kinds ACCEL_INSTMESHMB_*; the motion-blur trees keep their time-dependent nodes, so the node array has two sections:
+//   nodes : top-level tree | every scene's static triangle and quad trees (QNode8, in the order above without the motion-blur trees) |
+//           zero padding up to a multiple of 144 bytes from the start of the buffer |
+//           scene 0: MB triangle, MB quad nodes | scene 1: ... | ...                                          (QNodeMB8)
+// A child or root reference inside a motion-blur tree indexes the buffer as ONE array of QNodeMB8: (the section's byte offset) / 144 +
+// the node's place in the section (below 2^31, or the commit is refused).  The QNodeMB8s are the instanced scene's own nodes, byte for
+// byte apart from the rebased child words, so the containment guarantee of QNodeMB8 holds below an instance as it stands.  The
+// top-level tree and the boxes of moving instances are QNode8s over swept boxes as in all instance kinds.  Which node type a reference
+// names follows from where it was found: the roots triMBRoot / quadMBRoot of an InstanceSceneRecord and every child below them name
+// QNodeMB8s, everything else QNode8s (the kernel keeps the tree's code in its lane state, INST_TREE_*: bit 1 = a motion-blur tree).
+// blobOffsets holds two words for inspection: the number of QNodeMB8s and the index of the first one, in 144-byte units.
+//
 // Kinds ACCEL_INSTSUBDIV_GRID / ACCEL_INSTSUBDIV_CBVH_LEAF (Scene::instSubdivAccel, an accel of its own beside the one above): instances
 // of scenes that hold subdivision meshes only, all with the eager accel or all with bvh4.compressed.leaf at one compression level C.  Per
 // distinct instanced scene, stored once, in the order of first use:
@@ -375,17 +388,28 @@ enum AccelKind : uint32_t
   ACCEL_TRIMB_LINEAR_PLUECKER = 26,
   ACCEL_TRIMB_LINEAR_MOELLER = 27,
   ACCEL_QUADMB_LINEAR_PLUECKER = 28,
-  ACCEL_QUADMB_LINEAR_MOELLER = 29
+  ACCEL_QUADMB_LINEAR_MOELLER = 29,
+  // inst_mb_bounds=linear: the kinds 22 / 23 when at least one instanced scene's motion-blur accel is of the kinds 26..29.  `nodes` holds
+  // two sections, QNode8s and then QNodeMB8s (see InstanceRecord); `blobs` and `prims` are those of the kinds 22 / 23
+  ACCEL_INSTMESHMB_LINEAR_PLUECKER = 30,
+  ACCEL_INSTMESHMB_LINEAR_MOELLER = 31
 };
-inline bool is_instance_kind(uint32_t kind) { return kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF; } // traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip
+inline bool is_inst_linear_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_LINEAR_PLUECKER || kind == ACCEL_INSTMESHMB_LINEAR_MOELLER; } // traced by trace_instance_mesh_mb_linear.hip
+// traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip / trace_instance_mesh_mb_linear.hip
+inline bool is_instance_kind(uint32_t kind) { return (kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF) || is_inst_linear_kind(kind); }
 
 inline bool is_mb_linear_kind(uint32_t kind) { return kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER; } // nodes are QNodeMB8
+// the arithmetic of a motion-blur mesh accel, under swept and under linear bounds
+inline bool is_mb_pluecker_kind(uint32_t kind)
+{
+  return kind == ACCEL_TRIMB_PLUECKER || kind == ACCEL_QUADMB_PLUECKER || kind == ACCEL_TRIMB_LINEAR_PLUECKER || kind == ACCEL_QUADMB_LINEAR_PLUECKER;
+}
 inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKER && kind <= ACCEL_QUADMB_MOELLER) || is_mb_linear_kind(kind); } // lane kernel only, no service kernel
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
 {
-  const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*
+  const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_*
   const TriRecord* prims;
   const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16

@@ -45,6 +45,10 @@ void Device::parse(const std::string& cfg)
       if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "mb_bounds=: unknown value '" + val + "' (swept or linear)");
       mb_bounds = val;
     }
+    else if (key == "inst_mb_bounds") {
+      if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "inst_mb_bounds=: unknown value '" + val + "' (swept or linear)");
+      inst_mb_bounds = val;
+    }
     else if (key == "verbose") verbose = atoi(val.c_str());
     else if (key == "gpu" || key == "device") { gpu = (val == "none") ? -1 : atoi(val.c_str()); gpuList.clear(); }
     else if (key == "gpus") {

@@ -31,6 +31,7 @@ struct Device : RefCounted
   std::string tri_accel_mb = "default"; // triangle meshes with more than one time step
   std::string quad_accel_mb = "default"; // quad meshes with more than one time step
   std::string mb_bounds = "swept"; // node boxes of the motion-blur mesh accels: "swept" (one box over the whole shutter, QNode8) or "linear" (time-dependent, QNodeMB8)
+  std::string inst_mb_bounds = "swept"; // node boxes of motion-blur trees below an instance: "swept" (scenes built under mb_bounds=linear are refused below an instance) or "linear" (such scenes keep their QNodeMB8s, kinds ACCEL_INSTMESHMB_LINEAR_*)
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
@@ -331,7 +332,9 @@ struct Geometry : RefCounted
 struct Accel
 {
   std::vector<QNode8> nodes;
-  std::vector<QNodeMB8> nodesMB; // the kinds ACCEL_*MB_LINEAR_* (mb_bounds=linear): their time-dependent nodes, `nodes` is empty then
+  std::vector<QNodeMB8> nodesMB; // the kinds ACCEL_*MB_LINEAR_* (mb_bounds=linear): their time-dependent nodes, `nodes` is empty then;
+                                 // the kinds ACCEL_INSTMESHMB_LINEAR_*: the second section of the node array, behind `nodes`
+  std::vector<uint8_t> nodeImage; // the kinds ACCEL_INSTMESHMB_LINEAR_*: `nodes` | zero padding to a multiple of 144 bytes | `nodesMB`, as uploaded
   std::vector<TriRecord> prims;
   std::vector<uint8_t> blobs;
   std::vector<uint32_t> blobOffsets;
@@ -353,10 +356,15 @@ struct Accel
   std::vector<DevCopy> dev;
   std::vector<int> devOrdinals; // ordinal each copy lives on (for freeDevice)
   AccelDesc desc(size_t shard = 0) const;
-  // the node array whichever of the two it is: what is uploaded, counted and handed out for inspection
+  // the node array whichever of the two it is: what is counted and - see nodeImage*() - uploaded and handed out for inspection.  The kinds
+  // ACCEL_INSTMESHMB_LINEAR_* hold both: these three describe their QNode8 section (top-level tree and static trees), the QNodeMB8 section
+  // is described by the accel's two blobOffsets words
   size_t nodeCount() const { return is_mb_linear_kind(kind) ? nodesMB.size() : nodes.size(); }
   size_t nodeStride() const { return is_mb_linear_kind(kind) ? sizeof(QNodeMB8) : sizeof(QNode8); }
   const void* nodeData() const { return is_mb_linear_kind(kind) ? (const void*)nodesMB.data() : (const void*)nodes.data(); }
+  // the bytes of the device's node buffer
+  size_t nodeImageBytes() const { return is_inst_linear_kind(kind) ? nodeImage.size() : nodeCount() * nodeStride(); }
+  const void* nodeImageData() const { return is_inst_linear_kind(kind) ? (const void*)nodeImage.data() : nodeData(); }
   bool traceable() const { return kind != ACCEL_NONE && root != REF_EMPTY; } // a launch on anything else returns before it touches the GPU
   size_t deviceBytes() const;
   void upload(Device* dev);

@@ -162,7 +162,7 @@ AccelDesc Accel::desc(size_t shard) const
 
 size_t Accel::deviceBytes() const
 {
-  return nodeCount() * nodeStride() + prims.size() * sizeof(TriRecord) + blobs.size() + blobOffsets.size() * 4;
+  return nodeImageBytes() + prims.size() * sizeof(TriRecord) + blobs.size() + blobOffsets.size() * 4;
 }
 
 void Accel::freeDevice()
@@ -184,6 +184,7 @@ void Accel::clear()
 {
   nodes.clear();
   nodesMB.clear();
+  nodeImage.clear();
   prims.clear();
   blobs.clear();
   blobOffsets.clear();
@@ -216,7 +217,7 @@ void Accel::upload(Device* device)
     sh.use();
     devOrdinals[i] = sh.ordinal;
     DevCopy& c = dev[i];
-    c.dNodes = upload_array(sh.stream, nodeData(), nodeCount() * nodeStride());
+    c.dNodes = upload_array(sh.stream, nodeImageData(), nodeImageBytes());
     c.dPrims = upload_array(sh.stream, prims.data(), prims.size() * sizeof(TriRecord));
     c.dBlobs = upload_array(sh.stream, blobs.data(), blobs.size());
     c.dBlobOffsets = upload_array(sh.stream, blobOffsets.data(), blobOffsets.size() * 4);
@@ -677,6 +678,14 @@ static V3 xfm_point(const float* m, V3 q)
 // extends them by the swept boxes).  A host-only device takes such scenes only when its config names inst_accel= and one of
 // tri_accel_mb= / quad_accel_mb= (Device::inst_mesh_motion_enabled); a top scene without a motion-blur accel below it keeps the kinds
 // 14..21 and their arrays.
+// Linear node bounds below an instance (inst_mb_bounds=linear, Device::inst_mb_bounds; on a host-only device only where motion-blur
+// meshes below an instance are taken at all): an instanced scene whose motion-blur accels were built under mb_bounds=linear (kinds
+// 26..29) is then placed with its QNodeMB8s, and as soon as there is one the kinds are ACCEL_INSTMESHMB_LINEAR_*: `prims` and `blobs`
+// as in the kinds ACCEL_INSTMESHMB_*, the node array in two sections (accel.h InstanceRecord) - `A.nodes` with the top-level tree and
+// the static trees, `A.nodesMB` with the motion-blur trees, child indices counted in 144-byte units from the start of the uploaded
+// buffer, and `A.nodeImage` the two with the padding between them.  One device has one mb_bounds and an instance cannot name a scene
+// of another device (Geometry::setInstancedScene), so the motion-blur trees below one top scene are all of one node type.  Without
+// the key such a scene is refused as before; with it and no such scene the accel is what it is without the key.
 // Subdivision scenes below an instance: an instanced scene that enables a subdivision mesh is left to build_instance_subdiv_accel (a
 // second accel of the top scene; this one and its kinds stay what they are) when the device takes such scenes
 // (Device::inst_subdiv_enabled); otherwise it is refused here with the message of the config, as before.
@@ -715,6 +724,8 @@ static void build_instance_accel(Scene* s)
   std::vector<Src> src;
   std::vector<BuildPrim> bp;
   bool haveKind = false, pluecker = false, anyQuads = false, anyMotion = false, anyMeshMotion = false;
+  const bool linearOk = meshMotionOk && s->device->inst_mb_bounds == "linear";
+  bool anyLinear = false, anySwept = false; // traceable motion-blur accels of the kinds 26..29 / 10..13 below this scene
   uint32_t pendingMax = 0; // most trees of one instanced scene, minus one
   unsigned kindGeom = 0;   // the instance whose scene fixed the arithmetic, and the accels that scene has: for the refusal below
   std::string kindNames;
@@ -726,8 +737,9 @@ static void build_instance_accel(Scene* s)
     if (!o) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance without an instanced scene");
     if (o->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instanced scene got not committed");
     if (subdivOk && is_subdivision_scene(o)) continue; // build_instance_subdiv_accel places it
-    // the instanced scenes' trees are copied behind the top-level tree as QNode8s: time-dependent nodes have no place there
-    if (is_mb_linear_kind(o->triMBAccel.kind) || is_mb_linear_kind(o->quadMBAccel.kind))
+    // without inst_mb_bounds=linear the instanced scenes' trees are copied behind the top-level tree as QNode8s: time-dependent nodes
+    // have no place there
+    if (!linearOk && (is_mb_linear_kind(o->triMBAccel.kind) || is_mb_linear_kind(o->quadMBAccel.kind)))
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene with a motion blur accel built under mb_bounds=linear is not supported (instance accels hold swept node boxes: use mb_bounds=swept)");
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
@@ -754,9 +766,9 @@ static void build_instance_accel(Scene* s)
     if (trisMB || quadsMB) {
       // one arithmetic per top scene, over all four trees of every instanced scene
       struct { bool have, pl; const char* name; } const t[4] = {{tris, o->triAccel.kind == ACCEL_TRI_PLUECKER, "triangle"},
-                                                                {trisMB, o->triMBAccel.kind == ACCEL_TRIMB_PLUECKER, "motion blur triangle"},
+                                                                {trisMB, is_mb_pluecker_kind(o->triMBAccel.kind), "motion blur triangle"},
                                                                 {quads, o->quadAccel.kind == ACCEL_QUAD_PLUECKER, "quad"},
-                                                                {quadsMB, o->quadMBAccel.kind == ACCEL_QUADMB_PLUECKER, "motion blur quad"}};
+                                                                {quadsMB, is_mb_pluecker_kind(o->quadMBAccel.kind), "motion blur quad"}};
       std::string pl, mo;
       for (const auto& e : t)
         if (e.have) (e.pl ? pl : mo) += std::string((e.pl ? pl : mo).empty() ? "" : ", ") + e.name;
@@ -765,6 +777,8 @@ static void build_instance_accel(Scene* s)
       const bool scenePl = !pl.empty();
       if (haveKind && scenePl != pluecker) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(scenePl));
       anyMeshMotion = true;
+      for (const Accel* m : {trisMB ? &o->triMBAccel : nullptr, quadsMB ? &o->quadMBAccel : nullptr})
+        if (m) (is_mb_linear_kind(m->kind) ? anyLinear : anySwept) = true;
     }
     pendingMax = std::max(pendingMax, (uint32_t)tris + (uint32_t)trisMB + (uint32_t)quads + (uint32_t)quadsMB - 1u);
     // the kernel runs ONE arithmetic on both levels and in both leaves: every accel below this scene is Pluecker / robust, or every one
@@ -774,7 +788,7 @@ static void build_instance_accel(Scene* s)
                                             "as a robust scene under quad_accel=bvh8.quad4v builds them): instances need one arithmetic");
     const bool pl = tris ? o->triAccel.kind == ACCEL_TRI_PLUECKER
                   : quads ? o->quadAccel.kind == ACCEL_QUAD_PLUECKER
-                  : trisMB ? o->triMBAccel.kind == ACCEL_TRIMB_PLUECKER : o->quadMBAccel.kind == ACCEL_QUADMB_PLUECKER;
+                  : is_mb_pluecker_kind(trisMB ? o->triMBAccel.kind : o->quadMBAccel.kind);
     if (haveKind && pl != pluecker) {
       if (!anyQuads && !quads && !anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
       if (anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(pl));
@@ -800,6 +814,7 @@ static void build_instance_accel(Scene* s)
   }
   if (bp.empty()) return;
   if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances for the 26-bit leaf reference");
+  if (anyLinear && anySwept) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: motion blur accels of both node types below one scene");
 
   // top-level tree, one instance per leaf: leaf reference = record index, count 1
   std::vector<InstanceRecord> recs(bp.size());
@@ -841,6 +856,27 @@ static void build_instance_accel(Scene* s)
     deepest = std::max(deepest, O.maxDepth);
     return rebase(O.root);
   };
+  // ACCEL_INSTMESHMB_LINEAR_*: the same for a tree of QNodeMB8s, into the second section of the node array, which starts mbNodeBase
+  // 144-byte units into the buffer (computed below, from the number of QNode8s in front)
+  size_t mbNodeBase = 0;
+  auto append_tree_mb = [&](const Accel& O, size_t leafBase) -> uint32_t {
+    if (!O.traceable()) return REF_EMPTY;
+    const size_t nodeBase = mbNodeBase + A.nodesMB.size();
+    if (nodeBase + O.nodesMB.size() >= (size_t)REF_LEAF)
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced motion blur nodes for the 31-bit node reference (they follow all other nodes in one buffer, counted in 144-byte units)");
+    auto rebase = [&](uint32_t ref) -> uint32_t {
+      if (ref == REF_EMPTY) return ref;
+      if (ref & REF_LEAF) return ref + (uint32_t)leafBase;
+      return ref + (uint32_t)nodeBase;
+    };
+    for (QNodeMB8 n : O.nodesMB) {
+      for (uint32_t& c : n.child) c = rebase(c);
+      A.nodesMB.push_back(n);
+    }
+    deepest = std::max(deepest, O.maxDepth);
+    return rebase(O.root);
+  };
+  auto append_mb = [&](const Accel& O, size_t leafBase) -> uint32_t { return anyLinear ? append_tree_mb(O, leafBase) : append_tree(O, leafBase); };
   // ACCEL_INSTMESHMB_*: where the sections of `blobs` start follows from the counts of everything in front of them
   std::vector<InstanceSceneRecord> sceneRecs;
   std::map<Scene*, uint32_t> sceneRecOf; // -> index into sceneRecs
@@ -848,7 +884,7 @@ static void build_instance_accel(Scene* s)
   std::vector<QuadMBRecord> quadMBRecs;
   size_t numSteps = 0, sceneRecBase = 0, triMBOffset = 0, quadMBOffset = 0; // sceneRecBase in 64-byte units, the offsets in bytes
   if (anyMeshMotion) {
-    size_t nQuads = 0, nTriMB = 0, nScenes = 0;
+    size_t nQuads = 0, nTriMB = 0, nScenes = 0, nQNodes = A.nodes.size();
     std::map<Scene*, int> seen;
     for (const Src& sr : src) {
       const size_t n = s->geometries[sr.geomID]->local2world.size();
@@ -857,7 +893,10 @@ static void build_instance_accel(Scene* s)
       nScenes++;
       if (sr.scene->quadAccel.traceable()) nQuads += sr.scene->quadAccel.blobs.size() / sizeof(QuadRecord);
       if (sr.scene->triMBAccel.traceable()) nTriMB += sr.scene->triMBAccel.blobs.size() / sizeof(TriMBRecord);
+      for (const Accel* st : {&sr.scene->triAccel, &sr.scene->quadAccel})
+        if (st->traceable()) nQNodes += st->nodes.size();
     }
+    mbNodeBase = (nQNodes * sizeof(QNode8) + sizeof(QNodeMB8) - 1) / sizeof(QNodeMB8);
     sceneRecBase = recs.size() + nQuads + numSteps;
     triMBOffset = ((sceneRecBase + nScenes) * sizeof(InstanceRecord) + sizeof(TriMBRecord) - 1) / sizeof(TriMBRecord) * sizeof(TriMBRecord);
     quadMBOffset = (triMBOffset + nTriMB * sizeof(TriMBRecord) + sizeof(QuadMBRecord) - 1) / sizeof(QuadMBRecord) * sizeof(QuadMBRecord);
@@ -880,7 +919,7 @@ static void build_instance_accel(Scene* s)
       if (base + n >= ((size_t)1 << TRI_START_BITS))
         RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced motion blur triangle segments for the 26-bit leaf reference (their records follow the instance, quad, step and "
                                               "scene records in one array)");
-      sc.triMBRoot = append_tree(TM, base);
+      sc.triMBRoot = append_mb(TM, base);
       const TriMBRecord* t = (const TriMBRecord*)TM.blobs.data();
       triMBRecs.insert(triMBRecs.end(), t, t + n);
     }
@@ -902,7 +941,7 @@ static void build_instance_accel(Scene* s)
       const size_t n = QM.blobs.size() / sizeof(QuadMBRecord), base = quadMBOffset / sizeof(QuadMBRecord) + quadMBRecs.size();
       if (base + n >= ((size_t)1 << TRI_START_BITS))
         RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced motion blur quad segments for the 26-bit leaf reference (their records follow all other records in one array)");
-      sc.quadMBRoot = append_tree(QM, base);
+      sc.quadMBRoot = append_mb(QM, base);
       const QuadMBRecord* q = (const QuadMBRecord*)QM.blobs.data();
       quadMBRecs.insert(quadMBRecs.end(), q, q + n);
     }
@@ -938,7 +977,8 @@ static void build_instance_accel(Scene* s)
       }
     }
   }
-  if (anyMeshMotion) A.kind = pluecker ? ACCEL_INSTMESHMB_PLUECKER : ACCEL_INSTMESHMB_MOELLER;
+  if (anyLinear) A.kind = pluecker ? ACCEL_INSTMESHMB_LINEAR_PLUECKER : ACCEL_INSTMESHMB_LINEAR_MOELLER;
+  else if (anyMeshMotion) A.kind = pluecker ? ACCEL_INSTMESHMB_PLUECKER : ACCEL_INSTMESHMB_MOELLER;
   else if (anyMotion) A.kind = anyQuads ? (pluecker ? ACCEL_INSTMB_PLUECKER : ACCEL_INSTMB_MOELLER) : (pluecker ? ACCEL_INSTMB_TRI_PLUECKER : ACCEL_INSTMB_TRI_MOELLER);
   else if (anyQuads) A.kind = pluecker ? ACCEL_INST_PLUECKER : ACCEL_INST_MOELLER;
   else A.kind = pluecker ? ACCEL_INST_TRI_PLUECKER : ACCEL_INST_TRI_MOELLER;
@@ -959,6 +999,13 @@ static void build_instance_accel(Scene* s)
   memcpy(A.blobs.data(), recs.data(), recs.size() * sizeof(InstanceRecord));
   if (!quadRecs.empty()) memcpy(A.blobs.data() + recs.size() * sizeof(InstanceRecord), quadRecs.data(), quadRecs.size() * sizeof(QuadRecord));
   if (!steps.empty()) memcpy(A.blobs.data() + (recs.size() + quadRecs.size()) * sizeof(InstanceRecord), steps.data(), steps.size() * sizeof(InstanceStep));
+  if (anyLinear) { // the node buffer: the QNode8s, zero padding, the QNodeMB8s from the multiple of 144 bytes their references count from
+    if ((A.nodes.size() * sizeof(QNode8) + sizeof(QNodeMB8) - 1) / sizeof(QNodeMB8) != mbNodeBase) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: node counts");
+    A.nodeImage.assign((mbNodeBase + A.nodesMB.size()) * sizeof(QNodeMB8), 0);
+    if (!A.nodes.empty()) memcpy(A.nodeImage.data(), A.nodes.data(), A.nodes.size() * sizeof(QNode8));
+    if (!A.nodesMB.empty()) memcpy(A.nodeImage.data() + mbNodeBase * sizeof(QNodeMB8), A.nodesMB.data(), A.nodesMB.size() * sizeof(QNodeMB8));
+    A.blobOffsets = {(uint32_t)A.nodesMB.size(), (uint32_t)mbNodeBase};
+  }
 }
 
 // Instances of subdivision scenes: the second instance accel of a scene (accel.h InstanceRecord, kinds ACCEL_INSTSUBDIV_*), laid out
@@ -1177,7 +1224,7 @@ void Scene::commit()
   {
     size_t nTriMB = 0, nQuadMB = 0, nQuads = instAccel.blobs.size() / sizeof(InstanceRecord) - instAccel.leafCount; // (kinds ACCEL_INSTMB_*: quads and InstanceSteps)
     // kinds ACCEL_INSTMESHMB_*: `blobs` holds more kinds of records and padding, so the records of the distinct instanced scenes are counted
-    if (instAccel.kind == ACCEL_INSTMESHMB_PLUECKER || instAccel.kind == ACCEL_INSTMESHMB_MOELLER) {
+    if (instAccel.kind == ACCEL_INSTMESHMB_PLUECKER || instAccel.kind == ACCEL_INSTMESHMB_MOELLER || is_inst_linear_kind(instAccel.kind)) {
       std::map<Scene*, int> seen;
       nQuads = 0;
       for (Geometry* geo : geometries)
@@ -1191,6 +1238,9 @@ void Scene::commit()
                     "segment records, %zu instanced motion blur quad segment records, depth %u\n", instAccel.kind,
             instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),
             nQuads, nTriMB, nQuadMB, instAccel.maxDepth);
+    if (is_inst_linear_kind(instAccel.kind))
+      fprintf(stderr, "embree3-amd: instance accel kind %u: %zu time-dependent nodes (%zu B) from node index %u in 144-byte units, node buffer %zu B\n", instAccel.kind,
+              instAccel.nodesMB.size(), instAccel.nodesMB.size() * sizeof(QNodeMB8), instAccel.blobOffsets[1], instAccel.nodeImage.size());
   }
   if (instSubdivAccel.kind != ACCEL_NONE && device->verbose >= 2)
     fprintf(stderr, "embree3-amd: subdivision instance accel kind %u (C %u): %zu nodes (%zu B), %zu instances, %u instanced leaf blobs of %u B from blob index %u, depth %u\n",

@@ -132,6 +132,7 @@ hipError_t launch_trace_cbvh_full(const LaunchParams& p, hipStream_t stream); //
 hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  // trace_instance.hip
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb.hip
 hipError_t launch_trace_instance_subdiv(const LaunchParams& p, hipStream_t stream);  // trace_instance_subdiv.hip
+hipError_t launch_trace_instance_mesh_mb_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb_linear.hip
 // Development builds (-DTRACE_DEV_METRIC_ONLY, tools/README.md): of the subdivision accels only the metric's kind is dispatched (the
 // others fail with hipErrorInvalidValue, so that only trace_cbvh_leaf.hip has to be rebuilt), and launch_service serves no other kind.
 inline hipError_t launch_service(const ServiceParams& s, hipStream_t stream)
@@ -178,6 +179,8 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_INSTMESHMB_MOELLER: return launch_trace_instance_mesh_mb(p, stream);
   case ACCEL_INSTSUBDIV_GRID:
   case ACCEL_INSTSUBDIV_CBVH_LEAF: return launch_trace_instance_subdiv(p, stream);
+  case ACCEL_INSTMESHMB_LINEAR_PLUECKER:
+  case ACCEL_INSTMESHMB_LINEAR_MOELLER: return launch_trace_instance_mesh_mb_linear(p, stream);
   case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
 #ifdef TRACE_DEV_METRIC_ONLY
   case ACCEL_GRIDSOA:

@@ -1,5 +1,5 @@
 // The two-level traversal kernel of trace_instance.hip (where it is described) as a template, shared with
-// trace_instance_mesh_mb.hip, which instantiates its MESHMB form.
+// trace_instance_mesh_mb.hip, which instantiates its MESHMB form, and trace_instance_mesh_mb_linear.hip (the NODEMB form).
 #pragma once
 #include <type_traits>
 #include "trace_leaf.hip.h"
@@ -48,17 +48,20 @@ namespace dev {
 #ifndef TRACE_INST_MESHMB_MIN_WAVES_MOELLER_CLOSEST
 #define TRACE_INST_MESHMB_MIN_WAVES_MOELLER_CLOSEST 3
 #endif
+// NODEMB (trace_instance_mesh_mb_linear.hip): the MESHMB form with time-dependent nodes in the motion-blur trees - twelve more node words
+// and the ray's time across the node step.  Each instantiation is asked for the bound of its MESHMB twin.
 constexpr int inst_min_waves(bool pluecker, bool occluded, bool quads, bool xfmb, bool meshmb = false)
 {
   if (meshmb && !occluded) return pluecker ? TRACE_INST_MESHMB_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_MESHMB_MIN_WAVES_MOELLER_CLOSEST;
   return quads && pluecker && !occluded ? TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_MIN_WAVES;
 }
+constexpr int inst_nodemb_min_waves(bool pluecker, bool occluded) { return inst_min_waves(pluecker, occluded, true, true, true); }
 
 template <bool PLUECKER, bool OCCLUDED, bool VEC, bool QUADS, bool XFMB>
 __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUADS, XFMB)) void trace_instance_kernel(LaunchParams P)
 {
-  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB (it asserts them)
-  constexpr bool MESHMB = false; // the MESHMB form is trace_instance_mesh_mb.hip's kernel
+  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB (it asserts them)
+  constexpr bool MESHMB = false, NODEMB = false; // the MESHMB form is trace_instance_mesh_mb.hip's kernel, the NODEMB form trace_instance_mesh_mb_linear.hip's
 #include "trace_instance_body.hip.h"
 }
 

@@ -1,9 +1,10 @@
-// The body of the two-level traversal kernel (trace_instance.hip, where it is described; trace_instance_mesh_mb.hip), as text: it is
+// The body of the two-level traversal kernel (trace_instance.hip, where it is described; trace_instance_mesh_mb.hip;
+// trace_instance_mesh_mb_linear.hip), as text: it is
 // included inside the braces of a __global__ function that has the launch parameters `P` and the compile-time constants PLUECKER,
-// OCCLUDED, VEC, QUADS, XFMB and MESHMB in scope.  Text and not a function called from the kernels: through a function the compiler
+// OCCLUDED, VEC, QUADS, XFMB, MESHMB and NODEMB in scope.  Text and not a function called from the kernels: through a function the compiler
 // schedules the loads of the launch parameters differently, and the instruction streams of the instantiations of trace_instance.hip
 // are held to what they were (tools/kernel_metadata.py --digest, docs/experiments.md).  No include guard: one inclusion per kernel.
-// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and six `bool`
+// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and seven `bool`
 // constants.  Everything else the text uses comes from the headers trace_instance.hip.h includes and from the TRACE_INST_* macros it
 // defines; the text declares only locals of its own and ends with the traversal loop.
 // trace_instance_subdiv.hip restates the refill, node step, ranking, instance entry and pop of this text for subdivision leaves: a fix to
@@ -11,14 +12,15 @@
   static_assert(std::is_same<decltype(P), LaunchParams>::value, "trace_instance_body.hip.h: `LaunchParams P` must be the kernel's parameter");
 #define TRACE_INSTANCE_BODY_BOOL(x) std::is_same<typename std::remove_const<decltype(x)>::type, bool>::value
   static_assert(TRACE_INSTANCE_BODY_BOOL(PLUECKER) && TRACE_INSTANCE_BODY_BOOL(OCCLUDED) && TRACE_INSTANCE_BODY_BOOL(VEC) && TRACE_INSTANCE_BODY_BOOL(QUADS) &&
-                    TRACE_INSTANCE_BODY_BOOL(XFMB) && TRACE_INSTANCE_BODY_BOOL(MESHMB),
-                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB and MESHMB must be bool constants in scope");
+                    TRACE_INSTANCE_BODY_BOOL(XFMB) && TRACE_INSTANCE_BODY_BOOL(MESHMB) && TRACE_INSTANCE_BODY_BOOL(NODEMB),
+                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB and NODEMB must be bool constants in scope");
 #undef TRACE_INSTANCE_BODY_BOOL
   constexpr uint32_t FETCH = TRACE_INST_FETCH;
   constexpr uint32_t QFETCH = TRACE_INST_QUAD_FETCH;
   constexpr uint32_t TMFETCH = TRACE_INST_TRIMB_FETCH;
   constexpr uint32_t QMFETCH = TRACE_INST_QUADMB_FETCH;
   static_assert(!MESHMB || (QUADS && XFMB), "the MESHMB form carries the general layout: quads and instance steps");
+  static_assert(!NODEMB || MESHMB, "the NODEMB form is the MESHMB form over time-dependent nodes in the motion-blur trees");
   constexpr bool ROBUST = PLUECKER; // Pluecker <-> robust traversal, Moeller <-> fast traversal, on both levels
   __shared__ uint2 ldsStack[TRACE_LDS_STACK + 1][TRACE_BLOCK]; // + one scratch row for the branch-free pushes
   const uint32_t tid = threadIdx.x;
@@ -47,12 +49,16 @@
   RayState r;
   TravRay<ROBUST> tr;
   float travFar = 0.f;
+  float nodeTime = 0.f; // NODEMB: the ray's time, clamped to [0, 1] (a NaN becomes 0), as in trace_loop.hip.h
   uint32_t sp = 0, cur = REF_EMPTY, rayIdx = 0;
   uint32_t curInst = 0xFFFFFFFFu, hitInst = 0xFFFFFFFFu; // geomID of the instance being traversed / of the hit's instance
   // lane state bits (vector register, see RayState::hit): the lane owns a ray, its next event is a pop, it is inside an instance,
   // it is in the instanced scene's quad tree (QUADS only).  MESHMB: two bits, the code of the tree it is in (accel.h INST_TREE_*)
   enum : uint32_t { ST_ACTIVE = 1u, ST_POP = 2u, ST_INSIDE = 4u, ST_QUADS = 8u, ST_TREE_SHIFT = 3u, ST_TREE = 3u << ST_TREE_SHIFT };
   static_assert((INST_TREE_QUAD << ST_TREE_SHIFT) == ST_QUADS, "the quad tree's code is the ST_QUADS bit");
+  // NODEMB: bit 1 of the code says that the tree's nodes are QNodeMB8s; the bits are clear outside an instance
+  enum : uint32_t { ST_TREE_MB = 2u << ST_TREE_SHIFT };
+  static_assert(!(INST_TREE_TRI & 2u) && !(INST_TREE_QUAD & 2u) && (INST_TREE_TRIMB & 2u) && (INST_TREE_QUADMB & 2u), "bit 1 of a tree's code: a motion-blur tree");
   uint32_t st = 0u;
   r.hit = 0u;
 
@@ -106,6 +112,7 @@
           if (ok) {
             tr.init(r);
             travFar = fmaxf(r.tfar, 0.0f); // tray.tfar
+            if (NODEMB) nodeTime = fminf(fmaxf(ray_time(P, rayIdx), 0.0f), 1.0f);
             sp = 0;
             cur = P.accel.root;
             st = ST_ACTIVE;
@@ -121,7 +128,10 @@
 
     // ---- inner node step: the lane-per-ray step of trace_loop.hip.h, on either level ---------------------------------
     if (!(st & ST_POP) && (st & ST_ACTIVE) && !(cur & REF_LEAF)) {
-      const uint4* np = (const uint4*)(nodes + cur);
+      // NODEMB: the lane's tree says which node type `cur` names - a QNodeMB8 of the buffer indexed in 144-byte units while the lane is in
+      // a motion-blur tree of an instanced scene, a QNode8 everywhere else (top level, static trees)
+      const bool mbNode = NODEMB && (st & ST_TREE_MB) != 0u;
+      const uint4* np = mbNode ? (const uint4*)((const QNodeMB8*)nodes + cur) : (const uint4*)(nodes + cur);
       const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3], n4 = np[4], n5 = np[5];
       const float ox = __uint_as_float(n0.x), oy = __uint_as_float(n0.y), oz = __uint_as_float(n0.z);
       const float sx = __uint_as_float((n0.w & 0xffu) << 23);
@@ -139,21 +149,54 @@
 
       uint32_t dist[8];
       uint32_t mask = 0;
+      if (!NODEMB) { // the loop of the other forms as it stands (shared with the NODEMB form through a lambda it left their instruction streams changed)
 #pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const int kk = k & 3;
-        const float npx = madd(q2f(k < 4 ? nx0 : nx1, kk), sx, ox);
-        const float npy = madd(q2f(k < 4 ? ny0 : ny1, kk), sy, oy);
-        const float npz = madd(q2f(k < 4 ? nz0 : nz1, kk), sz, oz);
-        const float fpx = madd(q2f(k < 4 ? fx0 : fx1, kk), sx, ox);
-        const float fpy = madd(q2f(k < 4 ? fy0 : fy1, kk), sy, oy);
-        const float fpz = madd(q2f(k < 4 ? fz0 : fz1, kk), sz, oz);
-        const float tN = fmaxf(tr.nearT(npx, npy, npz), tr.tnear);
-        const float tF = fminf(tr.farT(fpx, fpy, fpz), travFar);
-        const bool h = (tN <= tF) & (cref[k] != REF_EMPTY);
-        // non-hit: distinct sentinels above every distance and below 2^31 (the ranking takes the sign of 32-bit differences)
-        dist[k] = h ? __float_as_uint(tN) : (0x7FFFFFF8u + (uint32_t)k);
-        mask |= h ? (1u << k) : 0u;
+        for (int k = 0; k < 8; k++) {
+          const int kk = k & 3;
+          const float npx = madd(q2f(k < 4 ? nx0 : nx1, kk), sx, ox);
+          const float npy = madd(q2f(k < 4 ? ny0 : ny1, kk), sy, oy);
+          const float npz = madd(q2f(k < 4 ? nz0 : nz1, kk), sz, oz);
+          const float fpx = madd(q2f(k < 4 ? fx0 : fx1, kk), sx, ox);
+          const float fpy = madd(q2f(k < 4 ? fy0 : fy1, kk), sy, oy);
+          const float fpz = madd(q2f(k < 4 ? fz0 : fz1, kk), sz, oz);
+          const float tN = fmaxf(tr.nearT(npx, npy, npz), tr.tnear);
+          const float tF = fminf(tr.farT(fpx, fpy, fpz), travFar);
+          const bool h = (tN <= tF) & (cref[k] != REF_EMPTY);
+          // non-hit: distinct sentinels above every distance and below 2^31 (the ranking takes the sign of 32-bit differences)
+          dist[k] = h ? __float_as_uint(tN) : (0x7FFFFFF8u + (uint32_t)k);
+          mask |= h ? (1u << k) : 0u;
+        }
+      } else {
+        // NODEMB: every plane interpolated between the node's two plane blocks at nodeTime, by the formula of accel.h QNodeMB8 and of
+        // trace_loop.hip.h's plane().  A lane at a QNode8 takes its only block for both: fmaf(t, q - q, q) = q for the finite t, the
+        // planes of the other forms bit for bit, and all lanes of the wave run one instruction stream (a branch around the timed decode
+        // was measured slower and spills at these wave bounds: docs/experiments.md "Linear node bounds below an instance")
+        uint4 n6 = n3, n7 = n4, n8 = n5;
+        if (mbNode) { n6 = np[6]; n7 = np[7]; n8 = np[8]; }
+        const uint32_t rnx0 = ngx ? n6.z : n6.x, rnx1 = ngx ? n6.w : n6.y;
+        const uint32_t rfx0 = ngx ? n6.x : n6.z, rfx1 = ngx ? n6.y : n6.w;
+        const uint32_t rny0 = ngy ? n7.z : n7.x, rny1 = ngy ? n7.w : n7.y;
+        const uint32_t rfy0 = ngy ? n7.x : n7.z, rfy1 = ngy ? n7.y : n7.w;
+        const uint32_t rnz0 = ngz ? n8.z : n8.x, rnz1 = ngz ? n8.w : n8.y;
+        const uint32_t rfz0 = ngz ? n8.x : n8.z, rfz1 = ngz ? n8.y : n8.w;
+        auto plane = [&](uint32_t w0, uint32_t w1, int kk, float s, float o) -> float {
+          return madd(madd(nodeTime, q2f(w1, kk) - q2f(w0, kk), q2f(w0, kk)), s, o);
+        };
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          const int kk = k & 3;
+          const float npx = plane(k < 4 ? nx0 : nx1, k < 4 ? rnx0 : rnx1, kk, sx, ox);
+          const float npy = plane(k < 4 ? ny0 : ny1, k < 4 ? rny0 : rny1, kk, sy, oy);
+          const float npz = plane(k < 4 ? nz0 : nz1, k < 4 ? rnz0 : rnz1, kk, sz, oz);
+          const float fpx = plane(k < 4 ? fx0 : fx1, k < 4 ? rfx0 : rfx1, kk, sx, ox);
+          const float fpy = plane(k < 4 ? fy0 : fy1, k < 4 ? rfy0 : rfy1, kk, sy, oy);
+          const float fpz = plane(k < 4 ? fz0 : fz1, k < 4 ? rfz0 : rfz1, kk, sz, oz);
+          const float tN = fmaxf(tr.nearT(npx, npy, npz), tr.tnear);
+          const float tF = fminf(tr.farT(fpx, fpy, fpz), travFar);
+          const bool h = (tN <= tF) & (cref[k] != REF_EMPTY);
+          dist[k] = h ? __float_as_uint(tN) : (0x7FFFFFF8u + (uint32_t)k); // sentinels as above
+          mask |= h ? (1u << k) : 0u;
+        }
       }
       const int nhit = __popc(mask);
       if (nhit == 0) st |= ST_POP;

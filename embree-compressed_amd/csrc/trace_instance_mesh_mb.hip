@@ -17,7 +17,7 @@
 //       rebased so that `blobs` is indexed as one array of that record type;
 //   4". the exit marker clears the bits.
 // Instance steps (XFMB) and the leaf-batching rule (leafBatch / nodeWork, over all four leaf kinds together) are those of the other forms.
-// Node boxes of the motion-blur trees are the swept boxes of the motion-blur accels.
+// Node boxes of the motion-blur trees are the swept boxes of the motion-blur accels (time-dependent ones: trace_instance_mesh_mb_linear.hip).
 #include "trace_instance.hip.h"
 
 namespace rtamd {
@@ -26,7 +26,7 @@ namespace dev {
 template <bool PLUECKER, bool OCCLUDED, bool VEC>
 __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, true, true, true)) void trace_instance_mesh_mb_kernel(LaunchParams P)
 {
-  constexpr bool QUADS = true, XFMB = true, MESHMB = true; // always the general layout: quads and instance steps allowed
+  constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = false; // always the general layout: quads and instance steps allowed
 #include "trace_instance_body.hip.h"
 }
 

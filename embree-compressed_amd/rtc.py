@@ -49,6 +49,9 @@ ACCEL_TRIMB_LINEAR_PLUECKER = 26
 ACCEL_TRIMB_LINEAR_MOELLER = 27
 ACCEL_QUADMB_LINEAR_PLUECKER = 28
 ACCEL_QUADMB_LINEAR_MOELLER = 29
+# instance accels under inst_mb_bounds=linear whose motion-blur trees keep these time-dependent nodes (two-section node buffer)
+ACCEL_INSTMESHMB_LINEAR_PLUECKER = 30
+ACCEL_INSTMESHMB_LINEAR_MOELLER = 31
 # Scene.accel_data(kind + ACCEL_DATA_INSTSUBDIV): the arrays of that second instance accel, whatever else the scene holds
 ACCEL_DATA_INSTSUBDIV = 16
 RTC_SCENE_FLAG_NONE = 0

@@ -64,7 +64,12 @@ struct RTCAMDSceneStats
                                8 quads (Pluecker), 9 quads (Moeller),
                                10 / 11 motion blur triangles (Pluecker / Moeller), 12 / 13 motion blur quads, 14..25 instance accels,
                                26 / 27 motion blur triangles and 28 / 29 motion blur quads over time-dependent node boxes
-                               (device config mb_bounds=linear; nodeBytes is 144 there) */
+                               (device config mb_bounds=linear; nodeBytes is 144 there),
+                               30 / 31 the instance accels 22 / 23 over such scenes (device config inst_mb_bounds=linear, default swept:
+                               without it a top scene over a scene of the kinds 26..29 is refused at commit); nodeCount / nodeBytes
+                               describe their 96-byte nodes (top-level tree, static trees), the instanced scenes' 144-byte nodes follow
+                               in the same buffer from a multiple of 144 bytes on: rtcamdGetAccelData(scene, 0) returns all of it,
+                               (scene, 3) two words - how many there are and the index of the first one in 144-byte units */
   unsigned int branching;   /* 8 */
   size_t nodeCount;         /* quantized BVH8 nodes */
   size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29) */

@@ -2,13 +2,18 @@
 places them: general transforms - a rotation about y and a uniform scale of 0.8..1.2 per instance - with one step each) of the bomberman triangles with the two time steps of tests/test_gpu_motion_blur.py (`two_steps`: step 1 =
 step 0 rotated by 20 degrees about y and moved by 0.3 x the extent along x), 1 M random rays at random times over the bounds of all
 instances and both steps, device-resident, ONE stream, kernel time by HIP events around every step (the batch is restored from a
-pristine copy before each step, untimed).  Both variants (Pluecker / Moeller).  Three cases:
+pristine copy before each step, untimed).  Both variants (Pluecker / Moeller).  Five cases:
   a  static       the mesh with one time step: the static kinds (14 / 15) - what the library traced before it took moving meshes here;
   b  at-rest      the mesh with two EQUAL steps: kinds 22 / 23, the same boxes and the same hits, through the MESHMB kernel and the
                   96-byte records - b / a is the price of the kernel form and of the interpolation;
-  c  moving       the two steps of `two_steps`: the node boxes are swept over the whole shutter - c / b is the price of the swept boxes.
-The rays are the same in the three cases (bounds of case c), so that a, b and c differ in the scene only.
-usage: instance_mesh_mb_rates.py [steps] [repeats] [cases, e.g. abc]
+  c  moving       the two steps of `two_steps`: the node boxes are swept over the whole shutter - c / b is the price of the swept boxes;
+  d  at-rest      case b on a device with mb_bounds=linear,inst_mb_bounds=linear: kinds 30 / 31, time-dependent nodes (equal plane blocks)
+     linear       below the instances, the NODEMB kernel - d / b is the price of the 144-byte nodes and of the per-lane node step;
+  e  moving       case c on that device - e / c is what the time-dependent boxes save below an instance.
+     linear
+The rays are the same in all cases (bounds of case c), so that the cases differ in the scene and the device config only; all run on
+the same build.
+usage: instance_mesh_mb_rates.py [steps] [repeats] [cases, e.g. abcde]
 (an older build of the library, RTAMD_LIB=..., serves case a only)"""
 import importlib
 import os
@@ -24,7 +29,7 @@ root = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 d = np.load(os.path.join(root, 'assets/bomberman.mesh.npz'))
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-cases = sys.argv[3] if len(sys.argv) > 3 else 'abc'
+cases = sys.argv[3] if len(sys.argv) > 3 else 'abcde'
 n = 1 << 20
 COUNT = 9
 
@@ -59,14 +64,14 @@ def placements(count):
 
 
 def measure(case, variant, xfms, pristine):
-    dev = rtc.Device('gpu=0')
+    dev = rtc.Device('gpu=0,mb_bounds=linear,inst_mb_bounds=linear' if case in 'de' else 'gpu=0')
     flags = rtc.RTC_SCENE_FLAG_ROBUST if variant == 'pluecker' else 0
     sc = rtc.Scene(dev, flags)
     inner = rtc.Scene(dev, flags)
     if case == 'a':
         inner.add_triangles(s0, tris)
     else:
-        inner.add_triangles_mb([s0, s0 if case == 'b' else s1], tris)
+        inner.add_triangles_mb([s0, s0 if case in 'bd' else s1], tris)
     inner.commit()
     for m in xfms:
         sc.add_instance(inner, m)
@@ -93,8 +98,8 @@ def measure(case, variant, xfms, pristine):
         meds.append(float(np.median(ms)))
     stt = sc.stats()
     med = float(np.median(meds))
-    name = {'a': 'static', 'b': 'at-rest', 'c': 'moving'}[case]
-    print(f'{len(xfms):5d} {case} {name:8s} {variant:8s}: accel kind {stt["accelKind"]}, {stt["nodeCount"]} nodes, {stt["totalBytes"]} B, depth {stt["maxDepth"]}, {hits} hits; '
+    name = {'a': 'static', 'b': 'at-rest', 'c': 'moving', 'd': 'at-rest linear', 'e': 'moving linear'}[case]
+    print(f'{len(xfms):5d} {case} {name:14s} {variant:8s}: accel kind {stt["accelKind"]}, {stt["nodeCount"]} nodes, {stt["totalBytes"]} B, depth {stt["maxDepth"]}, {hits} hits; '
           f'kernel {med:.4f} ms per 1 M-ray batch (median of {repeats} repeats of {steps} steps; repeats {min(meds):.4f}..{max(meds):.4f}) = {n / med / 1e3:.0f} Mrays/s', flush=True)
     sc.release()
     inner.release()
@@ -121,3 +126,7 @@ for variant in ('pluecker', 'moeller'):
         print(f'{COUNT:5d} {variant:8s}: at-rest / static = {ms["b"] / ms["a"]:.2f}', flush=True)
     if 'b' in ms and 'c' in ms:
         print(f'{COUNT:5d} {variant:8s}: moving / at-rest = {ms["c"] / ms["b"]:.2f}', flush=True)
+    if 'b' in ms and 'd' in ms:
+        print(f'{COUNT:5d} {variant:8s}: at-rest linear / at-rest = {ms["d"] / ms["b"]:.2f}', flush=True)
+    if 'c' in ms and 'e' in ms:
+        print(f'{COUNT:5d} {variant:8s}: moving linear / moving = {ms["e"] / ms["c"]:.2f}', flush=True)

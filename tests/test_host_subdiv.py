@@ -7,6 +7,7 @@ import pytest
 
 LEAF, EMPTY = 0x80000000, 0xFFFFFFFF
 CELL_DT = np.dtype([("px", "<f4", 9), ("py", "<f4", 9), ("pz", "<f4", 9), ("uv", "<u4", 9), ("geomID", "<u4"), ("primID", "<u4"), ("pad", "<u4", 2)])
+import cbvh_truth_helpers as th  # noqa: E402
 from helpers import CBVH_HDR_DT, CBVH_NODES, CBVH_TAIL_DT, cbvh_header, cbvh_layout  # noqa: E402
 T1 = np.array([0.0, 0.005, 0.01, 0.05, 0.1, 0.2, 0.4, 0.6], np.float32)  # compressed_node.h:31-38
 T2 = np.array([0.0, 0.4, 0.48, 0.49, 0.5, 0.51, 0.52, 0.6], np.float32)  # :22-29
@@ -207,11 +208,23 @@ def test_full_precision_nodes_hold_the_merged_cell_boxes(rtc, bomberman):
         assert H["box"][0] == np.float32(zlo) and H["box"][1] == np.float32(zhi)  # frustum z range = the stored cells' (compressed.h:277-292)
 
 
+WSTICK = {("bvh4.compressed.leaf", 3): 0.0414, ("bvh4.compressed.box", 2): 0.0523, ("bvh4.compressed.grid", 3): 0.0354}
+
+
 @pytest.mark.parametrize("mode,Cl", [("bvh4.compressed.leaf", 3), ("bvh4.compressed.box", 2), ("bvh4.compressed.grid", 3)])
 def test_cbvh_encoder_is_conservative(rtc, bomberman, mode, Cl):
     """Decode every blob with the tables of compressed_node.h: each cell's decoded box (in the blob's projected
-    frame) must contain the four projected grid vertices of that cell up to the quantizer's documented slack, and
-    the header must be self-consistent (iproj = proj^-1, uv window, elems, world bounds contain the vertices)."""
+    frame) must contain the four projected grid vertices of that cell, and the header must be self-consistent
+    (iproj = proj^-1, uv window, elems, world bounds contain the vertices).
+
+    Containment has no relative slack (it was 0.2 of the parent box; tests/test_host_cbvh_encoder_truth.py, rule c, has the
+    derivation): a vertex may leave its cell's box by the blob's own root mismatch - its projected bounds against the
+    traversal root [-1,1]^2 x [box0, box1], per axis - plus the rounding of the encoder's float32 projection
+    (cbvh_truth_helpers.fp32_projection_error), and never by more than the old slack.  `worst`, the largest cut-in beyond that slack over all cells, is asserted
+    <= 0, and the largest cut-in relative to the root box is printed.  The world bounds are NOT conservative (the
+    reference's corner list omits (lx,ly,uz), compressed.h:260-267, copied as is): vertices stick out by up to 0.048 of
+    the blob's largest extent on the 32-face mesh at the form matrix's pairs and by the figures of WSTICK here (measured
+    on these 300 blobs, asserted at 1.5 x, on top of the old bound of 0.25 of every axis' extent)."""
     verts, fs, fi = bomberman
     L = 4
     dev = rtc.Device(f"gpu=none,keep_grids=1,subdiv_accel={mode}")
@@ -227,7 +240,7 @@ def test_cbvh_encoder_is_conservative(rtc, bomberman, mode, Cl):
     assert len(blobs) == 727 * (n // sub) ** 2 == st["primCount"]
     elems = (4 ** Cl - 1) // 3
     rng = np.random.RandomState(0)
-    worst = 0.0
+    worst, rel, wstick = -np.inf, np.zeros(3), 0.0
     for b in blobs[rng.choice(len(blobs), 300, replace=False)]:
         H = cbvh_header(b, Cl, mode.split(".")[-1])
         assert H["elems"] == elems and H["grid_width"] == sub + 1 and H["levels"] == Cl
@@ -239,13 +252,18 @@ def test_cbvh_encoder_is_conservative(rtc, bomberman, mode, Cl):
         # the reference's bounds_o is NOT strictly conservative: its corner list omits (lx,ly,uz) (compressed.h:260-267,
         # copied as is), so vertices may stick out by a fraction of the blob's extent
         wslack = 0.25 * (H["whi"] - H["wlo"]) + 1e-4
-        assert np.all(P >= H["wlo"] - wslack) and np.all(P <= H["whi"] + wslack)
+        assert np.all(P >= H["wlo"] - wslack) and np.all(P <= H["whi"] + wslack)  # per axis, as before; the pinned figure below is the tighter one
+        wstick = max(wstick, float(np.maximum(H["wlo"] - P, P - H["whi"]).max()) / float((H["whi"] - H["wlo"]).max()))
         S = H["space"].reshape(3, 3).astype(np.float64)
         loc = P @ S.T
         M = H["proj"].reshape(3, 3).astype(np.float64)
         hom = np.concatenate([loc[..., :2], np.ones(loc.shape[:2] + (1,))], -1) @ M.T
         pr = np.concatenate([hom[..., :2] / hom[..., 2:3], loc[..., 2:3]], -1)
         assert np.all(np.abs(pr[..., :2]) <= 1.0 + 1e-3)  # rescaled to the projected bounding box
+        flat = pr.reshape(-1, 3)
+        rlo, rhi = np.array([-1.0, -1.0, H["box"][0]]), np.array([1.0, 1.0, H["box"][1]])
+        mismatch = np.maximum(np.abs(flat.min(0) - rlo), np.abs(flat.max(0) - rhi))
+        slack = mismatch + 2.0 * th.fp32_projection_error(P, S, M) + 4 * th.U * np.maximum(np.abs(rlo), np.abs(rhi))
         words = b[CBVH_NODES:CBVH_NODES + 4 * elems].view(np.uint32)
         assert H["rootWord"] == words[0]
         # walk the implicit quadtree; the traversal root box is [-1,1]^2 x [box0,box1] (compressed.h:517-519)
@@ -261,11 +279,18 @@ def test_cbvh_encoder_is_conservative(rtc, bomberman, mode, Cl):
                 else:
                     cx, cy = _morton(child - elems)
                     q = pr[cy:cy + 2, cx:cx + 2].reshape(4, 3)
-                    ext = np.maximum(cb[1] - cb[0], 1e-6)
-                    # table steps are coarse (largest entry <= value): the decoded box may cut in by less than one step
-                    slack = np.array([0.2, 0.2, 0.25]) * np.maximum(box[1] - box[0], 1e-6) + 1e-4
-                    worst = max(worst, float(np.max(np.maximum(cb[0] - q, q - cb[1]) / ext)))
-                    assert np.all(q >= cb[0] - slack) and np.all(q <= cb[1] + slack)
+                    # the encoder stores the largest table entry that does not cut: no slack of a table step
+                    cut = np.maximum(cb[0].astype(np.float64) - q, q - cb[1].astype(np.float64)).max(0)
+                    # never more than the slack this test had, 0.2 / 0.25 of the parent box + 1e-4 (a parent with a tiny z extent)
+                    cell_slack = np.minimum(slack, np.array([0.2, 0.2, 0.25]) * np.maximum(box[1] - box[0], 1e-6) + 1e-4)
+                    worst = max(worst, float((cut - cell_slack).max()))
+                    axes = 3 if rhi[2] - rlo[2] > 100 * slack[2] else 2  # a flat blob, or one whose z range is rounding noise, has no z extent to relate to
+                    rel[:axes] = np.maximum(rel[:axes], (np.maximum(cut, 0.0) / np.maximum(rhi - rlo, 1e-30))[:axes])
+                    assert np.all(q >= cb[0] - cell_slack) and np.all(q <= cb[1] + cell_slack)
+    print(f"[encoder] {mode} C{Cl}: largest cut-in beyond the slack {worst:.2e}; relative to the root box x {rel[0]:.2e} y {rel[1]:.2e} z {rel[2]:.2e}; "
+          f"vertices stick out of the world bounds by {wstick:.3g} of the blob's extent")
+    assert worst <= 0.0
+    assert wstick <= 1.5 * WSTICK[(mode, Cl)]
     sc.release()
     dev.release()
 

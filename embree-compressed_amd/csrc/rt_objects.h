@@ -32,7 +32,7 @@ struct Device : RefCounted
   std::string quad_accel_mb = "default"; // quad meshes with more than one time step
   std::string mb_bounds = "swept"; // node boxes of the motion-blur mesh accels: "swept" (one box over the whole shutter, QNode8) or "linear" (time-dependent, QNodeMB8)
   std::string inst_mb_bounds = "swept"; // node boxes of motion-blur trees below an instance: "swept" (scenes built under mb_bounds=linear are refused below an instance) or "linear" (such scenes keep their QNodeMB8s, kinds ACCEL_INSTMESHMB_LINEAR_*)
-  std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel raises for any other at commit)
+  std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel, rt_instance_build.cpp, raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
   bool triAccelMBNamed = false; // "tri_accel_mb=" given (with inst_accel=: a host-only device takes motion-blur meshes inside an instanced scene, inst_mesh_motion_enabled())
@@ -402,6 +402,10 @@ struct Scene : RefCounted
   enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, INST = 5, INSTSUBDIV = 6, NUM_ACCELS = 7 };
   std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &instAccel, &instSubdivAccel}; }
   bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
+  // records the layout of instAccel placed in `blobs` behind the InstanceRecords, as build_instance_accel counted them (host only: the
+  // verbose line of commit prints them)
+  struct InstanceCounts { size_t quads = 0, steps = 0, triMB = 0, quadMB = 0; };
+  InstanceCounts instCounts;
 
   explicit Scene(Device* d);
   ~Scene() override;
@@ -413,5 +417,14 @@ struct Scene : RefCounted
   void commit();
   bool isRobust() const { return (flags & RTC_SCENE_FLAG_ROBUST) != 0; }
 };
+
+// affine maps as the columns vx, vy, vz, p (rt_scene.cpp): the inverse, false for a singular map; xfmPoint
+bool invert_affine(const float* m, float* out);
+V3 xfm_point(const float* m, V3 q);
+
+// the two instance accels of a scene (rt_instance_build.cpp), in Scene::commit's order: the second relies on the first having refused
+// instances without a committed scene
+void build_instance_accel(Scene* s);
+void build_instance_subdiv_accel(Scene* s);
 
 } // namespace rtamd

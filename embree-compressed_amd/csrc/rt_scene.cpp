@@ -598,7 +598,7 @@ static void build_quadmb_accel(Scene* s)
 // world2local = inverse(local2world), both as the columns vx, vy, vz, p: inverted in double precision and rounded once to fp32
 // (deviation: the reference inverts in fp32 with its rcp, affinespace.h rcp()).  false: singular (or not finite) - the caller stores
 // an all-zero matrix, under which no triangle test passes (the local direction is 0: den == 0 in both tests).
-static bool invert_affine(const float* m, float* out)
+bool invert_affine(const float* m, float* out)
 {
   const double a[3][3] = {{m[0], m[3], m[6]}, {m[1], m[4], m[7]}, {m[2], m[5], m[8]}}; // a[row][col], columns vx vy vz
   const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1], c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2], c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];
@@ -649,526 +649,11 @@ bool Geometry::world2localAt(float time, float* out) const
 }
 
 // xfmPoint (affinespace.h:110): madd(p.x, vx, madd(p.y, vy, madd(p.z, vz, p)))
-static V3 xfm_point(const float* m, V3 q)
+V3 xfm_point(const float* m, V3 q)
 {
   V3 r;
   for (int k = 0; k < 3; k++) r[k] = fmaf(q.x, m[k], fmaf(q.y, m[3 + k], fmaf(q.z, m[6 + k], m[9 + k])));
   return r;
-}
-
-// Instances (RTC_GEOMETRY_TYPE_INSTANCE, one time step, one level): a top-level BVH8 over the instances' world bounds - xfmBounds of
-// the instanced scene's bounds, its eight transformed corners (instance_intersector.cpp:24-39, affinespace.h:114-126) - with ONE
-// instance per leaf, followed in the same arrays by the trees and records of every distinct instanced scene, rebased.  The instanced
-// scenes were committed before; what this commit sees of them is their committed triangle and quad accels (their `bounds` cover both:
-// build_mesh_bvh8 extends them per accel).
-// As long as no instanced scene has a traceable quad accel the result is the triangle-only accel (kinds ACCEL_INST_TRI_*: triangle
-// trees behind the top-level tree, TriRecords, InstanceRecords, `pad` zero); otherwise it is the layout of accel.h InstanceRecord
-// (kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER).  A host-only device takes quads in an instanced scene only when its config names
-// inst_accel= (Device::inst_quads_enabled), as it takes quad meshes at all only with quad_accel=.
-// Instance motion blur: as soon as one enabled instance has more than one time step the kinds are ACCEL_INSTMB_* (chosen otherwise
-// exactly as ACCEL_INST_*) and the steps' local-to-world transforms follow the quad records in `blobs` as InstanceSteps (accel.h).  The
-// world box of a moving instance is the union over its steps of xfmBounds(local2world[i], scene bounds): the instanced scene is static
-// and the lerp of two affine maps sends a point to the lerp of its images, so the union of the steps' boxes holds the object at every
-// time - one box swept over the whole shutter, like the motion-blur mesh accels.  A host-only device takes
-// such instances under the rule of quads (Device::inst_motion_enabled).
-// Motion-blur meshes below an instance: as soon as one instanced scene has a traceable motion-blur accel (triangle or quad meshes with
-// time steps) the kinds are ACCEL_INSTMESHMB_* and the layout is the general one of accel.h InstanceRecord: all four trees of every
-// distinct scene behind the top-level tree, the roots in one InstanceSceneRecord per scene, the TriMBRecords and QuadMBRecords in
-// sections of their own at the end of `blobs`.  The instanced scenes' bounds cover their moving meshes at every time (build_mb_bvh8
-// extends them by the swept boxes).  A host-only device takes such scenes only when its config names inst_accel= and one of
-// tri_accel_mb= / quad_accel_mb= (Device::inst_mesh_motion_enabled); a top scene without a motion-blur accel below it keeps the kinds
-// 14..21 and their arrays.
-// Linear node bounds below an instance (inst_mb_bounds=linear, Device::inst_mb_bounds; on a host-only device only where motion-blur
-// meshes below an instance are taken at all): an instanced scene whose motion-blur accels were built under mb_bounds=linear (kinds
-// 26..29) is then placed with its QNodeMB8s, and as soon as there is one the kinds are ACCEL_INSTMESHMB_LINEAR_*: `prims` and `blobs`
-// as in the kinds ACCEL_INSTMESHMB_*, the node array in two sections (accel.h InstanceRecord) - `A.nodes` with the top-level tree and
-// the static trees, `A.nodesMB` with the motion-blur trees, child indices counted in 144-byte units from the start of the uploaded
-// buffer, and `A.nodeImage` the two with the padding between them.  One device has one mb_bounds and an instance cannot name a scene
-// of another device (Geometry::setInstancedScene), so the motion-blur trees below one top scene are all of one node type.  Without
-// the key such a scene is refused as before; with it and no such scene the accel is what it is without the key.
-// Subdivision scenes below an instance: an instanced scene that enables a subdivision mesh is left to build_instance_subdiv_accel (a
-// second accel of the top scene; this one and its kinds stay what they are) when the device takes such scenes
-// (Device::inst_subdiv_enabled); otherwise it is refused here with the message of the config, as before.
-// maxDepth (launch_on reserves 7 * (maxDepth + 1) + 2 stack entries) =
-//     the top-level depth
-//   + 1 for the exit marker
-//   + the largest number of pending-tree markers any instanced scene can have stacked at once (its tree count - 1, at most 3; in the
-//     kinds 14..21: 1 as soon as any scene has quads)
-//   + the deepest of all instanced trees (the trees of a scene are never stacked together: a marker is popped only when the entries
-//     of the tree before it are gone).
-// First InstanceStep a record may name, in 64-byte units from the start of `blobs`, exclusive: 24 bits beside the segment count.
-static const size_t INSTANCE_FIRST_STEP_LIMIT = (size_t)1 << 24;
-// The class of an instanced scene: a subdivision scene as soon as it enables a subdivision mesh (build_instance_subdiv_accel refuses
-// anything beside it), a mesh scene otherwise.
-static bool is_subdivision_scene(const Scene* o)
-{
-  for (const Geometry* og : o->geometries)
-    if (og && og->enabled && og->type == RTC_GEOMETRY_TYPE_SUBDIVISION) return true;
-  return false;
-}
-static void build_instance_accel(Scene* s)
-{
-  Accel& A = s->instAccel;
-  A.clear();
-  if (s->device->inst_accel != "default") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown instance acceleration structure " + s->device->inst_accel);
-  const bool quadsOk = s->device->inst_quads_enabled();
-  const bool subdivOk = s->device->inst_subdiv_enabled(); // implies quadsOk; scenes of subdivision meshes go to the second instance accel
-  const char* const onlyTris = "an instanced scene may hold static triangle meshes only (no quads, time steps, subdivision meshes or instances)";
-  const char* const onlyStatic = "an instanced scene may hold static triangle and quad meshes only (no time steps, subdivision meshes or instances)";
-  const bool meshMotionOk = s->device->inst_mesh_motion_enabled(); // implies quadsOk
-  const char* const onlyMeshes = "an instanced scene may hold triangle and quad meshes only (no subdivision meshes or instances)";
-  // (the wording is from before subdivision scenes could be instanced and is kept: on a device that takes them, "no subdivision meshes"
-  // reads "not beside meshes in one instanced scene" - a scene of subdivision meshes only never gets here)
-  const char* const only = meshMotionOk ? onlyMeshes : quadsOk ? onlyStatic : onlyTris;
-  struct Src { unsigned geomID; Scene* scene; };
-  std::vector<Src> src;
-  std::vector<BuildPrim> bp;
-  bool haveKind = false, pluecker = false, anyQuads = false, anyMotion = false, anyMeshMotion = false;
-  const bool linearOk = meshMotionOk && s->device->inst_mb_bounds == "linear";
-  bool anyLinear = false, anySwept = false; // traceable motion-blur accels of the kinds 26..29 / 10..13 below this scene
-  uint32_t pendingMax = 0; // most trees of one instanced scene, minus one
-  unsigned kindGeom = 0;   // the instance whose scene fixed the arithmetic, and the accels that scene has: for the refusal below
-  std::string kindNames;
-  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
-    Geometry* g = s->geometries[gid];
-    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_INSTANCE) continue;
-    if (g->timeSteps != 1 && !s->device->inst_motion_enabled()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instances with more than one time step are not supported");
-    Scene* o = g->instScene;
-    if (!o) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance without an instanced scene");
-    if (o->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instanced scene got not committed");
-    if (subdivOk && is_subdivision_scene(o)) continue; // build_instance_subdiv_accel places it
-    // without inst_mb_bounds=linear the instanced scenes' trees are copied behind the top-level tree as QNode8s: time-dependent nodes
-    // have no place there
-    if (!linearOk && (is_mb_linear_kind(o->triMBAccel.kind) || is_mb_linear_kind(o->quadMBAccel.kind)))
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene with a motion blur accel built under mb_bounds=linear is not supported (instance accels hold swept node boxes: use mb_bounds=swept)");
-    for (Geometry* og : o->geometries) {
-      if (!og || !og->enabled) continue;
-      const bool mesh = og->type == RTC_GEOMETRY_TYPE_TRIANGLE || (quadsOk && og->type == RTC_GEOMETRY_TYPE_QUAD);
-      if (!mesh || (og->timeSteps != 1 && !meshMotionOk)) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
-      if (og->intersectFilter || og->occludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
-    }
-    for (const Accel* oa : o->accels())
-      if (oa != &o->triAccel && !(quadsOk && oa == &o->quadAccel) && !(meshMotionOk && (oa == &o->triMBAccel || oa == &o->quadMBAccel)) && oa->kind != ACCEL_NONE)
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
-    if (o->triIntersectFilter || o->triOccludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
-    const bool tris = o->triAccel.traceable(), quads = o->quadAccel.traceable();
-    const bool trisMB = o->triMBAccel.traceable(), quadsMB = o->quadMBAccel.traceable();
-    if (!tris && !quads && !trisMB && !quadsMB) continue; // empty scene: nothing to hit
-    std::string names; // this scene's traceable accels
-    for (const char* nm : {tris ? "triangle" : "", trisMB ? "motion blur triangle" : "", quads ? "quad" : "", quadsMB ? "motion blur quad" : ""})
-      if (*nm) names += std::string(names.empty() ? "" : ", ") + nm;
-    // scenes that disagree while a motion-blur accel is involved: the message names the accels on either side
-    auto disagree = [&](bool thisPl) {
-      const char* const ar[2] = {"Moeller / fast", "Pluecker / robust"};
-      return "the instanced scenes of one scene disagree in accel kind (Pluecker / robust and Moeller / fast): the scene of instance " + std::to_string(gid) + " has " +
-             ar[thisPl] + " accels (" + names + "), the scene of instance " + std::to_string(kindGeom) + " " + ar[!thisPl] + " ones (" + kindNames + "): instances need one arithmetic";
-    };
-    if (trisMB || quadsMB) {
-      // one arithmetic per top scene, over all four trees of every instanced scene
-      struct { bool have, pl; const char* name; } const t[4] = {{tris, o->triAccel.kind == ACCEL_TRI_PLUECKER, "triangle"},
-                                                                {trisMB, is_mb_pluecker_kind(o->triMBAccel.kind), "motion blur triangle"},
-                                                                {quads, o->quadAccel.kind == ACCEL_QUAD_PLUECKER, "quad"},
-                                                                {quadsMB, is_mb_pluecker_kind(o->quadMBAccel.kind), "motion blur quad"}};
-      std::string pl, mo;
-      for (const auto& e : t)
-        if (e.have) (e.pl ? pl : mo) += std::string((e.pl ? pl : mo).empty() ? "" : ", ") + e.name;
-      if (!pl.empty() && !mo.empty())
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "the accels of an instanced scene disagree in kind (Pluecker / robust: " + pl + "; Moeller / fast: " + mo + "): instances need one arithmetic");
-      const bool scenePl = !pl.empty();
-      if (haveKind && scenePl != pluecker) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(scenePl));
-      anyMeshMotion = true;
-      for (const Accel* m : {trisMB ? &o->triMBAccel : nullptr, quadsMB ? &o->quadMBAccel : nullptr})
-        if (m) (is_mb_linear_kind(m->kind) ? anyLinear : anySwept) = true;
-    }
-    pendingMax = std::max(pendingMax, (uint32_t)tris + (uint32_t)trisMB + (uint32_t)quads + (uint32_t)quadsMB - 1u);
-    // the kernel runs ONE arithmetic on both levels and in both leaves: every accel below this scene is Pluecker / robust, or every one
-    // Moeller / fast
-    if (tris && quads && (o->triAccel.kind == ACCEL_TRI_PLUECKER) != (o->quadAccel.kind == ACCEL_QUAD_PLUECKER))
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "the triangle and quad accels of an instanced scene disagree in kind (Pluecker / robust triangles beside Moeller / fast quads, "
-                                            "as a robust scene under quad_accel=bvh8.quad4v builds them): instances need one arithmetic");
-    const bool pl = tris ? o->triAccel.kind == ACCEL_TRI_PLUECKER
-                  : quads ? o->quadAccel.kind == ACCEL_QUAD_PLUECKER
-                  : is_mb_pluecker_kind(trisMB ? o->triMBAccel.kind : o->quadMBAccel.kind);
-    if (haveKind && pl != pluecker) {
-      if (!anyQuads && !quads && !anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
-      if (anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(pl));
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in accel kind (Pluecker / robust and Moeller / fast): instances need one arithmetic");
-    }
-    if (!haveKind) {
-      kindGeom = gid;
-      kindNames = names;
-    }
-    haveKind = true;
-    pluecker = pl;
-    anyQuads |= quads;
-    anyMotion |= g->local2world.size() > 1;
-    BuildPrim p;
-    const V3 c[2] = {o->bounds.lo, o->bounds.hi};
-    for (const Geometry::Xfm& step : g->local2world) // one step: xfmBounds; more: the union over the steps
-      for (int i = 0; i < 8; i++) p.box.extend(xfm_point(step.data(), V3(c[i >> 2].x, c[(i >> 1) & 1].y, c[i & 1].z)));
-    if (!(std::isfinite(p.box.lo.x) && std::isfinite(p.box.lo.y) && std::isfinite(p.box.lo.z) && std::isfinite(p.box.hi.x) && std::isfinite(p.box.hi.y) && std::isfinite(p.box.hi.z)))
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance transform yields bounds that are not finite");
-    p.id = (uint32_t)src.size();
-    src.push_back({gid, o});
-    bp.push_back(p);
-  }
-  if (bp.empty()) return;
-  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances for the 26-bit leaf reference");
-  if (anyLinear && anySwept) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: motion blur accels of both node types below one scene");
-
-  // top-level tree, one instance per leaf: leaf reference = record index, count 1
-  std::vector<InstanceRecord> recs(bp.size());
-  std::vector<uint32_t> order; // record index -> src index, leaf order
-  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
-    if (end - begin != 1) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: a leaf must hold one instance");
-    order.push_back(prims[begin].id);
-    return make_tri_leaf((uint32_t)order.size() - 1u, 1u);
-  };
-  BuildSettings cfg;
-  cfg.blockSize = 1; cfg.minLeaf = 1; cfg.maxLeaf = 1;
-  cfg.threads = 1; // the leaf callback appends in leaf order
-  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
-  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
-  A.nodes = std::move(r.nodes);
-  A.root = r.root;
-  A.leafCount = r.leafCount;
-
-  // the distinct instanced scenes' trees behind it, rebased: the triangle tree, then (anyQuads) the quad tree; with anyMeshMotion all
-  // four trees in Scene::commit's order
-  struct Roots { uint32_t tri, quad; };
-  std::map<Scene*, Roots> rootsOf;
-  std::vector<QuadRecord> quadRecs;
-  uint32_t deepest = 0;
-  // copies the nodes of O behind A.nodes; leaf references move by leafBase, which keeps the first record in bits 0..25 (guarded by the caller)
-  auto append_tree = [&](const Accel& O, size_t leafBase) -> uint32_t {
-    if (!O.traceable()) return REF_EMPTY;
-    const size_t nodeBase = A.nodes.size();
-    if (nodeBase + O.nodes.size() >= (size_t)REF_LEAF) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced nodes for the 31-bit node reference");
-    auto rebase = [&](uint32_t ref) -> uint32_t {
-      if (ref == REF_EMPTY) return ref;
-      if (ref & REF_LEAF) return ref + (uint32_t)leafBase;
-      return ref + (uint32_t)nodeBase;
-    };
-    for (QNode8 n : O.nodes) {
-      for (uint32_t& c : n.child) c = rebase(c);
-      A.nodes.push_back(n);
-    }
-    deepest = std::max(deepest, O.maxDepth);
-    return rebase(O.root);
-  };
-  // ACCEL_INSTMESHMB_LINEAR_*: the same for a tree of QNodeMB8s, into the second section of the node array, which starts mbNodeBase
-  // 144-byte units into the buffer (computed below, from the number of QNode8s in front)
-  size_t mbNodeBase = 0;
-  auto append_tree_mb = [&](const Accel& O, size_t leafBase) -> uint32_t {
-    if (!O.traceable()) return REF_EMPTY;
-    const size_t nodeBase = mbNodeBase + A.nodesMB.size();
-    if (nodeBase + O.nodesMB.size() >= (size_t)REF_LEAF)
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced motion blur nodes for the 31-bit node reference (they follow all other nodes in one buffer, counted in 144-byte units)");
-    auto rebase = [&](uint32_t ref) -> uint32_t {
-      if (ref == REF_EMPTY) return ref;
-      if (ref & REF_LEAF) return ref + (uint32_t)leafBase;
-      return ref + (uint32_t)nodeBase;
-    };
-    for (QNodeMB8 n : O.nodesMB) {
-      for (uint32_t& c : n.child) c = rebase(c);
-      A.nodesMB.push_back(n);
-    }
-    deepest = std::max(deepest, O.maxDepth);
-    return rebase(O.root);
-  };
-  auto append_mb = [&](const Accel& O, size_t leafBase) -> uint32_t { return anyLinear ? append_tree_mb(O, leafBase) : append_tree(O, leafBase); };
-  // ACCEL_INSTMESHMB_*: where the sections of `blobs` start follows from the counts of everything in front of them
-  std::vector<InstanceSceneRecord> sceneRecs;
-  std::map<Scene*, uint32_t> sceneRecOf; // -> index into sceneRecs
-  std::vector<TriMBRecord> triMBRecs;
-  std::vector<QuadMBRecord> quadMBRecs;
-  size_t numSteps = 0, sceneRecBase = 0, triMBOffset = 0, quadMBOffset = 0; // sceneRecBase in 64-byte units, the offsets in bytes
-  if (anyMeshMotion) {
-    size_t nQuads = 0, nTriMB = 0, nScenes = 0, nQNodes = A.nodes.size();
-    std::map<Scene*, int> seen;
-    for (const Src& sr : src) {
-      const size_t n = s->geometries[sr.geomID]->local2world.size();
-      if (n > 1) numSteps += n;
-      if (seen[sr.scene]++) continue;
-      nScenes++;
-      if (sr.scene->quadAccel.traceable()) nQuads += sr.scene->quadAccel.blobs.size() / sizeof(QuadRecord);
-      if (sr.scene->triMBAccel.traceable()) nTriMB += sr.scene->triMBAccel.blobs.size() / sizeof(TriMBRecord);
-      for (const Accel* st : {&sr.scene->triAccel, &sr.scene->quadAccel})
-        if (st->traceable()) nQNodes += st->nodes.size();
-    }
-    mbNodeBase = (nQNodes * sizeof(QNode8) + sizeof(QNodeMB8) - 1) / sizeof(QNodeMB8);
-    sceneRecBase = recs.size() + nQuads + numSteps;
-    triMBOffset = ((sceneRecBase + nScenes) * sizeof(InstanceRecord) + sizeof(TriMBRecord) - 1) / sizeof(TriMBRecord) * sizeof(TriMBRecord);
-    quadMBOffset = (triMBOffset + nTriMB * sizeof(TriMBRecord) + sizeof(QuadMBRecord) - 1) / sizeof(QuadMBRecord) * sizeof(QuadMBRecord);
-  }
-  for (const Src& sr : src) {
-    if (rootsOf.count(sr.scene)) continue;
-    Roots roots;
-    InstanceSceneRecord sc;
-    memset(&sc, 0, sizeof(sc));
-    const Accel& O = sr.scene->triAccel;
-    const size_t primBase = A.prims.size();
-    if (primBase + O.prims.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced triangles for the 26-bit leaf reference");
-    roots.tri = append_tree(O, primBase);
-    if (O.traceable()) A.prims.insert(A.prims.end(), O.prims.begin(), O.prims.end());
-    sc.triMBRoot = REF_EMPTY;
-    const Accel& TM = sr.scene->triMBAccel;
-    if (anyMeshMotion && TM.traceable()) {
-      // motion-blur triangle leaves index `blobs` as one array of 96-byte records
-      const size_t n = TM.blobs.size() / sizeof(TriMBRecord), base = triMBOffset / sizeof(TriMBRecord) + triMBRecs.size();
-      if (base + n >= ((size_t)1 << TRI_START_BITS))
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced motion blur triangle segments for the 26-bit leaf reference (their records follow the instance, quad, step and "
-                                              "scene records in one array)");
-      sc.triMBRoot = append_mb(TM, base);
-      const TriMBRecord* t = (const TriMBRecord*)TM.blobs.data();
-      triMBRecs.insert(triMBRecs.end(), t, t + n);
-    }
-    roots.quad = REF_EMPTY;
-    const Accel& Q = sr.scene->quadAccel;
-    if ((anyQuads || anyMeshMotion) && Q.traceable()) {
-      // quad leaves index `blobs` as one array of 64-byte records: the instance records, then every scene's quads
-      const size_t nq = Q.blobs.size() / sizeof(QuadRecord), quadBase = recs.size() + quadRecs.size();
-      if (quadBase + nq >= ((size_t)1 << TRI_START_BITS))
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances and instanced quads for the 26-bit leaf reference (quad records follow the instance records in one array)");
-      roots.quad = append_tree(Q, quadBase);
-      const QuadRecord* q = (const QuadRecord*)Q.blobs.data();
-      quadRecs.insert(quadRecs.end(), q, q + nq);
-    }
-    sc.quadMBRoot = REF_EMPTY;
-    const Accel& QM = sr.scene->quadMBAccel;
-    if (anyMeshMotion && QM.traceable()) {
-      // motion-blur quad leaves index `blobs` as one array of 128-byte records
-      const size_t n = QM.blobs.size() / sizeof(QuadMBRecord), base = quadMBOffset / sizeof(QuadMBRecord) + quadMBRecs.size();
-      if (base + n >= ((size_t)1 << TRI_START_BITS))
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced motion blur quad segments for the 26-bit leaf reference (their records follow all other records in one array)");
-      sc.quadMBRoot = append_mb(QM, base);
-      const QuadMBRecord* q = (const QuadMBRecord*)QM.blobs.data();
-      quadMBRecs.insert(quadMBRecs.end(), q, q + n);
-    }
-    rootsOf[sr.scene] = roots;
-    if (anyMeshMotion) {
-      sc.triRoot = roots.tri;
-      sc.quadRoot = roots.quad;
-      sceneRecOf[sr.scene] = (uint32_t)sceneRecs.size();
-      sceneRecs.push_back(sc);
-    }
-  }
-  std::vector<InstanceStep> steps; // of the moving instances, in record order, behind the quad records
-  for (size_t i = 0; i < order.size(); i++) {
-    const Src& sr = src[order[i]];
-    const Geometry* g = s->geometries[sr.geomID];
-    InstanceRecord& rec = recs[i];
-    memset(&rec, 0, sizeof(rec));
-    if (!invert_affine(g->local2world[0].data(), rec.world2local)) memset(rec.world2local, 0, sizeof(rec.world2local)); // singular: never hit
-    rec.geomID = sr.geomID;
-    rec.root = rootsOf[sr.scene].tri;
-    if (anyMeshMotion) rec.root = (uint32_t)sceneRecBase + sceneRecOf[sr.scene]; // its InstanceSceneRecord, in 64-byte units from the start of `blobs`
-    else if (anyQuads) rec.pad[0] = rootsOf[sr.scene].quad;
-    if (g->local2world.size() > 1) {
-      const size_t firstStep = recs.size() + quadRecs.size() + steps.size();
-      if (firstStep >= INSTANCE_FIRST_STEP_LIMIT)
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances, instanced quads and instance time steps for the 24-bit step offset of an instance record");
-      rec.pad[1] = ((uint32_t)(g->local2world.size() - 1) << 24) | (uint32_t)firstStep;
-      for (const Geometry::Xfm& x : g->local2world) {
-        InstanceStep st;
-        memset(&st, 0, sizeof(st));
-        memcpy(st.local2world, x.data(), sizeof(st.local2world));
-        steps.push_back(st);
-      }
-    }
-  }
-  if (anyLinear) A.kind = pluecker ? ACCEL_INSTMESHMB_LINEAR_PLUECKER : ACCEL_INSTMESHMB_LINEAR_MOELLER;
-  else if (anyMeshMotion) A.kind = pluecker ? ACCEL_INSTMESHMB_PLUECKER : ACCEL_INSTMESHMB_MOELLER;
-  else if (anyMotion) A.kind = anyQuads ? (pluecker ? ACCEL_INSTMB_PLUECKER : ACCEL_INSTMB_MOELLER) : (pluecker ? ACCEL_INSTMB_TRI_PLUECKER : ACCEL_INSTMB_TRI_MOELLER);
-  else if (anyQuads) A.kind = pluecker ? ACCEL_INST_PLUECKER : ACCEL_INST_MOELLER;
-  else A.kind = pluecker ? ACCEL_INST_TRI_PLUECKER : ACCEL_INST_TRI_MOELLER;
-  A.robust = pluecker ? 1 : 0;
-  // launch_on's stack bound counts 7 entries per level.  Triangle-only: the top-level levels, the exit marker, the deepest instanced
-  // tree.  With quads a ray in a triangle tree has the marker of the pending quad tree stacked as well - one more entry, counted as a
-  // level - and the deepest tree is the deeper of all triangle and quad trees (the two trees of a scene are never stacked together:
-  // the quad marker is popped only when the triangle tree's entries are gone).
-  A.maxDepth = r.maxDepth + 1u + (anyMeshMotion ? pendingMax : anyQuads ? 1u : 0u) + deepest;
-  A.blobStride = sizeof(InstanceRecord);
-  A.blobs.assign(anyMeshMotion ? quadMBOffset + quadMBRecs.size() * sizeof(QuadMBRecord) : (recs.size() + quadRecs.size() + steps.size()) * sizeof(InstanceRecord), 0);
-  if (anyMeshMotion) {
-    if (recs.size() + quadRecs.size() + steps.size() != sceneRecBase) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: record counts");
-    memcpy(A.blobs.data() + sceneRecBase * sizeof(InstanceRecord), sceneRecs.data(), sceneRecs.size() * sizeof(InstanceSceneRecord));
-    if (!triMBRecs.empty()) memcpy(A.blobs.data() + triMBOffset, triMBRecs.data(), triMBRecs.size() * sizeof(TriMBRecord));
-    if (!quadMBRecs.empty()) memcpy(A.blobs.data() + quadMBOffset, quadMBRecs.data(), quadMBRecs.size() * sizeof(QuadMBRecord));
-  }
-  memcpy(A.blobs.data(), recs.data(), recs.size() * sizeof(InstanceRecord));
-  if (!quadRecs.empty()) memcpy(A.blobs.data() + recs.size() * sizeof(InstanceRecord), quadRecs.data(), quadRecs.size() * sizeof(QuadRecord));
-  if (!steps.empty()) memcpy(A.blobs.data() + (recs.size() + quadRecs.size()) * sizeof(InstanceRecord), steps.data(), steps.size() * sizeof(InstanceStep));
-  if (anyLinear) { // the node buffer: the QNode8s, zero padding, the QNodeMB8s from the multiple of 144 bytes their references count from
-    if ((A.nodes.size() * sizeof(QNode8) + sizeof(QNodeMB8) - 1) / sizeof(QNodeMB8) != mbNodeBase) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: node counts");
-    A.nodeImage.assign((mbNodeBase + A.nodesMB.size()) * sizeof(QNodeMB8), 0);
-    if (!A.nodes.empty()) memcpy(A.nodeImage.data(), A.nodes.data(), A.nodes.size() * sizeof(QNode8));
-    if (!A.nodesMB.empty()) memcpy(A.nodeImage.data() + mbNodeBase * sizeof(QNodeMB8), A.nodesMB.data(), A.nodesMB.size() * sizeof(QNodeMB8));
-    A.blobOffsets = {(uint32_t)A.nodesMB.size(), (uint32_t)mbNodeBase};
-  }
-}
-
-// Instances of subdivision scenes: the second instance accel of a scene (accel.h InstanceRecord, kinds ACCEL_INSTSUBDIV_*), laid out
-// like the first.  One node array holds the top-level BVH8 over the instances' world boxes (one instance per leaf; the box is the union
-// over the transform's time steps of xfmBounds(local2world, scene bounds), as above) and behind it the rebased subdivision BVH8 of every
-// distinct instanced scene; `blobs` holds the InstanceRecords, the InstanceSteps of moving instances, and - from a multiple of the blob
-// stride on - the leaf blobs of all instanced scenes, so that a rebased leaf reference indexes `blobs` the way the leaf functions of
-// the subdivision kernels do (GridCellLeaf::intersect, CbvhLeaf::intersect).  Two subdivision accels are placed: the eager default
-// (ACCEL_GRIDSOA) and bvh4.compressed.leaf at every compression level; the kernel is instantiated per leaf family and level, so all
-// instanced subdivision scenes of one top scene must agree in both (their tessellation levels may differ).  A host-only device takes
-// such instances only when its config names inst_accel= and subdiv_accel= (Device::inst_subdiv_enabled); otherwise
-// build_instance_accel refuses them as it always did.
-// maxDepth = the top-level depth + 1 for the exit marker + the deepest instanced tree.
-static void build_instance_subdiv_accel(Scene* s)
-{
-  Accel& A = s->instSubdivAccel;
-  A.clear();
-  A.robust = 1; // the subdivision accels traverse robustly, on both levels here
-  if (!s->device->inst_subdiv_enabled()) return;
-  struct Src { unsigned geomID; Scene* scene; };
-  std::vector<Src> src;
-  std::vector<BuildPrim> bp;
-  bool haveKind = false;
-  uint32_t leafKind = ACCEL_NONE, levels = 0;
-  unsigned kindGeom = 0;
-  auto type_name = [](RTCGeometryType t) -> const char* {
-    return t == RTC_GEOMETRY_TYPE_TRIANGLE ? "triangle mesh" : t == RTC_GEOMETRY_TYPE_QUAD ? "quad mesh" : t == RTC_GEOMETRY_TYPE_INSTANCE ? "instance" : "geometry of another type";
-  };
-  auto accel_name = [](uint32_t kind, uint32_t C) -> std::string {
-    return kind == ACCEL_GRIDSOA ? std::string("the eager accel") : "bvh4.compressed.leaf at compression level " + std::to_string(C);
-  };
-  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
-    Geometry* g = s->geometries[gid];
-    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_INSTANCE) continue;
-    Scene* o = g->instScene; // present and committed: build_instance_accel has looked at every instance
-    if (!o || !is_subdivision_scene(o)) continue;
-    for (const Geometry* og : o->geometries) {
-      if (!og || !og->enabled) continue;
-      if (og->type == RTC_GEOMETRY_TYPE_INSTANCE)
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene that enables subdivision meshes may hold nothing else: the scene of instance " + std::to_string(gid) +
-                                              " also enables an instance (instances below instances are not supported)");
-      if (og->type != RTC_GEOMETRY_TYPE_SUBDIVISION)
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene that enables subdivision meshes may hold nothing else: the scene of instance " + std::to_string(gid) +
-                                              " also enables a " + type_name(og->type));
-      if (og->intersectFilter || og->occludedFilter)
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "subdivision geometry with a filter function inside an instanced scene is not supported (instance " + std::to_string(gid) + ")");
-    }
-    const Accel& O = o->subdivAccel;
-    if (O.kind == ACCEL_CBVH_BOX || O.kind == ACCEL_CBVH_GRID || O.kind == ACCEL_CBVH_FULL)
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, std::string("subdiv_accel=bvh4.compressed.") + (O.kind == ACCEL_CBVH_BOX ? "box" : O.kind == ACCEL_CBVH_GRID ? "grid" : "full") +
-                                            " below an instance is not supported (the eager accel and bvh4.compressed.leaf are)");
-    if (!O.traceable()) continue; // nothing to hit
-    if (O.kind != ACCEL_GRIDSOA && O.kind != ACCEL_CBVH_LEAF) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: unknown subdivision accel kind");
-    const uint32_t C = O.kind == ACCEL_CBVH_LEAF ? o->compressionLevel : 0u;
-    if (haveKind && (O.kind != leafKind || C != levels))
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced subdivision scenes of one scene disagree in accel kind or compression level: the scene of instance " + std::to_string(gid) + " has " +
-                                            accel_name(O.kind, C) + ", the scene of instance " + std::to_string(kindGeom) + " " + accel_name(leafKind, levels) +
-                                            ": the instance kernel is instantiated per leaf kind and level");
-    if (!haveKind) kindGeom = gid;
-    haveKind = true;
-    leafKind = O.kind;
-    levels = C;
-    BuildPrim p;
-    const V3 c[2] = {o->bounds.lo, o->bounds.hi};
-    for (const Geometry::Xfm& step : g->local2world) // one step: xfmBounds; more: the union over the steps
-      for (int i = 0; i < 8; i++) p.box.extend(xfm_point(step.data(), V3(c[i >> 2].x, c[(i >> 1) & 1].y, c[i & 1].z)));
-    if (!(std::isfinite(p.box.lo.x) && std::isfinite(p.box.lo.y) && std::isfinite(p.box.lo.z) && std::isfinite(p.box.hi.x) && std::isfinite(p.box.hi.y) && std::isfinite(p.box.hi.z)))
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance transform yields bounds that are not finite");
-    p.id = (uint32_t)src.size();
-    src.push_back({gid, o});
-    bp.push_back(p);
-  }
-  if (bp.empty()) return;
-  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances for the 26-bit leaf reference");
-
-  // top-level tree, one instance per leaf: leaf reference = record index, count 1
-  std::vector<InstanceRecord> recs(bp.size());
-  std::vector<uint32_t> order; // record index -> src index, leaf order
-  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
-    if (end - begin != 1) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: a leaf must hold one instance");
-    order.push_back(prims[begin].id);
-    return make_tri_leaf((uint32_t)order.size() - 1u, 1u);
-  };
-  BuildSettings cfg;
-  cfg.blockSize = 1; cfg.minLeaf = 1; cfg.maxLeaf = 1;
-  cfg.threads = 1; // the leaf callback appends in leaf order
-  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
-  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
-  A.nodes = std::move(r.nodes);
-  A.root = r.root;
-  A.leafCount = r.leafCount;
-
-  // where the blob section starts follows from the counts in front of it
-  const size_t stride = src[0].scene->subdivAccel.blobStride;
-  size_t numSteps = 0;
-  for (const Src& sr : src) {
-    const size_t n = s->geometries[sr.geomID]->local2world.size();
-    if (n > 1) numSteps += n;
-  }
-  const size_t blobBase = ((recs.size() + numSteps) * sizeof(InstanceRecord) + stride - 1) / stride; // index of the first leaf blob
-  std::map<Scene*, uint32_t> rootOf;
-  std::vector<const Accel*> placed; // the distinct scenes' accels, in the order of their blobs
-  size_t numBlobs = 0;
-  uint32_t deepest = 0;
-  for (const Src& sr : src) {
-    if (rootOf.count(sr.scene)) continue;
-    const Accel& O = sr.scene->subdivAccel;
-    if (O.blobStride != stride || O.blobs.size() % stride != 0) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: blob strides");
-    const size_t n = O.blobs.size() / stride, leafBase = blobBase + numBlobs;
-    if (leafBase + n >= ((size_t)1 << TRI_START_BITS))
-      RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced subdivision leaf blobs for the 26-bit leaf reference (the blobs follow the instance and step records in one array)");
-    const size_t nodeBase = A.nodes.size();
-    if (nodeBase + O.nodes.size() >= (size_t)REF_LEAF) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced nodes for the 31-bit node reference");
-    auto rebase = [&](uint32_t ref) -> uint32_t {
-      if (ref == REF_EMPTY) return ref;
-      if (ref & REF_LEAF) return ref + (uint32_t)leafBase;
-      return ref + (uint32_t)nodeBase;
-    };
-    for (QNode8 n8 : O.nodes) {
-      for (uint32_t& c : n8.child) c = rebase(c);
-      A.nodes.push_back(n8);
-    }
-    deepest = std::max(deepest, O.maxDepth);
-    rootOf[sr.scene] = rebase(O.root);
-    placed.push_back(&O);
-    numBlobs += n;
-  }
-  std::vector<InstanceStep> steps; // of the moving instances, in record order, behind the instance records
-  for (size_t i = 0; i < order.size(); i++) {
-    const Src& sr = src[order[i]];
-    const Geometry* g = s->geometries[sr.geomID];
-    InstanceRecord& rec = recs[i];
-    memset(&rec, 0, sizeof(rec));
-    if (!invert_affine(g->local2world[0].data(), rec.world2local)) memset(rec.world2local, 0, sizeof(rec.world2local)); // singular: never hit
-    rec.geomID = sr.geomID;
-    rec.root = rootOf[sr.scene];
-    if (g->local2world.size() > 1) {
-      const size_t firstStep = recs.size() + steps.size();
-      if (firstStep >= INSTANCE_FIRST_STEP_LIMIT)
-        RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances and instance time steps for the 24-bit step offset of an instance record");
-      rec.pad[1] = ((uint32_t)(g->local2world.size() - 1) << 24) | (uint32_t)firstStep;
-      for (const Geometry::Xfm& x : g->local2world) {
-        InstanceStep st;
-        memset(&st, 0, sizeof(st));
-        memcpy(st.local2world, x.data(), sizeof(st.local2world));
-        steps.push_back(st);
-      }
-    }
-  }
-  if (steps.size() != numSteps) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: record counts");
-  A.kind = leafKind == ACCEL_GRIDSOA ? ACCEL_INSTSUBDIV_GRID : ACCEL_INSTSUBDIV_CBVH_LEAF;
-  A.cbvhLevels = levels;
-  A.maxDepth = r.maxDepth + 1u + deepest;
-  A.blobStride = (uint32_t)stride;
-  A.blobs.assign((blobBase + numBlobs) * stride, 0);
-  memcpy(A.blobs.data(), recs.data(), recs.size() * sizeof(InstanceRecord));
-  if (!steps.empty()) memcpy(A.blobs.data() + recs.size() * sizeof(InstanceRecord), steps.data(), steps.size() * sizeof(InstanceStep));
-  size_t at = blobBase * stride;
-  for (const Accel* O : placed) {
-    memcpy(A.blobs.data() + at, O->blobs.data(), O->blobs.size());
-    at += O->blobs.size();
-  }
-  A.blobOffsets = {(uint32_t)numBlobs, (uint32_t)blobBase};
 }
 
 void Scene::commit()
@@ -1222,18 +707,10 @@ void Scene::commit()
   }
   if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
   {
-    size_t nTriMB = 0, nQuadMB = 0, nQuads = instAccel.blobs.size() / sizeof(InstanceRecord) - instAccel.leafCount; // (kinds ACCEL_INSTMB_*: quads and InstanceSteps)
-    // kinds ACCEL_INSTMESHMB_*: `blobs` holds more kinds of records and padding, so the records of the distinct instanced scenes are counted
-    if (instAccel.kind == ACCEL_INSTMESHMB_PLUECKER || instAccel.kind == ACCEL_INSTMESHMB_MOELLER || is_inst_linear_kind(instAccel.kind)) {
-      std::map<Scene*, int> seen;
-      nQuads = 0;
-      for (Geometry* geo : geometries)
-        if (geo && geo->enabled && geo->type == RTC_GEOMETRY_TYPE_INSTANCE && geo->instScene && !seen[geo->instScene]++) {
-          if (geo->instScene->quadAccel.traceable()) nQuads += geo->instScene->quadAccel.blobs.size() / sizeof(QuadRecord);
-          if (geo->instScene->triMBAccel.traceable()) nTriMB += geo->instScene->triMBAccel.blobs.size() / sizeof(TriMBRecord);
-          if (geo->instScene->quadMBAccel.traceable()) nQuadMB += geo->instScene->quadMBAccel.blobs.size() / sizeof(QuadMBRecord);
-        }
-    }
+    // the record counts of the layout (build_instance_accel).  Below the kinds ACCEL_INSTMESHMB_* "instanced quads" has always counted
+    // every 64-byte record behind the instance records: quads and InstanceSteps
+    const bool general = instAccel.kind == ACCEL_INSTMESHMB_PLUECKER || instAccel.kind == ACCEL_INSTMESHMB_MOELLER || is_inst_linear_kind(instAccel.kind);
+    const size_t nQuads = instCounts.quads + (general ? 0 : instCounts.steps), nTriMB = instCounts.triMB, nQuadMB = instCounts.quadMB;
     fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, %zu instanced quads, %zu instanced motion blur triangle "
                     "segment records, %zu instanced motion blur quad segment records, depth %u\n", instAccel.kind,
             instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),

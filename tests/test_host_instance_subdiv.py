@@ -1,5 +1,5 @@
 """Instances of scenes that hold subdivision meshes, on the CPU: what rtcCommitScene builds on a host-only device whose config names
-inst_accel= and subdiv_accel= (csrc/rt_scene.cpp build_instance_subdiv_accel; the layout is described at csrc/accel.h InstanceRecord),
+inst_accel= and subdiv_accel= (csrc/rt_instance_build.cpp build_instance_subdiv_accel; the layout is described at csrc/accel.h InstanceRecord),
 what it refuses, and that every other host-only config keeps the messages it always raised."""
 import ctypes as C
 

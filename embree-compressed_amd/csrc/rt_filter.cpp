@@ -1,5 +1,6 @@
 // Batches with filter callbacks: the host filter loop over exclusion-list re-traces.
 #include "rt_trace.h"
+#include "rt_excl_list.h"
 
 namespace rtamd {
 
@@ -24,54 +25,50 @@ namespace rtamd {
 //  * the fork's compressed modes never call a filter: CompressedBVHIntersector1::intersect writes the hit itself and occluded()
 //    is a stub (compressed.h:454-756, no runIntersectionFilter1 anywhere in compressed*.h).  Hits on such an accel are accepted
 //    without a callback, geometry and context filter alike; for any-hit queries the stub pass runs first, unfiltered.
+// Meshes below an instance (device config inst_filters=1; without it such filters are refused at commit / at the call and a hit on an
+// instance is accepted as it is):
+//  * a hit with hit.instID[0] != the context's value lies below the instance s->geometries[hit.instID[0]]; its geometry is
+//    instScene->geometries[hit.geomID].  The callbacks run in the reference's order (instance_intersector.cpp:51-62 traces the instanced
+//    scene with context->instID[0] = the instance, so the geometry's filter and then the context filter run down there): the instanced
+//    geometry's intersect / occluded filter with THAT geometry's user pointer, then the context filter if the lane is still valid.  Both
+//    get the caller's own context object (applications derive from RTCIntersectContext) with instID[0] = the instance's geomID for the
+//    duration of the callbacks.
+//  * a candidate is (instance geomID, geomID, primID, bits of t) for every leaf type - a list of its own (Scene::INST) whose flattened
+//    entries carry two words, t and the instance (trace.h); the re-trace of the instance accel runs the EXCL form of the two-level
+//    kernel (trace_instance_filter.hip).  t tells a quad's two triangles apart (the diagonal: as above) and a motion-blur record from
+//    its sibling; the instance tells two instances of one scene under one transform apart.
+//  * instances of subdivision scenes (Scene::instSubdivAccel): no filter can be set below them and a context filter is refused on such a
+//    top scene, so their hits stay accepted without a callback.
 static const unsigned FILTER_MAX_ROUNDS = 256;
 
-// The candidates the callbacks rejected on one accel, and their flattened form for the active rays of a round.
-struct ExclList
+// The candidates the callbacks rejected on one accel, and their flattened form for the active rays of a round (rt_excl_list.h), with the upload.
+struct ExclList : ExclListHost
 {
-  struct Rejected { uint32_t geomID, primID, tbits; };
-  bool keyedByT = false; // grid cells and quads: a candidate is (geomID, primID, bits of t); triangles: (geomID, primID)
-  std::vector<std::vector<Rejected>> perRay; // by ray of the batch
-  std::vector<uint32_t> off, tbits;
-  std::vector<uint2> pairs;
-  static size_t a16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-  void flatten(const std::vector<uint32_t>& act)
-  {
-    off.assign(act.size() + 1, 0);
-    pairs.clear();
-    tbits.clear();
-    for (size_t k = 0; k < act.size(); k++) {
-      off[k] = (uint32_t)pairs.size();
-      for (const Rejected& e : perRay[act[k]]) {
-        pairs.push_back(make_uint2(e.geomID, e.primID));
-        if (keyedByT) tbits.push_back(e.tbits);
-      }
-    }
-    off[act.size()] = (uint32_t)pairs.size();
-  }
-  size_t deviceBytes() const { return a16(off.size() * 4) + a16(pairs.size() * sizeof(uint2)) + a16(tbits.size() * 4); }
+  static_assert(sizeof(Pair) == sizeof(uint2), "ExclListHost::Pair is a device uint2");
   // into deviceBytes() bytes at D; an empty list is not uploaded and its launch gets no exclusion pointers
   LaunchExtras upload(char* D, hipStream_t stream) const
   {
     LaunchExtras x;
     if (pairs.empty()) return x;
-    char* dPairs = D + a16(off.size() * 4);
-    char* dT = dPairs + a16(pairs.size() * sizeof(uint2));
-    HIP_CHECK(hipMemcpyAsync(D, off.data(), off.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(dPairs, pairs.data(), pairs.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
-    if (keyedByT) HIP_CHECK(hipMemcpyAsync(dT, tbits.data(), tbits.size() * 4, hipMemcpyHostToDevice, stream));
+    char* dPairs = D + a16(offBytes());
+    char* dT = dPairs + a16(pairBytes());
+    HIP_CHECK(hipMemcpyAsync(D, off.data(), offBytes(), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(dPairs, pairs.data(), pairBytes(), hipMemcpyHostToDevice, stream));
+    if (!tbits.empty()) HIP_CHECK(hipMemcpyAsync(dT, tbits.data(), tBytes(), hipMemcpyHostToDevice, stream));
     x.exclOffsets = (const uint32_t*)D;
     x.exclPairs = (const uint2*)dPairs;
-    x.exclT = keyedByT ? (const uint32_t*)dT : nullptr;
+    x.exclT = tbits.empty() ? nullptr : (const uint32_t*)dT;
     return x;
   }
 };
 
-void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occluded, const RTCIntersectContext* ctx)
+void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occluded, const RTCIntersectContext* callerCtx)
 {
   Device* dev = s->device;
   RTCIntersectContext localCtx;
+  // the callbacks get the caller's own context object (applications derive from RTCIntersectContext: a copy would lose their fields); the
+  // only word written through it is instID[0] around the callbacks of a hit below an instance, put back before the call returns
+  RTCIntersectContext* ctx = const_cast<RTCIntersectContext*>(callerCtx);
   if (!ctx) { memset(&localCtx, 0, sizeof(localCtx)); localCtx.instID[0] = RTC_INVALID_GEOMETRY_ID; ctx = &localCtx; }
   const uint32_t instID = ctx->instID[0];
   const uint32_t recIn = occluded ? (uint32_t)sizeof(RTCRay) : (uint32_t)sizeof(RTCRayHit);
@@ -125,6 +122,7 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
   ExclList excl[Scene::NUM_ACCELS];
   for (ExclList& e : excl) e.perRay.resize(M);
   excl[Scene::QUAD].keyedByT = excl[Scene::QUADMB].keyedByT = excl[Scene::SUBDIV].keyedByT = true;
+  excl[Scene::INST].keyedByT = excl[Scene::INST].withInst = true; // below a mesh instance: (instance, geomID, primID, bits of t) for every leaf type
   std::vector<uint32_t> next;
   void* dExcl = nullptr;
   size_t dExclBytes = 0;
@@ -168,15 +166,27 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
         const bool found = got.hit.geomID != RTC_INVALID_GEOMETRY_ID &&
                            (got.ray.tfar != W[i].ray.tfar || got.hit.primID != W[i].hit.primID || got.hit.geomID != W[i].hit.geomID);
         if (!found) continue; // miss: the caller's record stays as it is
-        // a hit inside an instance names a geometry of the INSTANCED scene, and no filter applies to it (geometry filters inside instanced
-        // scenes are refused at commit, context filters on scenes with instances at the call): accepted as it is.  Such a hit carries the
-        // instance's geomID in instID, every other hit the context's value.
+        // a hit inside an instance names a geometry of the INSTANCED scene and carries the instance's geomID in instID, every other hit
+        // the context's value.  Without inst_filters=1 no filter applies to it (geometry filters inside instanced scenes are refused at
+        // commit, context filters on scenes with instances at the call): accepted as it is.  With the key, a hit below a MESH instance is
+        // resolved through the instance to the instanced scene's geometry, whose filter and user pointer the callbacks get; hits below an
+        // instance of a subdivision scene stay unfiltered (no filter can be set there, and the call refuses a context filter).
         const bool onInstance = s->hasInstances() && got.hit.instID[0] != instID;
         Geometry* geo = !onInstance && got.hit.geomID < s->geometries.size() ? s->geometries[got.hit.geomID] : nullptr;
+        bool belowMeshInstance = false;
+        if (onInstance && dev->inst_filters && got.hit.instID[0] < s->geometries.size()) {
+          const Geometry* inst = s->geometries[got.hit.instID[0]];
+          const Scene* o = inst && inst->type == RTC_GEOMETRY_TYPE_INSTANCE ? inst->instScene : nullptr;
+          Geometry* og = o && got.hit.geomID < o->geometries.size() ? o->geometries[got.hit.geomID] : nullptr;
+          if (og && (og->type == RTC_GEOMETRY_TYPE_TRIANGLE || og->type == RTC_GEOMETRY_TYPE_QUAD)) {
+            geo = og;
+            belowMeshInstance = true;
+          }
+        }
         const bool onSubdiv = geo && geo->type == RTC_GEOMETRY_TYPE_SUBDIVISION;
         const bool unfiltered = onSubdiv && forkAccel;
         RTCFilterFunctionN fn = geo && !unfiltered ? (occluded ? geo->occludedFilter : geo->intersectFilter) : nullptr;
-        RTCFilterFunctionN cfn = unfiltered ? nullptr : ctx->filter;
+        RTCFilterFunctionN cfn = unfiltered || (onInstance && !belowMeshInstance) ? nullptr : ctx->filter;
         bool accepted = true;
         RTCRayHit cand = W[i];
         cand.ray.tfar = got.ray.tfar; // filter.h / intersector_epilog.h:277-279: the callback sees tfar = candidate distance
@@ -190,8 +200,13 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
           a.ray = (RTCRayN*)&cand.ray;
           a.hit = (RTCHitN*)&hit;
           a.N = 1;
+          // below an instance the context names the instance while the callbacks run (instance_intersector.cpp:57-60).  The reference
+          // writes -1 back, which is what a top-level call held there; here the caller's value is put back, so that the hits of later
+          // rounds that are not on an instance (hit.instID = the context's value) stay right whatever the caller passed.
+          if (belowMeshInstance) ctx->instID[0] = got.hit.instID[0];
           if (fn) fn(&a);
           if (mask != 0 && cfn) cfn(&a);
+          if (belowMeshInstance) ctx->instID[0] = instID;
           accepted = mask != 0;
         }
         if (accepted) {
@@ -203,7 +218,8 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
           const bool onQuad = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD && geo->timeSteps == 1;
           const bool onQuadMB = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD && geo->timeSteps > 1; // as onTriMB; the two triangles of the quad are told apart by t
           const bool onTriMB = geo && geo->type == RTC_GEOMETRY_TYPE_TRIANGLE && geo->timeSteps > 1; // one record per segment, a ray sees one segment: (geomID, primID) names the candidate
-          excl[onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onQuadMB ? Scene::QUADMB : (onTriMB ? Scene::TRIMB : Scene::TRI)))].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb});
+          const size_t list = belowMeshInstance ? Scene::INST : onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onQuadMB ? Scene::QUADMB : (onTriMB ? Scene::TRIMB : Scene::TRI)));
+          excl[list].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb, got.hit.instID[0]});
           next.push_back(i);
         }
       }

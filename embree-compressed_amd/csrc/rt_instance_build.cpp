@@ -209,6 +209,7 @@ struct MeshInstances
   bool anyMeshMotion = false; // an instanced scene has a traceable motion-blur accel
   bool anyLinear = false;     // ... built under mb_bounds=linear (kinds 26..29): its nodes are QNodeMB8s
   uint32_t pendingMax = 0;    // most trees of one instanced scene, minus one
+  bool intersectFilter = false, occludedFilter = false; // inst_filters=1: an enabled geometry of a placed instance's scene has such a filter
 };
 
 // Instances are examined in geomID order.  The instanced scenes were committed before; what this commit sees of them is their committed
@@ -236,6 +237,9 @@ MeshInstances classify_mesh_instances(const Scene* s)
   // reads "not beside meshes in one instanced scene" - a scene of subdivision meshes only never gets here)
   const char* const only = meshMotionOk ? onlyMeshes : quadsOk ? onlyStatic : onlyTris;
   const bool linearOk = meshMotionOk && s->device->inst_mb_bounds == "linear";
+  // inst_filters=1: the meshes of an instanced scene may carry filter functions; what THIS commit sees of them is recorded below, for the
+  // scenes of the instances that are placed (as Scene::commit records triIntersectFilter / triOccludedFilter of its own meshes)
+  const bool filtersOk = s->device->inst_filters;
   bool haveKind = false, anySwept = false; // anySwept: a traceable motion-blur accel of the kinds 10..13 below this scene
   unsigned kindGeom = 0; // the instance whose scene fixed the arithmetic, and the accels that scene has: for the refusal below
   std::string kindNames;
@@ -255,12 +259,12 @@ MeshInstances classify_mesh_instances(const Scene* s)
       if (!og || !og->enabled) continue;
       const bool mesh = og->type == RTC_GEOMETRY_TYPE_TRIANGLE || (quadsOk && og->type == RTC_GEOMETRY_TYPE_QUAD);
       if (!mesh || (og->timeSteps != 1 && !meshMotionOk)) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
-      if (og->intersectFilter || og->occludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
+      if (!filtersOk && (og->intersectFilter || og->occludedFilter)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
     }
     for (const Accel* oa : o->accels())
       if (oa != &o->triAccel && !(quadsOk && oa == &o->quadAccel) && !(meshMotionOk && (oa == &o->triMBAccel || oa == &o->quadMBAccel)) && oa->kind != ACCEL_NONE)
         RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
-    if (o->triIntersectFilter || o->triOccludedFilter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
+    if (!filtersOk && (o->triIntersectFilter || o->triOccludedFilter)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
     const bool tris = o->triAccel.traceable(), quads = o->quadAccel.traceable();
     const bool trisMB = o->triMBAccel.traceable(), quadsMB = o->quadMBAccel.traceable();
     if (!tris && !quads && !trisMB && !quadsMB) continue; // empty scene: nothing to hit
@@ -313,6 +317,11 @@ MeshInstances classify_mesh_instances(const Scene* s)
     c.anyQuads |= quads;
     c.anyMotion |= g->local2world.size() > 1;
     c.placed.push_back({g, gid, o, instance_world_box(g, o)});
+    for (const Geometry* og : o->geometries) {
+      if (!og || !og->enabled) continue;
+      c.intersectFilter |= og->intersectFilter != nullptr;
+      c.occludedFilter |= og->occludedFilter != nullptr;
+    }
   }
   if (c.anyLinear && anySwept) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: motion blur accels of both node types below one scene");
   return c;
@@ -533,7 +542,10 @@ void build_instance_accel(Scene* s)
 {
   s->instAccel.clear();
   s->instCounts = Scene::InstanceCounts();
+  s->instIntersectFilter = s->instOccludedFilter = false;
   const MeshInstances c = classify_mesh_instances(s);
+  s->instIntersectFilter = c.intersectFilter;
+  s->instOccludedFilter = c.occludedFilter;
   if (!c.placed.empty()) s->instCounts = layout_mesh_instances(s, c);
 }
 

@@ -32,6 +32,7 @@ struct Device : RefCounted
   std::string quad_accel_mb = "default"; // quad meshes with more than one time step
   std::string mb_bounds = "swept"; // node boxes of the motion-blur mesh accels: "swept" (one box over the whole shutter, QNode8) or "linear" (time-dependent, QNodeMB8)
   std::string inst_mb_bounds = "swept"; // node boxes of motion-blur trees below an instance: "swept" (scenes built under mb_bounds=linear are refused below an instance) or "linear" (such scenes keep their QNodeMB8s, kinds ACCEL_INSTMESHMB_LINEAR_*)
+  bool inst_filters = false; // "inst_filters=1": filter functions run on hits below mesh instances (geometry filters inside instanced mesh scenes, RTCIntersectContext::filter on scenes with mesh instances); 0, the default: both are refused as before
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel, rt_instance_build.cpp, raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
@@ -386,6 +387,9 @@ struct Scene : RefCounted
   // filter callbacks present at commit time (Scene::hasGeometryFilterFunction, scene.h): they route a batch through the
   // host filter loop of rt_filter.cpp (the tri* flags cover quad meshes too)
   bool triIntersectFilter = false, triOccludedFilter = false, subdivFilter = false;
+  // the same for what lies below this scene's mesh instances (inst_filters=1; build_instance_accel, at this scene's commit): an enabled
+  // geometry with an intersect / occluded filter in the scene of a placed instance
+  bool instIntersectFilter = false, instOccludedFilter = false;
   std::mutex buildMutex;
   Box3 bounds;
 

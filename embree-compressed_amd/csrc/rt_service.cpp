@@ -280,7 +280,7 @@ static void combine_process(Device* dev, std::vector<Device::SmallCall*>& batch)
 void trace_call(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occluded, const RTCIntersectContext* ctx)
 {
   Device* dev = s->device;
-  if (M == 0 || M > COMBINE_MAX_RAYS || (ctx && ctx->filter) || s->triIntersectFilter || s->triOccludedFilter || s->subdivFilter || s->modified || (((uintptr_t)rays) & 3) ||
+  if (M == 0 || M > COMBINE_MAX_RAYS || (ctx && ctx->filter) || s->triIntersectFilter || s->triOccludedFilter || s->subdivFilter || s->instIntersectFilter || s->instOccludedFilter || s->modified || (((uintptr_t)rays) & 3) ||
       byteStride > 0xFFFFFFFFull || is_device_pointer(rays)) {
     trace_batch(s, rays, M, byteStride, occluded, ctx, nullptr); // large, device-resident, or about to raise its own error
     return;

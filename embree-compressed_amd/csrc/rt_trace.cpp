@@ -289,7 +289,9 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
   if (s->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "scene got not committed"); // scene.cpp:25,54
   if (M == 0) return;
   if (s->hasInstances()) { // refused before anything touches the GPU
-    if (ctx && ctx->filter) RT_THROW(RTC_ERROR_INVALID_OPERATION, "RTCIntersectContext::filter is not supported on a scene with instances");
+    // inst_filters=1: taken when all instances are mesh instances (the two-level kernel of subdivision instances has no exclusion scan)
+    if (ctx && ctx->filter && (!dev->inst_filters || s->instSubdivAccel.traceable()))
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "RTCIntersectContext::filter is not supported on a scene with instances");
     if (countersOut) RT_THROW(RTC_ERROR_INVALID_OPERATION, "counted batches are not supported on a scene with instances");
   }
   dev->useDevice();
@@ -297,7 +299,9 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
   if (((uintptr_t)rays) & 3) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "ray not aligned to 4 bytes"); // rtcore.cpp:413
   // (geometry filters on subdivision meshes are called on the eager accel only: the fork's intersector never calls one, see trace_filtered)
   const bool subdivFilters = s->subdivFilter && s->subdivAccel.kind == ACCEL_GRIDSOA;
-  if (!countersOut && ((ctx && ctx->filter) || subdivFilters || (occluded ? s->triOccludedFilter : s->triIntersectFilter))) {
+  // (instIntersectFilter / instOccludedFilter: filters below mesh instances, set only under inst_filters=1)
+  const bool instFilters = occluded ? s->instOccludedFilter : s->instIntersectFilter;
+  if (!countersOut && ((ctx && ctx->filter) || subdivFilters || instFilters || (occluded ? s->triOccludedFilter : s->triIntersectFilter))) {
     trace_filtered(s, rays, M, byteStride, occluded, ctx);
     return;
   }

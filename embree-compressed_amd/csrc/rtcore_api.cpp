@@ -961,6 +961,18 @@ API unsigned long long rtcamdDebugHostPoolSelfTest(RTCDevice h, unsigned int thr
   return 0;
 }
 
+API unsigned int rtcamdGetSceneFilterFlags(RTCScene h)
+{
+  CATCH_BEGIN
+  VERIFY(h);
+  const Scene* s = S(h);
+  return (s->triIntersectFilter ? RTCAMD_SCENE_FILTER_MESH_INTERSECT : 0u) | (s->triOccludedFilter ? RTCAMD_SCENE_FILTER_MESH_OCCLUDED : 0u) |
+         (s->subdivFilter ? RTCAMD_SCENE_FILTER_SUBDIV : 0u) | (s->instIntersectFilter ? RTCAMD_SCENE_FILTER_INSTANCED_INTERSECT : 0u) |
+         (s->instOccludedFilter ? RTCAMD_SCENE_FILTER_INSTANCED_OCCLUDED : 0u);
+  CATCH_END(devOf(h))
+  return 0;
+}
+
 API unsigned int rtcamdGetAccelRoot(RTCScene h)
 {
   CATCH_BEGIN

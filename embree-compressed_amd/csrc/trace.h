@@ -40,6 +40,10 @@ struct LaunchParams
   // Grid cells (eager subdivision path): the triangles of a patch share (geomID, primID), so an entry also carries the candidate's
   // distance, exclT[e] = bits of t - the kernels are deterministic, the same triangle yields the same t on the re-trace.
   // Quads use the same scheme (their two triangles share the quad's ids).
+  // Instance launches (the mesh instance accel, kinds 14..23, 30, 31; trace_instance_filter.hip): the listed candidates lie BELOW an
+  // instance, every entry is keyed by t whatever the leaf type, and exclT carries TWO words per entry, 8-byte aligned:
+  // exclT[2e] = bits of t, exclT[2e + 1] = geomID of the instance the candidate was found in; exclPairs[e] = the (geomID, primID)
+  // of the instanced scene's geometry.  exclOffsets is indexed by the ray's index in the batch, as everywhere.
   const uint32_t* exclOffsets;
   const uint2* exclPairs;
   const uint32_t* exclT;
@@ -133,6 +137,8 @@ hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  //
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb.hip
 hipError_t launch_trace_instance_subdiv(const LaunchParams& p, hipStream_t stream);  // trace_instance_subdiv.hip
 hipError_t launch_trace_instance_mesh_mb_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb_linear.hip
+// the three launchers above hand a launch with exclOffsets != nullptr (a filter re-trace below an instance, closest hit only) to this one
+hipError_t launch_trace_instance_filter(const LaunchParams& p, hipStream_t stream); // trace_instance_filter.hip
 // Development builds (-DTRACE_DEV_METRIC_ONLY, tools/README.md): of the subdivision accels only the metric's kind is dispatched (the
 // others fail with hipErrorInvalidValue, so that only trace_cbvh_leaf.hip has to be rebuilt), and launch_service serves no other kind.
 inline hipError_t launch_service(const ServiceParams& s, hipStream_t stream)

@@ -46,6 +46,7 @@ namespace rtamd {
 hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream)
 {
   if (p.counters) return hipErrorInvalidValue; // no instrumented twin (rt_trace.cpp refuses counted batches on scenes with instances)
+  if (p.exclOffsets) return launch_trace_instance_filter(p, stream); // a re-trace of the host filter loop: the EXCL form (trace_instance_filter.hip)
   switch (p.accel.kind) {
   case ACCEL_INST_TRI_PLUECKER: return p.occluded ? dev::launch_instance_vec<true, true, false, false>(p, stream) : dev::launch_instance_vec<true, false, false, false>(p, stream);
   case ACCEL_INST_TRI_MOELLER: return p.occluded ? dev::launch_instance_vec<false, true, false, false>(p, stream) : dev::launch_instance_vec<false, false, false, false>(p, stream);

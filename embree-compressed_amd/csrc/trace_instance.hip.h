@@ -57,11 +57,29 @@ constexpr int inst_min_waves(bool pluecker, bool occluded, bool quads, bool xfmb
 }
 constexpr int inst_nodemb_min_waves(bool pluecker, bool occluded) { return inst_min_waves(pluecker, occluded, true, true, true); }
 
+// Filter re-trace below an instance (the EXCL form of the body, trace_instance_filter.hip): a candidate the host filter loop rejected for this
+// ray before stays rejected.  The key is (instance geomID, geomID, primID, bits of t) for every leaf type: the kernels are deterministic,
+// the same record gives the same t when the ray is traced again; t tells the two triangles of a quad apart (a ray through the diagonal
+// v1-v3 hits both at one t: rejecting one rejects both) and a motion-blur record from its sibling; the instance tells apart two instances
+// of one scene that give the same local ray.  For instance launches an entry of exclT is two words (trace.h).
+__device__ __forceinline__ bool instance_candidate_excluded(const LaunchParams& P, uint32_t rayIdx, uint32_t inst, uint32_t geomID, uint32_t primID, float t)
+{
+  const uint2* __restrict__ ti = (const uint2*)P.exclT;
+  const uint32_t e1 = P.exclOffsets[rayIdx + 1];
+  for (uint32_t e = P.exclOffsets[rayIdx]; e < e1; e++) {
+    const uint2 q = P.exclPairs[e];
+    const uint2 k = ti[e];
+    if (q.x == geomID && q.y == primID && k.x == __float_as_uint(t) && k.y == inst) return true;
+  }
+  return false;
+}
+
 template <bool PLUECKER, bool OCCLUDED, bool VEC, bool QUADS, bool XFMB>
 __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUADS, XFMB)) void trace_instance_kernel(LaunchParams P)
 {
-  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB (it asserts them)
+  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, EXCL (it asserts them)
   constexpr bool MESHMB = false, NODEMB = false; // the MESHMB form is trace_instance_mesh_mb.hip's kernel, the NODEMB form trace_instance_mesh_mb_linear.hip's
+  constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 

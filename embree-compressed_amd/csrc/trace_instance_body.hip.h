@@ -1,10 +1,10 @@
 // The body of the two-level traversal kernel (trace_instance.hip, where it is described; trace_instance_mesh_mb.hip;
 // trace_instance_mesh_mb_linear.hip), as text: it is
 // included inside the braces of a __global__ function that has the launch parameters `P` and the compile-time constants PLUECKER,
-// OCCLUDED, VEC, QUADS, XFMB, MESHMB and NODEMB in scope.  Text and not a function called from the kernels: through a function the compiler
+// OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB and EXCL in scope.  Text and not a function called from the kernels: through a function the compiler
 // schedules the loads of the launch parameters differently, and the instruction streams of the instantiations of trace_instance.hip
 // are held to what they were (tools/kernel_metadata.py --digest, docs/experiments.md).  No include guard: one inclusion per kernel.
-// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and seven `bool`
+// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and eight `bool`
 // constants.  Everything else the text uses comes from the headers trace_instance.hip.h includes and from the TRACE_INST_* macros it
 // defines; the text declares only locals of its own and ends with the traversal loop.
 // trace_instance_subdiv.hip restates the refill, node step, ranking, instance entry and pop of this text for subdivision leaves: a fix to
@@ -12,8 +12,8 @@
   static_assert(std::is_same<decltype(P), LaunchParams>::value, "trace_instance_body.hip.h: `LaunchParams P` must be the kernel's parameter");
 #define TRACE_INSTANCE_BODY_BOOL(x) std::is_same<typename std::remove_const<decltype(x)>::type, bool>::value
   static_assert(TRACE_INSTANCE_BODY_BOOL(PLUECKER) && TRACE_INSTANCE_BODY_BOOL(OCCLUDED) && TRACE_INSTANCE_BODY_BOOL(VEC) && TRACE_INSTANCE_BODY_BOOL(QUADS) &&
-                    TRACE_INSTANCE_BODY_BOOL(XFMB) && TRACE_INSTANCE_BODY_BOOL(MESHMB) && TRACE_INSTANCE_BODY_BOOL(NODEMB),
-                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB and NODEMB must be bool constants in scope");
+                    TRACE_INSTANCE_BODY_BOOL(XFMB) && TRACE_INSTANCE_BODY_BOOL(MESHMB) && TRACE_INSTANCE_BODY_BOOL(NODEMB) && TRACE_INSTANCE_BODY_BOOL(EXCL),
+                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB and EXCL must be bool constants in scope");
 #undef TRACE_INSTANCE_BODY_BOOL
   constexpr uint32_t FETCH = TRACE_INST_FETCH;
   constexpr uint32_t QFETCH = TRACE_INST_QUAD_FETCH;
@@ -21,6 +21,10 @@
   constexpr uint32_t QMFETCH = TRACE_INST_QUADMB_FETCH;
   static_assert(!MESHMB || (QUADS && XFMB), "the MESHMB form carries the general layout: quads and instance steps");
   static_assert(!NODEMB || MESHMB, "the NODEMB form is the MESHMB form over time-dependent nodes in the motion-blur trees");
+  // EXCL (trace_instance_filter.hip, the re-traces of the host filter loop): in every leaf loop a candidate that passed its test is dropped
+  // before the block's minimum selection when the ray's exclusion list names it - (curInst, geomID, primID, bits of t), instance_candidate_excluded
+  // in trace_instance.hip.h.  P.exclOffsets is set for every launch of such a kernel and indexed by the ray's index in the batch.
+  static_assert(!EXCL || !OCCLUDED, "the filter loop runs closest-hit launches only");
   constexpr bool ROBUST = PLUECKER; // Pluecker <-> robust traversal, Moeller <-> fast traversal, on both levels
   __shared__ uint2 ldsStack[TRACE_LDS_STACK + 1][TRACE_BLOCK]; // + one scratch row for the branch-free pushes
   const uint32_t tid = threadIdx.x;
@@ -374,6 +378,7 @@
                 bool ok;
                 if (PLUECKER) ok = pluecker(r, a, bb, c, tfarBlock, h);
                 else ok = moeller(r, a, make_float4(a.x - bb.x, a.y - bb.y, a.z - bb.z, 0.0f), make_float4(c.x - a.x, c.y - a.y, c.z - a.z, 0.0f), tfarBlock, h);
+                if (EXCL) ok = ok && !instance_candidate_excluded(P, rayIdx, curInst, __float_as_uint(A0[k].w), __float_as_uint(B0[k].w), h.t);
                 if (ok) {
                   if (OCCLUDED) { occl = true; break; } // Occluded1EpilogM: any valid lane
                   if (!found || h.t < best.t) { // select_min over valid lanes, lowest lane wins ties
@@ -421,7 +426,8 @@
                 for (uint32_t half = 0; half < 2; half++) { // A then B of this quad (lanes g+k and 4+g+k)
                   const float4 v02 = half ? lerp_vertex(V[k][2], V[k][6], f) : lerp_vertex(V[k][0], V[k][4], f);
                   TriHit h;
-                  const bool ok = PLUECKER ? pluecker_quad(r, v02, v1, v3, tfarBlock, half != 0u, h) : moeller_quad(r, v02, v1, v3, tfarBlock, half != 0u, h);
+                  bool ok = PLUECKER ? pluecker_quad(r, v02, v1, v3, tfarBlock, half != 0u, h) : moeller_quad(r, v02, v1, v3, tfarBlock, half != 0u, h);
+                  if (EXCL) ok = ok && !instance_candidate_excluded(P, rayIdx, curInst, gid, pid, h.t);
                   if (ok) {
                     if (OCCLUDED) { occl = true; break; } // Occluded1EpilogM: any valid lane
                     const uint32_t lane = half * 4u + g + k; // select_min over the 8 lanes, lowest lane wins ties
@@ -466,8 +472,9 @@
 #pragma unroll
                 for (uint32_t half = 0; half < 2; half++) { // A then B of this quad (lanes g+k and 4+g+k)
                   TriHit h;
-                  const bool ok = PLUECKER ? pluecker_quad(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h)
-                                           : moeller_quad(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h);
+                  bool ok = PLUECKER ? pluecker_quad(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h)
+                                     : moeller_quad(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h);
+                  if (EXCL) ok = ok && !instance_candidate_excluded(P, rayIdx, curInst, gid, pid, h.t);
                   if (ok) {
                     if (OCCLUDED) { occl = true; break; } // Occluded1EpilogM: any valid lane
                     // select_min over the 8 lanes, lowest lane wins ties
@@ -509,7 +516,8 @@
               for (uint32_t k = 0; k < FETCH; k++) {
                 if (g + k >= nb) break;
                 TriHit h;
-                const bool ok = PLUECKER ? pluecker(r, A[k], B[k], C[k], tfarBlock, h) : moeller(r, A[k], B[k], C[k], tfarBlock, h);
+                bool ok = PLUECKER ? pluecker(r, A[k], B[k], C[k], tfarBlock, h) : moeller(r, A[k], B[k], C[k], tfarBlock, h);
+                if (EXCL) ok = ok && !instance_candidate_excluded(P, rayIdx, curInst, __float_as_uint(A[k].w), __float_as_uint(B[k].w), h.t);
                 if (ok) {
                   if (OCCLUDED) { occl = true; break; } // Occluded1EpilogM: any valid lane
                   // select_min over valid lanes, lowest lane wins ties (vfloat4_sse2.h:654-659)

@@ -27,6 +27,7 @@ template <bool PLUECKER, bool OCCLUDED, bool VEC>
 __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, true, true, true)) void trace_instance_mesh_mb_kernel(LaunchParams P)
 {
   constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = false; // always the general layout: quads and instance steps allowed
+  constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 
@@ -41,6 +42,7 @@ inline hipError_t launch_instance_mesh_mb_vec(const LaunchParams& p, hipStream_t
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream)
 {
   if (p.counters) return hipErrorInvalidValue; // no instrumented twin (rt_trace.cpp refuses counted batches on scenes with instances)
+  if (p.exclOffsets) return launch_trace_instance_filter(p, stream); // a re-trace of the host filter loop: the EXCL form (trace_instance_filter.hip)
   switch (p.accel.kind) {
   case ACCEL_INSTMESHMB_PLUECKER: return p.occluded ? dev::launch_instance_mesh_mb_vec<true, true>(p, stream) : dev::launch_instance_mesh_mb_vec<true, false>(p, stream);
   case ACCEL_INSTMESHMB_MOELLER: return p.occluded ? dev::launch_instance_mesh_mb_vec<false, true>(p, stream) : dev::launch_instance_mesh_mb_vec<false, false>(p, stream);

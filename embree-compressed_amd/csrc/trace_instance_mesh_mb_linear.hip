@@ -18,6 +18,7 @@ template <bool PLUECKER, bool OCCLUDED, bool VEC>
 __global__ __launch_bounds__(TRACE_BLOCK, inst_nodemb_min_waves(PLUECKER, OCCLUDED)) void trace_instance_mesh_mb_linear_kernel(LaunchParams P)
 {
   constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = true;
+  constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 
@@ -32,6 +33,7 @@ inline hipError_t launch_instance_mesh_mb_linear_vec(const LaunchParams& p, hipS
 hipError_t launch_trace_instance_mesh_mb_linear(const LaunchParams& p, hipStream_t stream)
 {
   if (p.counters) return hipErrorInvalidValue; // no instrumented twin (rt_trace.cpp refuses counted batches on scenes with instances)
+  if (p.exclOffsets) return launch_trace_instance_filter(p, stream); // a re-trace of the host filter loop: the EXCL form (trace_instance_filter.hip)
   switch (p.accel.kind) {
   case ACCEL_INSTMESHMB_LINEAR_PLUECKER: return p.occluded ? dev::launch_instance_mesh_mb_linear_vec<true, true>(p, stream) : dev::launch_instance_mesh_mb_linear_vec<true, false>(p, stream);
   case ACCEL_INSTMESHMB_LINEAR_MOELLER: return p.occluded ? dev::launch_instance_mesh_mb_linear_vec<false, true>(p, stream) : dev::launch_instance_mesh_mb_linear_vec<false, false>(p, stream);

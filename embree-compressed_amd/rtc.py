@@ -109,6 +109,13 @@ class RTCInterpolateNArguments(C.Structure):
                 ("valueCount", C.c_uint)]
 
 
+# rtcore_amd.h: enum RTCAMDSceneFilterFlags (Scene.filter_flags)
+RTCAMD_SCENE_FILTER_MESH_INTERSECT = 1
+RTCAMD_SCENE_FILTER_MESH_OCCLUDED = 2
+RTCAMD_SCENE_FILTER_SUBDIV = 4
+RTCAMD_SCENE_FILTER_INSTANCED_INTERSECT = 8
+RTCAMD_SCENE_FILTER_INSTANCED_OCCLUDED = 16
+
 # rtcore_amd.h: enum RTCAMDDeviceProperty
 RTCAMD_DEVICE_PROPERTY_TRACE_LAUNCHES = 240
 RTCAMD_DEVICE_PROPERTY_COMBINED_CALLS = 241
@@ -204,6 +211,7 @@ def load_library(path=LIB_PATH):
         "rtcamdOccluded1MCounted": (None, [vp, C.POINTER(RTCIntersectContext), vp, u, sz, C.POINTER(RTCAMDTraceCounters)]),
         "rtcamdGetAccelData": (vp, [vp, u, C.POINTER(sz)]),
         "rtcamdGetAccelRoot": (u, [vp]),
+        "rtcamdGetSceneFilterFlags": (u, [vp]),
         "rtcamdGetGeometryWorld2Local": (None, [vp, C.c_float, C.c_int, vp]),
         "rtcamdDebugReadWaveLog": (C.c_size_t, [vp, vp, C.c_size_t]),
         "rtcamdDebugHoldCombiner": (None, [vp, C.c_int]),
@@ -211,7 +219,7 @@ def load_library(path=LIB_PATH):
         "rtcamdDebugHostPoolSelfTest": (C.c_ulonglong, [vp, u, u, u, u]),
     }
     for name, (res, args) in sig.items():
-        if (name.startswith("rtcamdDebug") or name == "rtcamdGetGeometryWorld2Local") and not hasattr(lib, name):
+        if (name.startswith("rtcamdDebug") or name in ("rtcamdGetGeometryWorld2Local", "rtcamdGetSceneFilterFlags")) and not hasattr(lib, name):
             continue  # development hooks and the newest extension: an older build of the library (RTAMD_LIB=... in an A/B sweep) may lack them
         fn = getattr(lib, name)
         fn.restype = res
@@ -529,6 +537,25 @@ class Scene:
         self.lib.rtcCommitGeometry(g)
         self._keep += [intersect, occluded]
         self.device.check("set_filters")
+
+    def set_user_data(self, geom_id, ptr):
+        """rtcSetGeometryUserData: `ptr` (an address or None) is what the geometry's filter callbacks get as geometryUserPtr - also
+        when the geometry is hit through an instance of its scene (device config inst_filters=1)."""
+        self.lib.rtcSetGeometryUserData(self.lib.rtcGetGeometry(self.handle, geom_id), ptr)
+        self.device.check("set_user_data")
+
+    def set_enabled(self, geom_id, enabled):
+        """rtcEnableGeometry / rtcDisableGeometry + rtcCommitGeometry; the scene is committed by the caller."""
+        g = self.lib.rtcGetGeometry(self.handle, geom_id)
+        (self.lib.rtcEnableGeometry if enabled else self.lib.rtcDisableGeometry)(g)
+        self.lib.rtcCommitGeometry(g)
+        self.device.check("set_enabled")
+
+    def filter_flags(self):
+        """rtcamdGetSceneFilterFlags: RTCAMD_SCENE_FILTER_* bits, the geometry filter functions the last commit saw."""
+        v = self.lib.rtcamdGetSceneFilterFlags(self.handle)
+        self.device.check("rtcamdGetSceneFilterFlags")
+        return int(v)
 
     def set_vertex_attribute(self, geom_id, slot, values, topology_index=None, mode=None):
         """Bind a float32 [nv, k] (k <= 4) array as vertex attribute `slot` of an attached geometry and re-commit it.

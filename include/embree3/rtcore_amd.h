@@ -136,6 +136,18 @@ RTC_API void rtcamdDebugCbvhLeafCodec(const float* box, const float* v, float ex
 RTC_API unsigned long long rtcamdDebugHostPoolSelfTest(RTCDevice device, unsigned int threads, unsigned int cycles, unsigned int jobs, unsigned int parts);
 /* Root reference of the BVH8 (encoding documented in DESIGN.md / csrc/accel.h). */
 RTC_API unsigned int rtcamdGetAccelRoot(RTCScene scene);
+/* The geometry filter functions the scene's last commit saw - what routes a batch through the host filter loop: on its own enabled
+ * triangle / quad meshes (intersect, occluded), on its subdivision meshes (either), and - device config inst_filters=1 only - on the
+ * enabled meshes of the scenes of its placed mesh instances (intersect, occluded). */
+enum RTCAMDSceneFilterFlags
+{
+  RTCAMD_SCENE_FILTER_MESH_INTERSECT = 1,
+  RTCAMD_SCENE_FILTER_MESH_OCCLUDED = 2,
+  RTCAMD_SCENE_FILTER_SUBDIV = 4,
+  RTCAMD_SCENE_FILTER_INSTANCED_INTERSECT = 8,
+  RTCAMD_SCENE_FILTER_INSTANCED_OCCLUDED = 16
+};
+RTC_API unsigned int rtcamdGetSceneFilterFlags(RTCScene scene);
 
 #if defined(__cplusplus)
 }

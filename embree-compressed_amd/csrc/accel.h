@@ -228,10 +228,32 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // A child or root reference inside a motion-blur tree indexes the buffer as ONE array of QNodeMB8: (the section's byte offset) / 144 +
 // the node's place in the section (below 2^31, or the commit is refused).  The QNodeMB8s are the instanced scene's own nodes, byte for
 // byte apart from the rebased child words, so the containment guarantee of QNodeMB8 holds below an instance as it stands.  The
-// top-level tree and the boxes of moving instances are QNode8s over swept boxes as in all instance kinds.  Which node type a reference
+// top-level tree and the boxes of moving instances are QNode8s over swept boxes as in all instance kinds but ACCEL_INSTTOP_LINEAR_*.  Which node type a reference
 // names follows from where it was found: the roots triMBRoot / quadMBRoot of an InstanceSceneRecord and every child below them name
 // QNodeMB8s, everything else QNode8s (the kernel keeps the tree's code in its lane state, INST_TREE_*: bit 1 = a motion-blur tree).
 // blobOffsets holds two words for inspection: the number of QNodeMB8s and the index of the first one, in 144-byte units.
+//
+// Kinds ACCEL_INSTTOP_LINEAR_PLUECKER / _MOELLER (inst_bounds=linear, at least one enabled instance with more than one time step): the
+// top-level tree itself is made of time-dependent nodes, so a ray enters a moving instance only where the instance is at the ray's time.
+// `prims` and `blobs` are ALWAYS the general layout of the kinds ACCEL_INSTMESHMB_* (one InstanceSceneRecord per distinct scene, the
+// InstanceSteps, quad, TriMBRecord and QuadMBRecord sections - the last two empty when no instanced scene has moving meshes), so that
+// one kernel form serves; `root` of an InstanceRecord names its scene's InstanceSceneRecord.  The node array has the two sections of
+// the kinds ACCEL_INSTMESHMB_LINEAR_*, with the top-level tree in the second:
+//   nodes : every scene's static triangle and quad trees (QNode8, scene by scene in the order of first use) |
+//           zero padding up to a multiple of 144 bytes from the start of the buffer |
+//           top-level tree | scene 0: MB triangle, MB quad nodes | scene 1: ... | ...                         (QNodeMB8)
+// AccelDesc::root and the inner child references of the top-level tree index the buffer as ONE array of QNodeMB8, as the references
+// of the motion-blur trees do (below 2^31, or the commit is refused); a top scene of a single instance still gets a root node, of one
+// child, so that its box is tested.  Motion-blur trees exist below such a top scene only on a device that also has
+// mb_bounds=linear,inst_mb_bounds=linear - they are QNodeMB8s then, so the code bit INST_TREE_* & 2 keeps its one meaning - and the
+// commit refuses moving meshes below the instances otherwise.  Which node type a reference names: everything found outside an
+// instance and in a motion-blur tree names QNodeMB8s, the static trees of the instanced scenes QNode8s.
+// Child i of a top-level node holds, at every time t in [0, 1], the images of the eight corners of the instanced scenes' bounds
+// under lerp(step[k], step[k + 1], f) of every instance below it (instance_linear_bounds, rt_instance_build.cpp, hands quantize_node_mb
+// end boxes whose interpolation does; the quantizer's one-step padding covers fp32 as argued at QNodeMB8: all that enters the argument
+// is that the bounded points move on straight lines between step times, with |p1 - p0| on the node's grid).  A static instance has
+// equal boxes at both ends.  blobOffsets holds the two inspection words of the kinds ACCEL_INSTMESHMB_LINEAR_*; Accel::maxDepth and
+// Scene::bounds (extended by the swept unions) are what they are in every instance kind.
 //
 // Kinds ACCEL_INSTSUBDIV_GRID / ACCEL_INSTSUBDIV_CBVH_LEAF (Scene::instSubdivAccel, an accel of its own beside the one above): instances
 // of scenes that hold subdivision meshes only, all with the eager accel or all with bvh4.compressed.leaf at one compression level C.  Per
@@ -392,11 +414,20 @@ enum AccelKind : uint32_t
   // inst_mb_bounds=linear: the kinds 22 / 23 when at least one instanced scene's motion-blur accel is of the kinds 26..29.  `nodes` holds
   // two sections, QNode8s and then QNodeMB8s (see InstanceRecord); `blobs` and `prims` are those of the kinds 22 / 23
   ACCEL_INSTMESHMB_LINEAR_PLUECKER = 30,
-  ACCEL_INSTMESHMB_LINEAR_MOELLER = 31
+  ACCEL_INSTMESHMB_LINEAR_MOELLER = 31,
+  // inst_bounds=linear: the mesh instance accel of a top scene with at least one moving instance.  The top-level tree is made of QNodeMB8s
+  // in the second section of `nodes`; `blobs` and `prims` are the general layout of the kinds 22 / 23 / 30 / 31 (see InstanceRecord)
+  ACCEL_INSTTOP_LINEAR_PLUECKER = 32,
+  ACCEL_INSTTOP_LINEAR_MOELLER = 33
 };
 inline bool is_inst_linear_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_LINEAR_PLUECKER || kind == ACCEL_INSTMESHMB_LINEAR_MOELLER; } // traced by trace_instance_mesh_mb_linear.hip
-// traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip / trace_instance_mesh_mb_linear.hip
-inline bool is_instance_kind(uint32_t kind) { return (kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF) || is_inst_linear_kind(kind); }
+inline bool is_inst_top_linear_kind(uint32_t kind) { return kind == ACCEL_INSTTOP_LINEAR_PLUECKER || kind == ACCEL_INSTTOP_LINEAR_MOELLER; } // traced by trace_instance_top_linear.hip
+// the instance kinds whose node buffer has two sections, QNode8s and QNodeMB8s (Accel::nodeImage)
+inline bool is_inst_two_section_kind(uint32_t kind) { return is_inst_linear_kind(kind) || is_inst_top_linear_kind(kind); }
+// the instance kinds with the general layout of `blobs` (InstanceSceneRecords)
+inline bool is_inst_general_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_PLUECKER || kind == ACCEL_INSTMESHMB_MOELLER || is_inst_two_section_kind(kind); }
+// traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip / trace_instance_mesh_mb_linear.hip / trace_instance_top_linear.hip
+inline bool is_instance_kind(uint32_t kind) { return (kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF) || is_inst_two_section_kind(kind); }
 
 inline bool is_mb_linear_kind(uint32_t kind) { return kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER; } // nodes are QNodeMB8
 // the arithmetic of a motion-blur mesh accel, under swept and under linear bounds
@@ -409,7 +440,7 @@ inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKE
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
 {
-  const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_*
+  const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_*
   const TriRecord* prims;
   const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16

@@ -49,6 +49,10 @@ void Device::parse(const std::string& cfg)
       if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "inst_mb_bounds=: unknown value '" + val + "' (swept or linear)");
       inst_mb_bounds = val;
     }
+    else if (key == "inst_bounds") {
+      if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "inst_bounds=: unknown value '" + val + "' (swept or linear)");
+      inst_bounds = val;
+    }
     else if (key == "inst_filters") {
       if (val != "0" && val != "1") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "inst_filters=: unknown value '" + val + "' (0 or 1)");
       inst_filters = val == "1";
@@ -112,6 +116,7 @@ Device::Device(const char* cfg)
   if (const char* env = getenv("RTAMD_WALK_BATCH")) tuneWalkBatch = (uint32_t)std::max(1, atoi(env));
   if (const char* env = getenv("RTAMD_OCT_MAX")) tuneOctMax = (uint32_t)std::max(0, atoi(env));
   if (const char* env = getenv("RTAMD_KERNEL")) tunePoolKernel = strcmp(env, "pool") == 0 ? 1u : (strcmp(env, "lane") == 0 ? 0u : 2u);
+  if (const char* env = getenv("RTAMD_INST_SPILL_MAX")) tuneInstSpillMax = (uint32_t)std::max(0, atoi(env));
   if (const char* env = getenv("RTAMD_BLOCKS_PER_CU")) { tuneBlocksPerCU = (uint32_t)std::max(0, atoi(env)); tuneBlocksAuto = false; }
   if (cfg) parse(cfg);
   if (gpu == -1) {

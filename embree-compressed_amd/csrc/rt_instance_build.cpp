@@ -1,10 +1,11 @@
 // The two instance accels of a scene, built at commit from the committed accels of the instanced scenes (layouts: accel.h InstanceRecord).
-// build_instance_accel places the instances of mesh scenes (kinds 14..23, 30, 31), build_instance_subdiv_accel those of subdivision
+// build_instance_accel places the instances of mesh scenes (kinds 14..23, 30..33), build_instance_subdiv_accel those of subdivision
 // scenes (kinds 24, 25).  Each is: classify (which instances take part, which arithmetic, every refusal that depends on what the scenes
 // hold), then lay out (where things go), and the layouts are put together from one set of stages:
 //   instance_world_box        the box of one instance in the top scene
 //   distinct_scenes           the instanced scenes in order of first use: each is stored once, however many instances share it
 //   build_top_level           the BVH8 over the instances' boxes, one instance per leaf
+//   build_top_level_linear    the same over time-dependent boxes (inst_bounds=linear; instance_time_boxes, instance_linear_bounds)
 //   Section, add_section      where the sections of a byte array start (`blobs`, and the node buffer of the kinds 30 / 31)
 //   place_leaf_records        one scene's leaf records into their section
 //   append_tree               one scene's tree behind the nodes placed so far, references rebased
@@ -55,6 +56,54 @@ Box3 instance_world_box(const Geometry* g, const Scene* o)
   if (!(std::isfinite(box.lo.x) && std::isfinite(box.lo.y) && std::isfinite(box.lo.z) && std::isfinite(box.hi.x) && std::isfinite(box.hi.y) && std::isfinite(box.hi.z)))
     RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance transform yields bounds that are not finite");
   return box;
+}
+
+// inst_bounds=linear: the box of an instance at each of its time steps and at mid-shutter, in double (a static instance: none, its
+// `box` serves at every time).  Step k is at the global time k / S, S = steps - 1.
+struct InstanceTimeBoxes
+{
+  struct BoxD
+  {
+    double lo[3], hi[3];
+    BoxD() { for (int a = 0; a < 3; a++) { lo[a] = std::numeric_limits<double>::infinity(); hi[a] = -lo[a]; } }
+    void extend(const double* p) { for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); } }
+  };
+  std::vector<BoxD> steps;
+  Box3 mid; // topology only: rounded to fp32 as it comes
+};
+
+// the eight corners of `b` through the affine map m (columns vx, vy, vz, p), in double
+void extend_by_image(InstanceTimeBoxes::BoxD& box, const double* m, const Box3& b)
+{
+  const V3 c[2] = {b.lo, b.hi};
+  for (int i = 0; i < 8; i++) {
+    const double q[3] = {(double)c[i >> 2].x, (double)c[(i >> 1) & 1].y, (double)c[i & 1].z};
+    double r[3];
+    for (int k = 0; k < 3; k++) r[k] = q[0] * m[k] + q[1] * m[3 + k] + q[2] * m[6 + k] + m[9 + k];
+    box.extend(r);
+  }
+}
+
+InstanceTimeBoxes instance_time_boxes(const Geometry* g, const Scene* o)
+{
+  InstanceTimeBoxes tb;
+  const size_t n = g->local2world.size();
+  if (n < 2) return tb;
+  double m[12];
+  for (const Geometry::Xfm& step : g->local2world) {
+    for (int k = 0; k < 12; k++) m[k] = (double)step[k];
+    tb.steps.emplace_back();
+    extend_by_image(tb.steps.back(), m, o->bounds);
+  }
+  // mid-shutter: lerp(step[k], step[k + 1], f) at time 0.5
+  const double ts = 0.5 * (double)(n - 1);
+  const size_t k = std::min((size_t)ts, n - 2);
+  const double f = ts - (double)k;
+  for (int j = 0; j < 12; j++) m[j] = (1.0 - f) * (double)g->local2world[k][j] + f * (double)g->local2world[k + 1][j];
+  InstanceTimeBoxes::BoxD mid;
+  extend_by_image(mid, m, o->bounds);
+  for (int a = 0; a < 3; a++) { tb.mid.lo[a] = (float)mid.lo[a]; tb.mid.hi[a] = (float)mid.hi[a]; }
+  return tb;
 }
 
 // The distinct instanced scenes in order of first use, and which of them each placed instance names.
@@ -112,6 +161,95 @@ std::vector<uint32_t> build_top_level(Scene* s, const std::vector<PlacedInstance
   A.maxDepth = r.maxDepth;
   A.leafCount = r.leafCount;
   return order;
+}
+
+// inst_bounds=linear: the end boxes B(0), B(1) of one child of a top-level node over the instances prims[begin, end), whose linear
+// interpolation holds every instance below the child at every time in [0, 1].  The construction is linear_bounds' of rt_scene.cpp (the
+// reference's linearBounds): the first guess is the union of the instances' boxes at their first step and the union of their boxes at
+// their last step; both ends are then widened, per plane, by the largest amount by which any instance's box at any of its step times
+// k / S sticks out of the interpolated guess.  A static instance contributes its one box at both ends and never sticks out.
+// Why the result holds a moving instance BETWEEN its steps too:
+//  1. Between two steps the instance's transform is lerp(step[k], step[k + 1], f), and the lerp of two affine maps sends a point to the
+//     lerp of its images: every corner of the instanced scene's bounds (hence, the maps being affine, everything inside them) moves on
+//     a straight line from its place at step k to its place at step k + 1.
+//  2. Each plane of the instance's true box at time t is therefore bounded by the piecewise-linear interpolant of the planes of its
+//     step boxes (a max / min of linear functions lies below / above the chord of its end values).
+//  3. A plane that is linear in t and lies outside every step box at that step's time lies outside that interpolant on every piece,
+//     both being linear there - and after the widening the planes of lerp(B(0), B(1), t) are such planes.
+// Computed in double and rounded outward to fp32; what double loses, and the fp32 arithmetic of the kernel's decode and of its
+// interpolated transform, is covered by the one-grid-step padding of quantize_node_mb as argued in accel.h (QNodeMB8, InstanceRecord).
+void instance_linear_bounds(const std::vector<PlacedInstance>& placed, const std::vector<InstanceTimeBoxes>& time, const BuildPrim* prims, size_t begin, size_t end, Box3& b0, Box3& b1)
+{
+  typedef InstanceTimeBoxes::BoxD BoxD;
+  auto static_box = [&](size_t id) {
+    BoxD b;
+    for (int a = 0; a < 3; a++) { b.lo[a] = (double)placed[id].box.lo[a]; b.hi[a] = (double)placed[id].box.hi[a]; }
+    return b;
+  };
+  BoxD g0, g1; // the guess
+  for (size_t i = begin; i < end; i++) {
+    const std::vector<BoxD>& st = time[prims[i].id].steps;
+    const BoxD first = st.empty() ? static_box(prims[i].id) : st.front(), last = st.empty() ? first : st.back();
+    g0.extend(first.lo); g0.extend(first.hi);
+    g1.extend(last.lo); g1.extend(last.hi);
+  }
+  for (int a = 0; a < 3; a++) {
+    double dlo = 0.0, dhi = 0.0; // how far any step box sticks out of the interpolated guess
+    for (size_t i = begin; i < end; i++) {
+      const std::vector<BoxD>& st = time[prims[i].id].steps;
+      for (size_t k = 0; k < st.size(); k++) {
+        const double t = (double)k / (double)(st.size() - 1);
+        dlo = std::max(dlo, ((1.0 - t) * g0.lo[a] + t * g1.lo[a]) - st[k].lo[a]);
+        dhi = std::max(dhi, st[k].hi[a] - ((1.0 - t) * g0.hi[a] + t * g1.hi[a]));
+      }
+    }
+    // (the interpolated guess is itself rounded: one more ulp of double on each side, far inside the quantizer's padding)
+    auto down = [](double x) { float f = (float)x; return (double)f > x ? nextafterf(f, -std::numeric_limits<float>::infinity()) : f; };
+    auto up = [](double x) { float f = (float)x; return (double)f < x ? nextafterf(f, std::numeric_limits<float>::infinity()) : f; };
+    b0.lo[a] = down(g0.lo[a] - dlo); b1.lo[a] = down(g1.lo[a] - dlo);
+    b0.hi[a] = up(g0.hi[a] + dhi); b1.hi[a] = up(g1.hi[a] + dhi);
+  }
+}
+
+// The top-level tree under inst_bounds=linear: QNodeMB8s, one instance per leaf as in build_top_level.  The topology is the midpoint SAH
+// build over every instance's box at mid-shutter (a static instance: its box); the boxes stored are instance_linear_bounds'.  Returns the
+// nodes with references that count from the tree's own first node - the layout rebases them - and fills A.root likewise, A.maxDepth
+// and A.leafCount.  A single instance makes a tree that is one leaf: it gets a root node of one child, so that a ray is tested against
+// the instance's box at its time before it pays for the entry (depth 1).
+std::vector<QNodeMB8> build_top_level_linear(Scene* s, const std::vector<PlacedInstance>& placed, Accel& A, std::vector<uint32_t>& order)
+{
+  if (placed.size() >= LEAF_RECORD_LIMIT) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instances for the 26-bit leaf reference");
+  std::vector<InstanceTimeBoxes> time(placed.size());
+  std::vector<BuildPrim> bp(placed.size());
+  for (size_t i = 0; i < placed.size(); i++) {
+    time[i] = instance_time_boxes(placed[i].geom, placed[i].scene);
+    bp[i].box = time[i].steps.empty() ? placed[i].box : time[i].mid;
+    bp[i].id = (uint32_t)i;
+    s->bounds.extend(placed[i].box); // the swept union, as in build_top_level
+  }
+  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
+    if (end - begin != 1) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: a leaf must hold one instance");
+    order.push_back(prims[begin].id);
+    return make_tri_leaf((uint32_t)order.size() - 1u, 1u);
+  };
+  auto bounds = [&](const BuildPrim* prims, size_t begin, size_t end, Box3& b0, Box3& b1) { instance_linear_bounds(placed, time, prims, begin, end, b0, b1); };
+  BuildSettings cfg;
+  cfg.blockSize = 1; cfg.minLeaf = 1; cfg.maxLeaf = 1;
+  cfg.threads = 1; // the leaf callback appends in leaf order
+  BuildResultMB r = build_bvh8_mb(bp, cfg, makeLeaf, bounds);
+  if (r.root & REF_LEAF) {
+    Box3 b0, b1;
+    bounds(bp.data(), 0, 1, b0, b1);
+    QNodeMB8 q;
+    quantize_node_mb(&b0, &b1, &r.root, 1, q);
+    r.nodes.assign(1, q);
+    r.root = 0u;
+    r.maxDepth = 1u;
+  }
+  A.root = r.root;
+  A.maxDepth = r.maxDepth;
+  A.leafCount = r.leafCount;
+  return std::move(r.nodes);
 }
 
 // Where the sections of one byte array start.  A section holds records of `recordBytes` each and starts at the next multiple of its own
@@ -208,6 +346,7 @@ struct MeshInstances
   bool anyMotion = false;     // an instance has more than one time step
   bool anyMeshMotion = false; // an instanced scene has a traceable motion-blur accel
   bool anyLinear = false;     // ... built under mb_bounds=linear (kinds 26..29): its nodes are QNodeMB8s
+  bool topLinear = false;     // inst_bounds=linear and anyMotion: the top-level tree is made of QNodeMB8s (kinds ACCEL_INSTTOP_LINEAR_*)
   uint32_t pendingMax = 0;    // most trees of one instanced scene, minus one
   bool intersectFilter = false, occludedFilter = false; // inst_filters=1: an enabled geometry of a placed instance's scene has such a filter
 };
@@ -221,6 +360,10 @@ struct MeshInstances
 // meshes below an instance are taken at all): an instanced scene whose motion-blur accels were built under mb_bounds=linear is placed
 // only then; without the key it is refused as before.  One device has one mb_bounds and an instance cannot name a scene of another
 // device (Geometry::setInstancedScene), so the motion-blur trees below one top scene are all of one node type.
+// Time-dependent top-level boxes (inst_bounds=linear, Device::inst_top_linear_enabled): a top scene with a moving instance among those
+// placed here gets the kinds ACCEL_INSTTOP_LINEAR_*; one without keeps its kind and bytes.  Moving meshes below the instances of such a
+// top scene must come as QNodeMB8 trees (mb_bounds=linear,inst_mb_bounds=linear), so that one node type serves every motion-blur tree
+// of the kernel's TOPMB form; otherwise the commit is refused with a message that names the three keys.
 // Subdivision scenes below an instance: an instanced scene that enables a subdivision mesh is left to build_instance_subdiv_accel when
 // the device takes such scenes (Device::inst_subdiv_enabled); otherwise it is refused here with the message of the config, as before.
 MeshInstances classify_mesh_instances(const Scene* s)
@@ -240,6 +383,17 @@ MeshInstances classify_mesh_instances(const Scene* s)
   // inst_filters=1: the meshes of an instanced scene may carry filter functions; what THIS commit sees of them is recorded below, for the
   // scenes of the instances that are placed (as Scene::commit records triIntersectFilter / triOccludedFilter of its own meshes)
   const bool filtersOk = s->device->inst_filters;
+  // inst_bounds=linear: will this top scene get the time-dependent top level?  Known before the scenes are examined, so that the refusal of
+  // moving meshes below it has its own text from the first instance on (a moving instance of an empty scene is not placed and does not count)
+  bool wantTopLinear = false;
+  if (s->device->inst_top_linear_enabled())
+    for (const Geometry* g : s->geometries)
+      if (g && g->enabled && g->type == RTC_GEOMETRY_TYPE_INSTANCE && g->local2world.size() > 1 && g->instScene && !(subdivOk && is_subdivision_scene(g->instScene))) {
+        const Scene* o = g->instScene;
+        wantTopLinear |= o->triAccel.traceable() || o->quadAccel.traceable() || o->triMBAccel.traceable() || o->quadMBAccel.traceable();
+      }
+  const char* const topLinearNeedsLinear = "inst_bounds=linear: a scene with moving instances takes instanced scenes with motion blur meshes only when their accels hold "
+                                           "time-dependent nodes (use mb_bounds=linear,inst_mb_bounds=linear beside inst_bounds=linear, or inst_bounds=swept)";
   bool haveKind = false, anySwept = false; // anySwept: a traceable motion-blur accel of the kinds 10..13 below this scene
   unsigned kindGeom = 0; // the instance whose scene fixed the arithmetic, and the accels that scene has: for the refusal below
   std::string kindNames;
@@ -253,6 +407,8 @@ MeshInstances classify_mesh_instances(const Scene* s)
     if (subdivOk && is_subdivision_scene(o)) continue; // build_instance_subdiv_accel places it
     // without inst_mb_bounds=linear the instanced scenes' trees are copied behind the top-level tree as QNode8s: time-dependent nodes
     // have no place there
+    if (!linearOk && wantTopLinear && (is_mb_linear_kind(o->triMBAccel.kind) || is_mb_linear_kind(o->quadMBAccel.kind)))
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, topLinearNeedsLinear);
     if (!linearOk && (is_mb_linear_kind(o->triMBAccel.kind) || is_mb_linear_kind(o->quadMBAccel.kind)))
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene with a motion blur accel built under mb_bounds=linear is not supported (instance accels hold swept node boxes: use mb_bounds=swept)");
     for (Geometry* og : o->geometries) {
@@ -324,6 +480,8 @@ MeshInstances classify_mesh_instances(const Scene* s)
     }
   }
   if (c.anyLinear && anySwept) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: motion blur accels of both node types below one scene");
+  c.topLinear = c.anyMotion && s->device->inst_top_linear_enabled();
+  if (c.topLinear && anySwept) RT_THROW(RTC_ERROR_INVALID_OPERATION, topLinearNeedsLinear);
   return c;
 }
 
@@ -332,9 +490,11 @@ MeshInstances classify_mesh_instances(const Scene* s)
 // (kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER).  As soon as one enabled instance has more than one time step the kinds are
 // ACCEL_INSTMB_* (chosen otherwise exactly as ACCEL_INST_*); as soon as one instanced scene has a traceable motion-blur accel they are
 // ACCEL_INSTMESHMB_*, and ACCEL_INSTMESHMB_LINEAR_* as soon as one of those accels holds QNodeMB8s.  A top scene without a motion-blur
-// accel below it keeps the kinds 14..21 and their arrays, whatever the config names.
+// accel below it keeps the kinds 14..21 and their arrays, whatever the config names.  Under inst_bounds=linear a top scene with a moving
+// instance is of the kinds ACCEL_INSTTOP_LINEAR_*, whatever lies below its instances.
 uint32_t instance_kind(const MeshInstances& c)
 {
+  if (c.topLinear) return c.pluecker ? ACCEL_INSTTOP_LINEAR_PLUECKER : ACCEL_INSTTOP_LINEAR_MOELLER;
   if (c.anyLinear) return c.pluecker ? ACCEL_INSTMESHMB_LINEAR_PLUECKER : ACCEL_INSTMESHMB_LINEAR_MOELLER;
   if (c.anyMeshMotion) return c.pluecker ? ACCEL_INSTMESHMB_PLUECKER : ACCEL_INSTMESHMB_MOELLER;
   if (c.anyMotion) return c.anyQuads ? (c.pluecker ? ACCEL_INSTMB_PLUECKER : ACCEL_INSTMB_MOELLER) : (c.pluecker ? ACCEL_INSTMB_TRI_PLUECKER : ACCEL_INSTMB_TRI_MOELLER);
@@ -348,7 +508,8 @@ uint32_t instance_kind(const MeshInstances& c)
 //           | one InstanceSceneRecord per scene, which holds its four roots | TriMBRecords | QuadMBRecords
 //   nodes : with anyLinear in two sections - `A.nodes` with the top-level tree and the static trees, `A.nodesMB` with the motion-blur
 //           trees, child indices counted in 144-byte units from the start of the uploaded buffer, and `A.nodeImage` the two with the
-//           padding between them.
+//           padding between them.  With topLinear the top-level tree leads `A.nodesMB` instead of `A.nodes`, and the general layout
+//           of `blobs` is used whatever the scenes hold.
 // maxDepth (launch_on reserves 7 * (maxDepth + 1) + 2 stack entries) =
 //     the top-level depth
 //   + 1 for the exit marker
@@ -360,13 +521,18 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
 {
   Accel& A = s->instAccel;
   const DistinctScenes ds = distinct_scenes(c.placed);
-  const std::vector<uint32_t> order = build_top_level(s, c.placed, A);
+  std::vector<uint32_t> order;
+  std::vector<QNodeMB8> topMB; // topLinear: the top-level tree, references counted from its own first node
+  if (c.topLinear) topMB = build_top_level_linear(s, c.placed, A, order);
+  else order = build_top_level(s, c.placed, A);
+  const bool general = c.anyMeshMotion || c.topLinear;   // the layout of `blobs` with InstanceSceneRecords
+  const bool twoSections = c.anyLinear || c.topLinear;   // QNodeMB8s behind the QNode8s
 
   // what the distinct scenes bring (an accel that is absent or empty is not traceable and brings nothing)
   auto records = [](const Accel& O, size_t recordBytes) { return O.traceable() ? O.blobs.size() / recordBytes : 0; };
   Scene::InstanceCounts n;
   n.steps = count_steps(c.placed);
-  size_t staticNodes = A.nodes.size(), mbNodes = 0;
+  size_t staticNodes = A.nodes.size(), mbNodes = topMB.size();
   for (const Scene* o : ds.scenes) {
     n.quads += records(o->quadAccel, sizeof(QuadRecord));
     n.triMB += records(o->triMBAccel, sizeof(TriMBRecord));
@@ -382,7 +548,7 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
   Section quadSec = add_section(blobBytes, n.quads, sizeof(QuadRecord)); // quad leaves index `blobs` as one array of 64-byte records
   Section stepSec = add_section(blobBytes, n.steps, sizeof(InstanceStep));
   Section sceneSec{}, triMBSec{}, quadMBSec{};
-  if (c.anyMeshMotion) {
+  if (general) {
     sceneSec = add_section(blobBytes, ds.scenes.size(), sizeof(InstanceSceneRecord));
     triMBSec = add_section(blobBytes, n.triMB, sizeof(TriMBRecord));    // motion-blur triangle leaves index `blobs` as one array of 96-byte records
     quadMBSec = add_section(blobBytes, n.quadMB, sizeof(QuadMBRecord)); // motion-blur quad leaves as one of 128-byte records
@@ -393,6 +559,15 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
   const Section mbSec = add_section(nodeBytes, mbNodes, sizeof(QNodeMB8));
   A.blobStride = sizeof(InstanceRecord);
   A.blobs.assign(blobBytes, 0);
+  if (c.topLinear) { // the top-level tree leads the second section: its references move by where that section starts, in 144-byte units
+    if (mbSec.base() + topMB.size() >= (size_t)REF_LEAF)
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced nodes for the 31-bit node reference of the top-level tree (it follows all static nodes in one buffer, counted in 144-byte units)");
+    for (QNodeMB8& n : topMB)
+      for (uint32_t& ch : n.child)
+        if (ch != REF_EMPTY && !(ch & REF_LEAF)) ch += (uint32_t)mbSec.base();
+    A.root += (uint32_t)mbSec.base(); // an inner node always (build_top_level_linear)
+    A.nodesMB = std::move(topMB);
+  }
 
   uint32_t deepest = 0;
   auto append_static = [&](const Accel& O, size_t leafBase) { return append_tree(A.nodes, 0, O, O.nodes, leafBase, TOO_MANY_NODES, deepest); };
@@ -417,12 +592,12 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
     sc.quadMBRoot = append_mb(o->quadMBAccel, place_leaf_records(A.blobs, quadMBSec, o->quadMBAccel, "too many instanced motion blur quad segments for the 26-bit leaf reference (their records "
                                                                                                      "follow all other records in one array)"));
     quadRootOf.push_back(sc.quadRoot);
-    rootOf.push_back(c.anyMeshMotion ? (uint32_t)(sceneSec.base() + sceneSec.used) : sc.triRoot); // with anyMeshMotion: the scene's InstanceSceneRecord, in 64-byte units
-    if (c.anyMeshMotion) memcpy(A.blobs.data() + sceneSec.offset + sceneSec.used++ * sizeof(sc), &sc, sizeof(sc));
+    rootOf.push_back(general ? (uint32_t)(sceneSec.base() + sceneSec.used) : sc.triRoot); // general layout: the scene's InstanceSceneRecord, in 64-byte units
+    if (general) memcpy(A.blobs.data() + sceneSec.offset + sceneSec.used++ * sizeof(sc), &sc, sizeof(sc));
   }
-  write_instance_records(c.placed, ds, order, rootOf, !c.anyMeshMotion && c.anyQuads ? &quadRootOf : nullptr, stepSec.base(),
+  write_instance_records(c.placed, ds, order, rootOf, !general && c.anyQuads ? &quadRootOf : nullptr, stepSec.base(),
                          "too many instances, instanced quads and instance time steps for the 24-bit step offset of an instance record", A.blobs);
-  if (c.anyLinear) {
+  if (twoSections) {
     A.nodeImage.assign(nodeBytes, 0);
     if (!A.nodes.empty()) memcpy(A.nodeImage.data(), A.nodes.data(), A.nodes.size() * sizeof(QNode8));
     if (!A.nodesMB.empty()) memcpy(A.nodeImage.data() + mbSec.offset, A.nodesMB.data(), A.nodesMB.size() * sizeof(QNodeMB8));
@@ -430,7 +605,7 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
   }
   A.kind = instance_kind(c);
   A.robust = c.pluecker ? 1 : 0;
-  A.maxDepth += 1u + (c.anyMeshMotion ? c.pendingMax : c.anyQuads ? 1u : 0u) + deepest;
+  A.maxDepth += 1u + (general ? c.pendingMax : c.anyQuads ? 1u : 0u) + deepest;
   return n;
 }
 

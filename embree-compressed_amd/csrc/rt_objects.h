@@ -32,6 +32,7 @@ struct Device : RefCounted
   std::string quad_accel_mb = "default"; // quad meshes with more than one time step
   std::string mb_bounds = "swept"; // node boxes of the motion-blur mesh accels: "swept" (one box over the whole shutter, QNode8) or "linear" (time-dependent, QNodeMB8)
   std::string inst_mb_bounds = "swept"; // node boxes of motion-blur trees below an instance: "swept" (scenes built under mb_bounds=linear are refused below an instance) or "linear" (such scenes keep their QNodeMB8s, kinds ACCEL_INSTMESHMB_LINEAR_*)
+  std::string inst_bounds = "swept"; // top-level boxes of moving instances: "swept" (the union over the instance's time steps, QNode8) or "linear" (time-dependent, a top-level tree of QNodeMB8s, kinds ACCEL_INSTTOP_LINEAR_*)
   bool inst_filters = false; // "inst_filters=1": filter functions run on hits below mesh instances (geometry filters inside instanced mesh scenes, RTCIntersectContext::filter on scenes with mesh instances); 0, the default: both are refused as before
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel, rt_instance_build.cpp, raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
@@ -195,6 +196,7 @@ struct Device : RefCounted
   // (profiles/r04_wg_pool_ab.txt): 1 M rays 13.08 -> 13.65 Grays/s, 128 k 3.45 -> 3.77, 64 k 2.02 -> 2.83, 16 k 0.83 -> 0.89, but 4 k 215 -> 173 Mrays/s:
   // 32 workgroups whose four waves wait for one grab instead of grabbing side by side.
   uint32_t tuneWgPool = 2;
+  uint32_t tuneInstSpillMax = 0xFFFFFFFFu; // env RTAMD_INST_SPILL_MAX (tests): upper bound of the overflow entries per lane of a two-level launch (rt_trace.cpp launch_on)
   uint32_t tuneWgPoolMinRays = 16384;
   bool tuneChunkFixed = false; // RTAMD_CHUNK given: every batch uses exactly that chunk (otherwise small batches are cut finer, rt_trace.cpp ray_chunk_for)
   // traversal skeleton: 0 lane-per-ray (trace_loop.hip.h), 1 ray pool (trace_pool.hip.h), 2 by batch size: the pool kernel's
@@ -223,6 +225,9 @@ struct Device : RefCounted
   // Instances with more than one time step, the same rule: a host-only device whose config does not name inst_accel= refuses them at
   // commit, as before the instance accel took them.
   bool inst_motion_enabled() const { return gpu >= 0 || instAccelNamed; }
+  // Time-dependent top-level boxes (inst_bounds=linear) concern moving instances only: a host-only device honours the key where it takes
+  // such instances at all.
+  bool inst_top_linear_enabled() const { return inst_bounds == "linear" && inst_motion_enabled(); }
   // Triangle and quad meshes with time steps inside an instanced scene: a host-only device takes them only when its config names
   // inst_accel= and at least one of tri_accel_mb= / quad_accel_mb=; under any other config it refuses them as before.
   bool inst_mesh_motion_enabled() const { return gpu >= 0 || (instAccelNamed && (triAccelMBNamed || quadAccelMBNamed)); }
@@ -334,8 +339,8 @@ struct Accel
 {
   std::vector<QNode8> nodes;
   std::vector<QNodeMB8> nodesMB; // the kinds ACCEL_*MB_LINEAR_* (mb_bounds=linear): their time-dependent nodes, `nodes` is empty then;
-                                 // the kinds ACCEL_INSTMESHMB_LINEAR_*: the second section of the node array, behind `nodes`
-  std::vector<uint8_t> nodeImage; // the kinds ACCEL_INSTMESHMB_LINEAR_*: `nodes` | zero padding to a multiple of 144 bytes | `nodesMB`, as uploaded
+                                 // the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_*: the second section of the node array, behind `nodes`
+  std::vector<uint8_t> nodeImage; // the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_*: `nodes` | zero padding to a multiple of 144 bytes | `nodesMB`, as uploaded
   std::vector<TriRecord> prims;
   std::vector<uint8_t> blobs;
   std::vector<uint32_t> blobOffsets;
@@ -358,14 +363,14 @@ struct Accel
   std::vector<int> devOrdinals; // ordinal each copy lives on (for freeDevice)
   AccelDesc desc(size_t shard = 0) const;
   // the node array whichever of the two it is: what is counted and - see nodeImage*() - uploaded and handed out for inspection.  The kinds
-  // ACCEL_INSTMESHMB_LINEAR_* hold both: these three describe their QNode8 section (top-level tree and static trees), the QNodeMB8 section
-  // is described by the accel's two blobOffsets words
+  // ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* hold both: these three describe their QNode8 section (static trees, and in the
+  // kinds 30 / 31 the top-level tree), the QNodeMB8 section is described by the accel's two blobOffsets words
   size_t nodeCount() const { return is_mb_linear_kind(kind) ? nodesMB.size() : nodes.size(); }
   size_t nodeStride() const { return is_mb_linear_kind(kind) ? sizeof(QNodeMB8) : sizeof(QNode8); }
   const void* nodeData() const { return is_mb_linear_kind(kind) ? (const void*)nodesMB.data() : (const void*)nodes.data(); }
   // the bytes of the device's node buffer
-  size_t nodeImageBytes() const { return is_inst_linear_kind(kind) ? nodeImage.size() : nodeCount() * nodeStride(); }
-  const void* nodeImageData() const { return is_inst_linear_kind(kind) ? (const void*)nodeImage.data() : nodeData(); }
+  size_t nodeImageBytes() const { return is_inst_two_section_kind(kind) ? nodeImage.size() : nodeCount() * nodeStride(); }
+  const void* nodeImageData() const { return is_inst_two_section_kind(kind) ? (const void*)nodeImage.data() : nodeData(); }
   bool traceable() const { return kind != ACCEL_NONE && root != REF_EMPTY; } // a launch on anything else returns before it touches the GPU
   size_t deviceBytes() const;
   void upload(Device* dev);

@@ -709,13 +709,13 @@ void Scene::commit()
   {
     // the record counts of the layout (build_instance_accel).  Below the kinds ACCEL_INSTMESHMB_* "instanced quads" has always counted
     // every 64-byte record behind the instance records: quads and InstanceSteps
-    const bool general = instAccel.kind == ACCEL_INSTMESHMB_PLUECKER || instAccel.kind == ACCEL_INSTMESHMB_MOELLER || is_inst_linear_kind(instAccel.kind);
+    const bool general = is_inst_general_kind(instAccel.kind);
     const size_t nQuads = instCounts.quads + (general ? 0 : instCounts.steps), nTriMB = instCounts.triMB, nQuadMB = instCounts.quadMB;
     fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, %zu instanced quads, %zu instanced motion blur triangle "
                     "segment records, %zu instanced motion blur quad segment records, depth %u\n", instAccel.kind,
             instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),
             nQuads, nTriMB, nQuadMB, instAccel.maxDepth);
-    if (is_inst_linear_kind(instAccel.kind))
+    if (is_inst_two_section_kind(instAccel.kind))
       fprintf(stderr, "embree3-amd: instance accel kind %u: %zu time-dependent nodes (%zu B) from node index %u in 144-byte units, node buffer %zu B\n", instAccel.kind,
               instAccel.nodesMB.size(), instAccel.nodesMB.size() * sizeof(QNodeMB8), instAccel.blobOffsets[1], instAccel.nodeImage.size());
   }

@@ -82,6 +82,9 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
     spillBytes = (size_t)p.gridBlocks * (TRACE_POOL_BLOCK / 64) * TRACE_POOL_SLOTS * (size_t)p.spillDepth * 8u + 16u;
   } else {
     p.spillDepth = worst > (uint32_t)TRACE_LDS_STACK ? worst - TRACE_LDS_STACK : 0u;
+    // development aid (env RTAMD_INST_SPILL_MAX, two-level kernels only): fewer overflow entries than the depth asks for, to exercise the
+    // documented failure - a push beyond the area is dropped behind its bounds check, the kernel raises `overflow`, the call RTC_ERROR_UNKNOWN
+    if (instKernel) p.spillDepth = std::min(p.spillDepth, dev->tuneInstSpillMax);
     spillBytes = (size_t)p.gridBlocks * TRACE_BLOCK * (size_t)p.spillDepth * 8u + 16u;
   }
   p.counters = x.counters;

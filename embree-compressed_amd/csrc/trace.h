@@ -137,7 +137,8 @@ hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  //
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb.hip
 hipError_t launch_trace_instance_subdiv(const LaunchParams& p, hipStream_t stream);  // trace_instance_subdiv.hip
 hipError_t launch_trace_instance_mesh_mb_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb_linear.hip
-// the three launchers above hand a launch with exclOffsets != nullptr (a filter re-trace below an instance, closest hit only) to this one
+hipError_t launch_trace_instance_top_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_top_linear.hip (closest hit, any hit and its own EXCL form)
+// the mesh-instance launchers of the kinds 14..23, 30, 31 hand a launch with exclOffsets != nullptr (a filter re-trace below an instance, closest hit only) to this one
 hipError_t launch_trace_instance_filter(const LaunchParams& p, hipStream_t stream); // trace_instance_filter.hip
 // Development builds (-DTRACE_DEV_METRIC_ONLY, tools/README.md): of the subdivision accels only the metric's kind is dispatched (the
 // others fail with hipErrorInvalidValue, so that only trace_cbvh_leaf.hip has to be rebuilt), and launch_service serves no other kind.
@@ -187,6 +188,8 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_INSTSUBDIV_CBVH_LEAF: return launch_trace_instance_subdiv(p, stream);
   case ACCEL_INSTMESHMB_LINEAR_PLUECKER:
   case ACCEL_INSTMESHMB_LINEAR_MOELLER: return launch_trace_instance_mesh_mb_linear(p, stream);
+  case ACCEL_INSTTOP_LINEAR_PLUECKER:
+  case ACCEL_INSTTOP_LINEAR_MOELLER: return launch_trace_instance_top_linear(p, stream);
   case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
 #ifdef TRACE_DEV_METRIC_ONLY
   case ACCEL_GRIDSOA:

@@ -1,5 +1,6 @@
 // The two-level traversal kernel of trace_instance.hip (where it is described) as a template, shared with
-// trace_instance_mesh_mb.hip, which instantiates its MESHMB form, and trace_instance_mesh_mb_linear.hip (the NODEMB form).
+// trace_instance_mesh_mb.hip, which instantiates its MESHMB form, trace_instance_mesh_mb_linear.hip (the NODEMB form) and
+// trace_instance_top_linear.hip (the TOPMB form).
 #pragma once
 #include <type_traits>
 #include "trace_leaf.hip.h"
@@ -77,8 +78,8 @@ __device__ __forceinline__ bool instance_candidate_excluded(const LaunchParams& 
 template <bool PLUECKER, bool OCCLUDED, bool VEC, bool QUADS, bool XFMB>
 __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUADS, XFMB)) void trace_instance_kernel(LaunchParams P)
 {
-  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, EXCL (it asserts them)
-  constexpr bool MESHMB = false, NODEMB = false; // the MESHMB form is trace_instance_mesh_mb.hip's kernel, the NODEMB form trace_instance_mesh_mb_linear.hip's
+  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB, EXCL (it asserts them)
+  constexpr bool MESHMB = false, NODEMB = false, TOPMB = false; // the MESHMB form is trace_instance_mesh_mb.hip's kernel, the NODEMB form trace_instance_mesh_mb_linear.hip's
   constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
 #include "trace_instance_body.hip.h"
 }

@@ -1,10 +1,10 @@
 // The body of the two-level traversal kernel (trace_instance.hip, where it is described; trace_instance_mesh_mb.hip;
-// trace_instance_mesh_mb_linear.hip), as text: it is
+// trace_instance_mesh_mb_linear.hip; trace_instance_top_linear.hip), as text: it is
 // included inside the braces of a __global__ function that has the launch parameters `P` and the compile-time constants PLUECKER,
-// OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB and EXCL in scope.  Text and not a function called from the kernels: through a function the compiler
+// OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB and EXCL in scope.  Text and not a function called from the kernels: through a function the compiler
 // schedules the loads of the launch parameters differently, and the instruction streams of the instantiations of trace_instance.hip
 // are held to what they were (tools/kernel_metadata.py --digest, docs/experiments.md).  No include guard: one inclusion per kernel.
-// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and eight `bool`
+// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and nine `bool`
 // constants.  Everything else the text uses comes from the headers trace_instance.hip.h includes and from the TRACE_INST_* macros it
 // defines; the text declares only locals of its own and ends with the traversal loop.
 // trace_instance_subdiv.hip restates the refill, node step, ranking, instance entry and pop of this text for subdivision leaves: a fix to
@@ -12,8 +12,9 @@
   static_assert(std::is_same<decltype(P), LaunchParams>::value, "trace_instance_body.hip.h: `LaunchParams P` must be the kernel's parameter");
 #define TRACE_INSTANCE_BODY_BOOL(x) std::is_same<typename std::remove_const<decltype(x)>::type, bool>::value
   static_assert(TRACE_INSTANCE_BODY_BOOL(PLUECKER) && TRACE_INSTANCE_BODY_BOOL(OCCLUDED) && TRACE_INSTANCE_BODY_BOOL(VEC) && TRACE_INSTANCE_BODY_BOOL(QUADS) &&
-                    TRACE_INSTANCE_BODY_BOOL(XFMB) && TRACE_INSTANCE_BODY_BOOL(MESHMB) && TRACE_INSTANCE_BODY_BOOL(NODEMB) && TRACE_INSTANCE_BODY_BOOL(EXCL),
-                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB and EXCL must be bool constants in scope");
+                    TRACE_INSTANCE_BODY_BOOL(XFMB) && TRACE_INSTANCE_BODY_BOOL(MESHMB) && TRACE_INSTANCE_BODY_BOOL(NODEMB) && TRACE_INSTANCE_BODY_BOOL(TOPMB) &&
+                    TRACE_INSTANCE_BODY_BOOL(EXCL),
+                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB and EXCL must be bool constants in scope");
 #undef TRACE_INSTANCE_BODY_BOOL
   constexpr uint32_t FETCH = TRACE_INST_FETCH;
   constexpr uint32_t QFETCH = TRACE_INST_QUAD_FETCH;
@@ -21,6 +22,7 @@
   constexpr uint32_t QMFETCH = TRACE_INST_QUADMB_FETCH;
   static_assert(!MESHMB || (QUADS && XFMB), "the MESHMB form carries the general layout: quads and instance steps");
   static_assert(!NODEMB || MESHMB, "the NODEMB form is the MESHMB form over time-dependent nodes in the motion-blur trees");
+  static_assert(!TOPMB || NODEMB, "the TOPMB form is the NODEMB form over a top-level tree of time-dependent nodes");
   // EXCL (trace_instance_filter.hip, the re-traces of the host filter loop): in every leaf loop a candidate that passed its test is dropped
   // before the block's minimum selection when the ray's exclusion list names it - (curInst, geomID, primID, bits of t), instance_candidate_excluded
   // in trace_instance.hip.h.  P.exclOffsets is set for every launch of such a kernel and indexed by the ray's index in the batch.
@@ -133,8 +135,10 @@
     // ---- inner node step: the lane-per-ray step of trace_loop.hip.h, on either level ---------------------------------
     if (!(st & ST_POP) && (st & ST_ACTIVE) && !(cur & REF_LEAF)) {
       // NODEMB: the lane's tree says which node type `cur` names - a QNodeMB8 of the buffer indexed in 144-byte units while the lane is in
-      // a motion-blur tree of an instanced scene, a QNode8 everywhere else (top level, static trees)
-      const bool mbNode = NODEMB && (st & ST_TREE_MB) != 0u;
+      // a motion-blur tree of an instanced scene, a QNode8 everywhere else (top level, static trees).  TOPMB (kinds ACCEL_INSTTOP_LINEAR_*):
+      // the top-level tree is made of QNodeMB8s too - a lane outside an instance reads one, and enters a moving instance only where its
+      // box is at the ray's time
+      const bool mbNode = NODEMB && ((st & ST_TREE_MB) != 0u || (TOPMB && !(st & ST_INSIDE)));
       const uint4* np = mbNode ? (const uint4*)((const QNodeMB8*)nodes + cur) : (const uint4*)(nodes + cur);
       const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3], n4 = np[4], n5 = np[5];
       const float ox = __uint_as_float(n0.x), oy = __uint_as_float(n0.y), oz = __uint_as_float(n0.z);

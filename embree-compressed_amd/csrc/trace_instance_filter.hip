@@ -2,7 +2,7 @@
 // re-traces of the host filter loop (rt_filter.cpp).  The loop traces closest candidates, the host runs the callbacks, a rejected
 // candidate goes on its ray's exclusion list and the ray is traced again: a launch on the mesh instance accel that carries such a list
 // (LaunchParams::exclOffsets != nullptr; trace.h describes the entries) is handed over by launch_trace_instance, launch_trace_instance_mesh_mb
-// and launch_trace_instance_mesh_mb_linear to this unit.  Its kernels are the text of trace_instance_body.hip.h with EXCL = true: in the
+// and launch_trace_instance_mesh_mb_linear to this unit (the kinds 32 / 33 keep theirs beside their kernel, trace_instance_top_linear.hip).  Its kernels are the text of trace_instance_body.hip.h with EXCL = true: in the
 // triangle, quad, motion-blur triangle and motion-blur quad leaf loops a candidate that passed its test is dropped BEFORE the block's
 // minimum selection when the list names (instance geomID, geomID, primID, bits of t) - so the block's next best candidate is found, and
 // everything else (traversal order, tfar at block entry, ties) is the unfiltered kernel's.  The loop always asks for the closest
@@ -34,6 +34,7 @@ template <bool PLUECKER, bool VEC, bool QUADS, bool XFMB, bool MESHMB, bool NODE
 __global__ __launch_bounds__(TRACE_BLOCK, inst_filter_min_waves(PLUECKER, QUADS, XFMB, MESHMB)) void trace_instance_filter_kernel(LaunchParams P)
 {
   constexpr bool OCCLUDED = false, EXCL = true;
+  constexpr bool TOPMB = false; // the EXCL form over a time-dependent top level is trace_instance_top_linear.hip's filter kernel
 #include "trace_instance_body.hip.h"
 }
 

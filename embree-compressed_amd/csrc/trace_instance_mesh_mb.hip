@@ -26,7 +26,7 @@ namespace dev {
 template <bool PLUECKER, bool OCCLUDED, bool VEC>
 __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, true, true, true)) void trace_instance_mesh_mb_kernel(LaunchParams P)
 {
-  constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = false; // always the general layout: quads and instance steps allowed
+  constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = false, TOPMB = false; // always the general layout: quads and instance steps allowed
   constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
 #include "trace_instance_body.hip.h"
 }

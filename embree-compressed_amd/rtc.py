@@ -52,6 +52,10 @@ ACCEL_QUADMB_LINEAR_MOELLER = 29
 # instance accels under inst_mb_bounds=linear whose motion-blur trees keep these time-dependent nodes (two-section node buffer)
 ACCEL_INSTMESHMB_LINEAR_PLUECKER = 30
 ACCEL_INSTMESHMB_LINEAR_MOELLER = 31
+# mesh instance accels under inst_bounds=linear with at least one moving instance: the top-level tree is made of time-dependent nodes
+# (second section of the node buffer), `blobs` is the general layout of the kinds 22 / 23
+ACCEL_INSTTOP_LINEAR_PLUECKER = 32
+ACCEL_INSTTOP_LINEAR_MOELLER = 33
 # Scene.accel_data(kind + ACCEL_DATA_INSTSUBDIV): the arrays of that second instance accel, whatever else the scene holds
 ACCEL_DATA_INSTSUBDIV = 16
 RTC_SCENE_FLAG_NONE = 0

@@ -69,7 +69,11 @@ struct RTCAMDSceneStats
                                without it a top scene over a scene of the kinds 26..29 is refused at commit); nodeCount / nodeBytes
                                describe their 96-byte nodes (top-level tree, static trees), the instanced scenes' 144-byte nodes follow
                                in the same buffer from a multiple of 144 bytes on: rtcamdGetAccelData(scene, 0) returns all of it,
-                               (scene, 3) two words - how many there are and the index of the first one in 144-byte units */
+                               (scene, 3) two words - how many there are and the index of the first one in 144-byte units,
+                               32 / 33 the mesh instance accel of a scene with at least one moving instance under the device config
+                               inst_bounds=linear (default swept): the top-level tree itself is made of 144-byte time-dependent nodes
+                               and leads the second section of that buffer, so a ray enters a moving instance only where it is at
+                               the ray's time; nodeCount / nodeBytes describe the 96-byte nodes of the instanced scenes' static trees */
   unsigned int branching;   /* 8 */
   size_t nodeCount;         /* quantized BVH8 nodes */
   size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29) */

@@ -267,6 +267,21 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // records come first), so no leaf reference equals REF_INST_EXIT, and stays below 2^26.  `root` of an InstanceRecord is the rebased root
 // of its scene's tree, pad[0] is zero, pad[1] as in the kinds ACCEL_INSTMB_* (firstStep counts the InstanceRecords in front).
 // blobOffsets holds two words for inspection: the number of leaf blobs and the index of the first one.
+//
+// Kinds ACCEL_INSTSUBDIV_TOP_LINEAR_GRID / _CBVH_LEAF (inst_subdiv_bounds=linear, at least one placed subdivision instance with more than
+// one time step): the kinds above with a top-level tree of time-dependent nodes, so that a ray enters a moving subdivision instance only
+// where the instance is at the ray's time.  `prims` and `blobs` are those of the kinds ACCEL_INSTSUBDIV_* byte for byte apart from the
+// `root` words of the InstanceRecords; the node array has two sections as in the kinds ACCEL_INSTTOP_LINEAR_*:
+//   nodes : scene 0's subdivision BVH8 | scene 1's | ...   (QNode8, child indices rebased, in order of first use) |
+//           zero padding up to a multiple of 144 bytes from the start of the buffer |
+//           top-level tree                                                                                     (QNodeMB8)
+// AccelDesc::root and the inner child references of the top-level tree index the buffer as ONE array of QNodeMB8 (below 2^31, or the
+// commit is refused); the instanced trees lead the buffer, so their rebased roots differ from those of the swept layout.  A top scene of a
+// single instance gets a root node of one child.  Which node type a reference names: everything found outside an instance names
+// QNodeMB8s, everything inside QNode8s.  The containment guarantee of the top-level boxes is that of the kinds ACCEL_INSTTOP_LINEAR_*
+// (instance_linear_bounds over the instanced scene's bounds).  blobOffsets holds FOUR words: the number of leaf blobs, the index of the
+// first one, the number of QNodeMB8s and the index of the first one in 144-byte units.  Accel::maxDepth = the top-level depth + 1 for the
+// exit marker + the deepest instanced tree; Scene::bounds is extended by the swept unions as in every instance kind.
 struct alignas(16) InstanceRecord
 {
   float world2local[12]; // vx.xyz, vy.xyz, vz.xyz, p.xyz
@@ -418,15 +433,21 @@ enum AccelKind : uint32_t
   // inst_bounds=linear: the mesh instance accel of a top scene with at least one moving instance.  The top-level tree is made of QNodeMB8s
   // in the second section of `nodes`; `blobs` and `prims` are the general layout of the kinds 22 / 23 / 30 / 31 (see InstanceRecord)
   ACCEL_INSTTOP_LINEAR_PLUECKER = 32,
-  ACCEL_INSTTOP_LINEAR_MOELLER = 33
+  ACCEL_INSTTOP_LINEAR_MOELLER = 33,
+  // inst_subdiv_bounds=linear: the subdivision instance accel (kinds 24 / 25) of a top scene with at least one moving subdivision instance.
+  // The top-level tree is made of QNodeMB8s in the second section of `nodes`, behind the instanced scenes' QNode8 trees (see InstanceRecord)
+  ACCEL_INSTSUBDIV_TOP_LINEAR_GRID = 34,
+  ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF = 35
 };
 inline bool is_inst_linear_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_LINEAR_PLUECKER || kind == ACCEL_INSTMESHMB_LINEAR_MOELLER; } // traced by trace_instance_mesh_mb_linear.hip
 inline bool is_inst_top_linear_kind(uint32_t kind) { return kind == ACCEL_INSTTOP_LINEAR_PLUECKER || kind == ACCEL_INSTTOP_LINEAR_MOELLER; } // traced by trace_instance_top_linear.hip
 // the instance kinds whose node buffer has two sections, QNode8s and QNodeMB8s (Accel::nodeImage)
-inline bool is_inst_two_section_kind(uint32_t kind) { return is_inst_linear_kind(kind) || is_inst_top_linear_kind(kind); }
+inline bool is_inst_subdiv_top_linear_kind(uint32_t kind) { return kind == ACCEL_INSTSUBDIV_TOP_LINEAR_GRID || kind == ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF; } // traced by trace_instance_subdiv_top_linear.hip
+inline bool is_inst_two_section_kind(uint32_t kind) { return is_inst_linear_kind(kind) || is_inst_top_linear_kind(kind) || is_inst_subdiv_top_linear_kind(kind); }
 // the instance kinds with the general layout of `blobs` (InstanceSceneRecords)
-inline bool is_inst_general_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_PLUECKER || kind == ACCEL_INSTMESHMB_MOELLER || is_inst_two_section_kind(kind); }
-// traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip / trace_instance_mesh_mb_linear.hip / trace_instance_top_linear.hip
+inline bool is_inst_general_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_PLUECKER || kind == ACCEL_INSTMESHMB_MOELLER || is_inst_linear_kind(kind) || is_inst_top_linear_kind(kind); }
+// traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip / trace_instance_mesh_mb_linear.hip / trace_instance_top_linear.hip /
+// trace_instance_subdiv_top_linear.hip
 inline bool is_instance_kind(uint32_t kind) { return (kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF) || is_inst_two_section_kind(kind); }
 
 inline bool is_mb_linear_kind(uint32_t kind) { return kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER; } // nodes are QNodeMB8
@@ -440,7 +461,7 @@ inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKE
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
 {
-  const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_*
+  const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_*
   const TriRecord* prims;
   const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16

@@ -53,6 +53,10 @@ void Device::parse(const std::string& cfg)
       if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "inst_bounds=: unknown value '" + val + "' (swept or linear)");
       inst_bounds = val;
     }
+    else if (key == "inst_subdiv_bounds") {
+      if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "inst_subdiv_bounds=: unknown value '" + val + "' (swept or linear)");
+      inst_subdiv_bounds = val;
+    }
     else if (key == "inst_filters") {
       if (val != "0" && val != "1") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "inst_filters=: unknown value '" + val + "' (0 or 1)");
       inst_filters = val == "1";

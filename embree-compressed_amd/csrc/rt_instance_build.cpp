@@ -1,11 +1,12 @@
 // The two instance accels of a scene, built at commit from the committed accels of the instanced scenes (layouts: accel.h InstanceRecord).
 // build_instance_accel places the instances of mesh scenes (kinds 14..23, 30..33), build_instance_subdiv_accel those of subdivision
-// scenes (kinds 24, 25).  Each is: classify (which instances take part, which arithmetic, every refusal that depends on what the scenes
+// scenes (kinds 24, 25, 34, 35).  Each is: classify (which instances take part, which arithmetic, every refusal that depends on what the scenes
 // hold), then lay out (where things go), and the layouts are put together from one set of stages:
 //   instance_world_box        the box of one instance in the top scene
 //   distinct_scenes           the instanced scenes in order of first use: each is stored once, however many instances share it
 //   build_top_level           the BVH8 over the instances' boxes, one instance per leaf
-//   build_top_level_linear    the same over time-dependent boxes (inst_bounds=linear; instance_time_boxes, instance_linear_bounds)
+//   build_top_level_linear    the same over time-dependent boxes (inst_bounds=linear, inst_subdiv_bounds=linear; instance_time_boxes,
+//                             instance_linear_bounds)
 //   Section, add_section      where the sections of a byte array start (`blobs`, and the node buffer of the kinds 30 / 31)
 //   place_leaf_records        one scene's leaf records into their section
 //   append_tree               one scene's tree behind the nodes placed so far, references rebased
@@ -620,6 +621,7 @@ struct SubdivInstances
   std::vector<PlacedInstance> placed; // in geomID order
   uint32_t leafKind = ACCEL_NONE;     // ACCEL_GRIDSOA or ACCEL_CBVH_LEAF, of every instanced scene
   uint32_t levels = 0;                // ACCEL_CBVH_LEAF: the compression level of every instanced scene
+  bool topLinear = false;             // inst_subdiv_bounds=linear and a placed instance has more than one time step: kinds ACCEL_INSTSUBDIV_TOP_LINEAR_*
 };
 
 SubdivInstances classify_subdiv_instances(const Scene* s)
@@ -666,6 +668,7 @@ SubdivInstances classify_subdiv_instances(const Scene* s)
     c.leafKind = O.kind;
     c.levels = C;
     c.placed.push_back({g, gid, o, instance_world_box(g, o)});
+    c.topLinear |= g->local2world.size() > 1 && s->device->inst_subdiv_top_linear_enabled();
   }
   return c;
 }
@@ -674,12 +677,19 @@ SubdivInstances classify_subdiv_instances(const Scene* s)
 // instanced scene; `blobs` holds the InstanceRecords, the InstanceSteps of moving instances, and - from a multiple of the blob stride
 // on - the leaf blobs of all instanced scenes, so that a rebased leaf reference indexes `blobs` the way the leaf functions of the
 // subdivision kernels do (GridCellLeaf::intersect, CbvhLeaf::intersect).
+// With topLinear (kinds ACCEL_INSTSUBDIV_TOP_LINEAR_*) the top-level tree is made of QNodeMB8s and moves to a second section of the node
+// buffer, behind the instanced trees and the padding to a multiple of 144 bytes: `A.nodes` holds the instanced trees from index 0 on,
+// `A.nodesMB` the top-level tree with references counted in 144-byte units from the start of the buffer, `A.nodeImage` both as uploaded.
+// `blobs` is the same apart from the `root` words of the records (the instanced trees lead the buffer).
 // maxDepth = the top-level depth + 1 for the exit marker + the deepest instanced tree.
 void layout_subdiv_instances(Scene* s, const SubdivInstances& c)
 {
   Accel& A = s->instSubdivAccel;
   const DistinctScenes ds = distinct_scenes(c.placed);
-  const std::vector<uint32_t> order = build_top_level(s, c.placed, A);
+  std::vector<uint32_t> order;
+  std::vector<QNodeMB8> topMB; // topLinear: the top-level tree, references counted from its own first node
+  if (c.topLinear) topMB = build_top_level_linear(s, c.placed, A, order);
+  else order = build_top_level(s, c.placed, A);
 
   const size_t stride = ds.scenes[0]->subdivAccel.blobStride;
   size_t numBlobs = 0;
@@ -708,6 +718,24 @@ void layout_subdiv_instances(Scene* s, const SubdivInstances& c)
   A.cbvhLevels = c.levels;
   A.maxDepth += 1u + deepest;
   A.blobOffsets = {(uint32_t)numBlobs, (uint32_t)blobSec.base()};
+  if (c.topLinear) { // the top-level tree follows all instanced trees: its references move by where its section starts, in 144-byte units
+    size_t nodeBytes = 0;
+    add_section(nodeBytes, A.nodes.size(), sizeof(QNode8));
+    const Section mbSec = add_section(nodeBytes, topMB.size(), sizeof(QNodeMB8));
+    if (mbSec.base() + topMB.size() >= (size_t)REF_LEAF)
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many instanced nodes for the 31-bit node reference of the top-level tree (it follows all instanced nodes in one buffer, counted in 144-byte units)");
+    for (QNodeMB8& n : topMB)
+      for (uint32_t& ch : n.child)
+        if (ch != REF_EMPTY && !(ch & REF_LEAF)) ch += (uint32_t)mbSec.base();
+    A.root += (uint32_t)mbSec.base(); // an inner node always (build_top_level_linear)
+    A.nodesMB = std::move(topMB);
+    A.nodeImage.assign(nodeBytes, 0);
+    if (!A.nodes.empty()) memcpy(A.nodeImage.data(), A.nodes.data(), A.nodes.size() * sizeof(QNode8));
+    memcpy(A.nodeImage.data() + mbSec.offset, A.nodesMB.data(), A.nodesMB.size() * sizeof(QNodeMB8));
+    A.kind = c.leafKind == ACCEL_GRIDSOA ? ACCEL_INSTSUBDIV_TOP_LINEAR_GRID : ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF;
+    A.blobOffsets.push_back((uint32_t)A.nodesMB.size());
+    A.blobOffsets.push_back((uint32_t)mbSec.base());
+  }
 }
 
 } // namespace
@@ -724,7 +752,7 @@ void build_instance_accel(Scene* s)
   if (!c.placed.empty()) s->instCounts = layout_mesh_instances(s, c);
 }
 
-// Instances of subdivision scenes: the second instance accel of a scene (accel.h InstanceRecord, kinds ACCEL_INSTSUBDIV_*).  Runs after
+// Instances of subdivision scenes: the second instance accel of a scene (accel.h InstanceRecord, kinds ACCEL_INSTSUBDIV_* and ACCEL_INSTSUBDIV_TOP_LINEAR_*).  Runs after
 // build_instance_accel, which has refused instances without a committed scene.
 void build_instance_subdiv_accel(Scene* s)
 {

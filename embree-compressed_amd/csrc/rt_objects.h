@@ -33,6 +33,7 @@ struct Device : RefCounted
   std::string mb_bounds = "swept"; // node boxes of the motion-blur mesh accels: "swept" (one box over the whole shutter, QNode8) or "linear" (time-dependent, QNodeMB8)
   std::string inst_mb_bounds = "swept"; // node boxes of motion-blur trees below an instance: "swept" (scenes built under mb_bounds=linear are refused below an instance) or "linear" (such scenes keep their QNodeMB8s, kinds ACCEL_INSTMESHMB_LINEAR_*)
   std::string inst_bounds = "swept"; // top-level boxes of moving instances: "swept" (the union over the instance's time steps, QNode8) or "linear" (time-dependent, a top-level tree of QNodeMB8s, kinds ACCEL_INSTTOP_LINEAR_*)
+  std::string inst_subdiv_bounds = "swept"; // top-level boxes of moving subdivision instances (Scene::instSubdivAccel): "swept" (QNode8, kinds 24 / 25) or "linear" (a top-level tree of QNodeMB8s, kinds ACCEL_INSTSUBDIV_TOP_LINEAR_*)
   bool inst_filters = false; // "inst_filters=1": filter functions run on hits below mesh instances (geometry filters inside instanced mesh scenes, RTCIntersectContext::filter on scenes with mesh instances); 0, the default: both are refused as before
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel, rt_instance_build.cpp, raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
@@ -234,6 +235,9 @@ struct Device : RefCounted
   // Instances of scenes that hold subdivision meshes: a host-only device takes them only when its config names inst_accel= and
   // subdiv_accel=; under any other config it refuses them as before.
   bool inst_subdiv_enabled() const { return gpu >= 0 || (instAccelNamed && subdivAccelNamed); }
+  // Time-dependent top-level boxes above moving subdivision instances (inst_subdiv_bounds=linear, independent of inst_bounds): a host-only
+  // device honours the key where it takes moving subdivision instances at all.
+  bool inst_subdiv_top_linear_enabled() const { return inst_subdiv_bounds == "linear" && inst_subdiv_enabled() && inst_motion_enabled(); }
   bool tuneBlocksAuto = true; // no RTAMD_BLOCKS_PER_CU given: 2 workgroups per CU, 1 when >= 2 batches run on other streams
   void memoryMonitor(ssize_t bytes, bool post);
 };
@@ -339,8 +343,8 @@ struct Accel
 {
   std::vector<QNode8> nodes;
   std::vector<QNodeMB8> nodesMB; // the kinds ACCEL_*MB_LINEAR_* (mb_bounds=linear): their time-dependent nodes, `nodes` is empty then;
-                                 // the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_*: the second section of the node array, behind `nodes`
-  std::vector<uint8_t> nodeImage; // the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_*: `nodes` | zero padding to a multiple of 144 bytes | `nodesMB`, as uploaded
+                                 // the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_*: the second section of the node array, behind `nodes`
+  std::vector<uint8_t> nodeImage; // the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_*: `nodes` | zero padding to a multiple of 144 bytes | `nodesMB`, as uploaded
   std::vector<TriRecord> prims;
   std::vector<uint8_t> blobs;
   std::vector<uint32_t> blobOffsets;
@@ -349,7 +353,7 @@ struct Accel
   uint32_t robust = 0;
   uint32_t maxDepth = 0;
   uint32_t blobStride = 0;
-  uint32_t cbvhLevels = 0; // ACCEL_INSTSUBDIV_CBVH_LEAF: the compression level C of the instanced scenes' blobs (0: the scene's own level applies)
+  uint32_t cbvhLevels = 0; // ACCEL_INSTSUBDIV_CBVH_LEAF / ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF: the compression level C of the instanced scenes' blobs (0: the scene's own level applies)
   size_t leafCount = 0;
   // device copies, one set per shard of the device (replicated accel)
   struct DevCopy
@@ -363,8 +367,9 @@ struct Accel
   std::vector<int> devOrdinals; // ordinal each copy lives on (for freeDevice)
   AccelDesc desc(size_t shard = 0) const;
   // the node array whichever of the two it is: what is counted and - see nodeImage*() - uploaded and handed out for inspection.  The kinds
-  // ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* hold both: these three describe their QNode8 section (static trees, and in the
-  // kinds 30 / 31 the top-level tree), the QNodeMB8 section is described by the accel's two blobOffsets words
+  // ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_* hold both: these three describe their QNode8 section
+  // (static trees, and in the kinds 30 / 31 the top-level tree), the QNodeMB8 section is described by the accel's two blobOffsets words
+  // (the kinds 34 / 35: its words 2 and 3)
   size_t nodeCount() const { return is_mb_linear_kind(kind) ? nodesMB.size() : nodes.size(); }
   size_t nodeStride() const { return is_mb_linear_kind(kind) ? sizeof(QNodeMB8) : sizeof(QNode8); }
   const void* nodeData() const { return is_mb_linear_kind(kind) ? (const void*)nodesMB.data() : (const void*)nodes.data(); }

@@ -723,6 +723,9 @@ void Scene::commit()
     fprintf(stderr, "embree3-amd: subdivision instance accel kind %u (C %u): %zu nodes (%zu B), %zu instances, %u instanced leaf blobs of %u B from blob index %u, depth %u\n",
             instSubdivAccel.kind, instSubdivAccel.cbvhLevels, instSubdivAccel.nodes.size(), instSubdivAccel.nodes.size() * sizeof(QNode8), instSubdivAccel.leafCount,
             instSubdivAccel.blobOffsets[0], instSubdivAccel.blobStride, instSubdivAccel.blobOffsets[1], instSubdivAccel.maxDepth);
+  if (is_inst_subdiv_top_linear_kind(instSubdivAccel.kind) && device->verbose >= 2)
+    fprintf(stderr, "embree3-amd: subdivision instance accel kind %u: %zu time-dependent nodes (%zu B) from node index %u in 144-byte units, node buffer %zu B\n", instSubdivAccel.kind,
+            instSubdivAccel.nodesMB.size(), instSubdivAccel.nodesMB.size() * sizeof(QNodeMB8), instSubdivAccel.blobOffsets[3], instSubdivAccel.nodeImage.size());
   modified = false;
 }
 

@@ -71,7 +71,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   if (is_mb_mesh_kind(A.kind))
     p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip), under swept and under linear bounds
   const bool instKernel = is_instance_kind(A.kind);
-  if (instKernel) p.poolKernel = 0u; // the two-level kernel is a lane-per-ray kernel of its own (trace_instance.hip, trace_instance_subdiv.hip): no pool form, no root cull pre-pass
+  if (instKernel) p.poolKernel = 0u; // the two-level kernel is a lane-per-ray kernel of its own (trace_instance.hip, trace_instance_subdiv.hip and their linear forms): no pool form, no root cull pre-pass
   // worst-case stack: 7 siblings per level plus the entry being expanded.  The overflow area is sized for it, so a push
   // can only be dropped if the tree is deeper than the builder reported; the kernels then raise `overflow` (below).
   const uint32_t worst = 7u * (A.maxDepth + 1u) + 2u;
@@ -88,7 +88,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
     spillBytes = (size_t)p.gridBlocks * TRACE_BLOCK * (size_t)p.spillDepth * 8u + 16u;
   }
   p.counters = x.counters;
-  p.cbvhLevels = A.cbvhLevels ? A.cbvhLevels : s->compressionLevel; // (instanced cBVH blobs carry the level of the scenes they come from)
+  p.cbvhLevels = A.cbvhLevels ? A.cbvhLevels : s->compressionLevel; // (instanced cBVH blobs, kinds 25 / 35, carry the level of the scenes they come from)
   // cBVH blob walk: quad form (four lanes per ray, two-stage visits) or one ray per lane.  Coherent batches (RTC_INTERSECT_CONTEXT_FLAG_COHERENT,
   // e.g. the primary rays of viewer_stream_device.cpp:305) keep most lanes at blobs at once; since the two-stage visits the quad form is the faster
   // one for them too when the batch has the chip (1920x1080 camera rays alone: 0.630 vs 0.768 ms), the lane form still wins with several batches

@@ -852,7 +852,7 @@ API void rtcamdGetSceneStats(RTCScene h, struct RTCAMDSceneStats* st)
   st->accelKind = A.kind;
   st->branching = 8;
   st->nodeCount = A.nodeCount();
-  st->nodeBytes = A.nodeStride(); // QNode8, or QNodeMB8 in the kinds 26..29 (the kinds 30 .. 33: their QNode8s; the QNodeMB8s behind them are counted in blobOffsets)
+  st->nodeBytes = A.nodeStride(); // QNode8, or QNodeMB8 in the kinds 26..29 (the kinds 30 .. 35: their QNode8s; the QNodeMB8s behind them are counted in blobOffsets)
   const bool tri = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER;
   st->primCount = tri ? A.prims.size() : (A.blobStride ? A.blobs.size() / A.blobStride : 0);
   st->primBytes = tri ? sizeof(TriRecord) : A.blobStride;
@@ -897,7 +897,7 @@ API const void* rtcamdGetAccelData(RTCScene h, unsigned int kind, size_t* byteSi
   const void* p = nullptr;
   size_t n = 0;
   switch (kind) {
-  case 0: p = A.nodeImageData(); n = A.nodeImageBytes(); break; // (the kinds 30 .. 33: both sections and the padding, as uploaded)
+  case 0: p = A.nodeImageData(); n = A.nodeImageBytes(); break; // (the kinds 30 .. 35: both sections and the padding, as uploaded)
   case 1: p = A.prims.data(); n = A.prims.size() * sizeof(TriRecord); break;
   case 2: p = A.blobs.data(); n = A.blobs.size(); break;
   case 3: p = A.blobOffsets.data(); n = A.blobOffsets.size() * 4; break;

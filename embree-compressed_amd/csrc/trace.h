@@ -18,7 +18,7 @@ struct LaunchParams
   void* spill;         // HBM overflow area of the per-lane LDS stacks
   uint32_t spillDepth; // entries per lane available in `spill`
   uint32_t gridBlocks; // persistent grid size the spill area was sized for
-  uint32_t cbvhLevels; // fork: depth C of every cBVH blob of the scene (rtcSetSceneLevels; ACCEL_INSTSUBDIV_CBVH_LEAF: of the instanced scenes)
+  uint32_t cbvhLevels; // fork: depth C of every cBVH blob of the scene (rtcSetSceneLevels; ACCEL_INSTSUBDIV_CBVH_LEAF / ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF: of the instanced scenes)
   uint32_t cbvhLaneForm; // fork, lane kernel: 1 = walk blobs one ray per lane (coherent batches), 0 = quad form (trace_cbvh.hip.h)
   WaveRecord* counters;    // non-null selects the instrumented kernel twin; one record per wavefront
   uint32_t numCUs;         // compute units of the device (persistent grid sizing)
@@ -138,6 +138,7 @@ hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stre
 hipError_t launch_trace_instance_subdiv(const LaunchParams& p, hipStream_t stream);  // trace_instance_subdiv.hip
 hipError_t launch_trace_instance_mesh_mb_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb_linear.hip
 hipError_t launch_trace_instance_top_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_top_linear.hip (closest hit, any hit and its own EXCL form)
+hipError_t launch_trace_instance_subdiv_top_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_subdiv_top_linear.hip (no EXCL form: filters stay refused)
 // the mesh-instance launchers of the kinds 14..23, 30, 31 hand a launch with exclOffsets != nullptr (a filter re-trace below an instance, closest hit only) to this one
 hipError_t launch_trace_instance_filter(const LaunchParams& p, hipStream_t stream); // trace_instance_filter.hip
 // Development builds (-DTRACE_DEV_METRIC_ONLY, tools/README.md): of the subdivision accels only the metric's kind is dispatched (the
@@ -190,6 +191,8 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_INSTMESHMB_LINEAR_MOELLER: return launch_trace_instance_mesh_mb_linear(p, stream);
   case ACCEL_INSTTOP_LINEAR_PLUECKER:
   case ACCEL_INSTTOP_LINEAR_MOELLER: return launch_trace_instance_top_linear(p, stream);
+  case ACCEL_INSTSUBDIV_TOP_LINEAR_GRID:
+  case ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF: return launch_trace_instance_subdiv_top_linear(p, stream);
   case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
 #ifdef TRACE_DEV_METRIC_ONLY
   case ACCEL_GRIDSOA:

@@ -56,6 +56,10 @@ ACCEL_INSTMESHMB_LINEAR_MOELLER = 31
 # (second section of the node buffer), `blobs` is the general layout of the kinds 22 / 23
 ACCEL_INSTTOP_LINEAR_PLUECKER = 32
 ACCEL_INSTTOP_LINEAR_MOELLER = 33
+# subdivision instance accels (24 / 25) under inst_subdiv_bounds=linear with at least one moving subdivision instance: the instanced
+# scenes' BVH8s lead the node buffer, the top-level tree of time-dependent nodes is its second section; blobOffsets has four words
+ACCEL_INSTSUBDIV_TOP_LINEAR_GRID = 34
+ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF = 35
 # Scene.accel_data(kind + ACCEL_DATA_INSTSUBDIV): the arrays of that second instance accel, whatever else the scene holds
 ACCEL_DATA_INSTSUBDIV = 16
 RTC_SCENE_FLAG_NONE = 0

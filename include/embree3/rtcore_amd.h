@@ -73,7 +73,12 @@ struct RTCAMDSceneStats
                                32 / 33 the mesh instance accel of a scene with at least one moving instance under the device config
                                inst_bounds=linear (default swept): the top-level tree itself is made of 144-byte time-dependent nodes
                                and leads the second section of that buffer, so a ray enters a moving instance only where it is at
-                               the ray's time; nodeCount / nodeBytes describe the 96-byte nodes of the instanced scenes' static trees */
+                               the ray's time; nodeCount / nodeBytes describe the 96-byte nodes of the instanced scenes' static trees,
+                               34 / 35 the subdivision instance accels 24 / 25 of a scene with at least one moving subdivision instance
+                               under the device config inst_subdiv_bounds=linear (default swept; independent of inst_bounds): the
+                               instanced scenes' 96-byte nodes lead the buffer (nodeCount / nodeBytes), the top-level tree of 144-byte
+                               time-dependent nodes follows from a multiple of 144 bytes on; rtcamdGetAccelData(scene, 3) returns four
+                               words - leaf blobs, index of the first blob, 144-byte nodes, index of the first one in 144-byte units */
   unsigned int branching;   /* 8 */
   size_t nodeCount;         /* quantized BVH8 nodes */
   size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29) */

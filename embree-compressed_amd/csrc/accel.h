@@ -8,6 +8,7 @@
 //                            or QuadRecord[] (64-byte quad records, leaf-contiguous) for quad geometry,
 //                            or TriMBRecord[] (96-byte motion-blur triangle records, leaf-contiguous) for triangle meshes with time steps,
 //                            or QuadMBRecord[] (128-byte motion-blur quad records, leaf-contiguous) for quad meshes with time steps,
+//                            or LineRecord[] (48-byte line segment records, leaf-contiguous) for flat linear curves,
 //                            or InstanceRecord[] (64-byte instance records, one per top-level leaf) for instances, followed in
 //                            the kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER by the instanced scenes' QuadRecord[], in the kinds
 //                            ACCEL_INSTMESHMB_* also by InstanceSceneRecord[], TriMBRecord[] and QuadMBRecord[] (see InstanceRecord)
@@ -29,6 +30,7 @@ namespace rtamd {
 // quad leaf   : the same form, counting quads
 // MB tri leaf : the same form, counting TriMBRecords (one per triangle and time segment)
 // MB quad leaf: the same form, counting QuadMBRecords (one per quad and time segment)
+// line leaf   : the same form, counting LineRecords
 // subdiv leaf : bits 0..30 = blob index (one blob per leaf, like encodeTypedLeaf(ptr,1) bvh_builder_subdiv.cpp:728)
 static const uint32_t REF_EMPTY = 0xFFFFFFFFu; // no child (reference: BVH::emptyNode, bvh.h:117-132)
 static const uint32_t REF_LEAF = 0x80000000u;
@@ -123,6 +125,21 @@ struct alignas(16) QuadRecord
   uint32_t pad1;
 };
 static_assert(sizeof(QuadRecord) == 64, "QuadRecord must be 64 bytes");
+
+// ---- line segment record, 48 bytes = 3 x dwordx4 -----------------------------------------------------------------------
+// One segment of a flat linear curve (RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE): its two end points with their radii, gathered at commit
+// (the reference keeps the index of the first vertex and gathers per visit, LineMi<4> / Line4i, kernels/geometry/linei.h; here the
+// record stands in for it as QuadRecord does for Quad4i).  One record serves the robust and the fast accel: the reference has a single
+// line intersector (LineIntersector1, line_intersector.h).  Every group of 4 records from the leaf start is one block of the
+// reference's 4-wide form: all 4 tested against the tfar at block entry, lowest lane wins ties.
+struct alignas(16) LineRecord
+{
+  float v0x, v0y, v0z, r0;
+  float v1x, v1y, v1z, r1;
+  uint32_t geomID, primID;
+  uint32_t pad[2];
+};
+static_assert(sizeof(LineRecord) == 48, "LineRecord must be 48 bytes");
 
 // ---- motion-blur triangle record, 96 bytes = 6 x dwordx4 -------------------------------------------------------------
 // The three vertices of a triangle at both ends of ONE time segment of its mesh (a0..c0 at step `segment`, a1..c1 at step `segment` + 1).
@@ -437,8 +454,13 @@ enum AccelKind : uint32_t
   // inst_subdiv_bounds=linear: the subdivision instance accel (kinds 24 / 25) of a top scene with at least one moving subdivision instance.
   // The top-level tree is made of QNodeMB8s in the second section of `nodes`, behind the instanced scenes' QNode8 trees (see InstanceRecord)
   ACCEL_INSTSUBDIV_TOP_LINEAR_GRID = 34,
-  ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF = 35
+  ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF = 35,
+  // flat linear curves (Scene::lineAccel, line_accel=default / bvh8.line4i / bvh4.line4i): LineRecord[] in `blobs`, one leaf arithmetic;
+  // robust traversal for RTC_SCENE_FLAG_ROBUST scenes, fast traversal otherwise.  Neither instance nor motion-blur kinds.
+  ACCEL_LINE_ROBUST = 36,
+  ACCEL_LINE_FAST = 37
 };
+inline bool is_line_kind(uint32_t kind) { return kind == ACCEL_LINE_ROBUST || kind == ACCEL_LINE_FAST; } // traced by trace_line.hip: lane and pool kernels, no service kernel
 inline bool is_inst_linear_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_LINEAR_PLUECKER || kind == ACCEL_INSTMESHMB_LINEAR_MOELLER; } // traced by trace_instance_mesh_mb_linear.hip
 inline bool is_inst_top_linear_kind(uint32_t kind) { return kind == ACCEL_INSTTOP_LINEAR_PLUECKER || kind == ACCEL_INSTTOP_LINEAR_MOELLER; } // traced by trace_instance_top_linear.hip
 // the instance kinds whose node buffer has two sections, QNode8s and QNodeMB8s (Accel::nodeImage)
@@ -463,7 +485,7 @@ struct AccelDesc
 {
   const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_*
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the LineRecord[] of a line accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind
@@ -482,7 +504,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (up to six launches per batch: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, instances)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel of a scene: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, lines, instances, subdivision instances)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

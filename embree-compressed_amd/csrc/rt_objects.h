@@ -35,6 +35,7 @@ struct Device : RefCounted
   std::string inst_bounds = "swept"; // top-level boxes of moving instances: "swept" (the union over the instance's time steps, QNode8) or "linear" (time-dependent, a top-level tree of QNodeMB8s, kinds ACCEL_INSTTOP_LINEAR_*)
   std::string inst_subdiv_bounds = "swept"; // top-level boxes of moving subdivision instances (Scene::instSubdivAccel): "swept" (QNode8, kinds 24 / 25) or "linear" (a top-level tree of QNodeMB8s, kinds ACCEL_INSTSUBDIV_TOP_LINEAR_*)
   bool inst_filters = false; // "inst_filters=1": filter functions run on hits below mesh instances (geometry filters inside instanced mesh scenes, RTCIntersectContext::filter on scenes with mesh instances); 0, the default: both are refused as before
+  std::string line_accel = "default"; // flat linear curves: default / bvh8.line4i / bvh4.line4i, all the one BVH8 over LineRecords (build_line_accel raises for any other at commit)
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel, rt_instance_build.cpp, raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
@@ -333,6 +334,11 @@ struct Geometry : RefCounted
   size_t numQuads() const { return numTriangles(); } // index buffer records (UINT4 for quads)
   void quad(size_t i, unsigned idx[4]) const;
   bool validQuad(size_t i, unsigned slot = 0) const;
+  // flat linear curve accessors (reference: LineSegments, kernels/common/scene_line_segments.h): segment i runs from vertex
+  // index[i] to vertex index[i] + 1; vertices are (x, y, z, radius)
+  size_t numSegments() const { return numTriangles(); } // index buffer records (UINT)
+  unsigned segment(size_t i) const;
+  bool validSegment(size_t i) const;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -397,6 +403,7 @@ struct Scene : RefCounted
   // filter callbacks present at commit time (Scene::hasGeometryFilterFunction, scene.h): they route a batch through the
   // host filter loop of rt_filter.cpp (the tri* flags cover quad meshes too)
   bool triIntersectFilter = false, triOccludedFilter = false, subdivFilter = false;
+  bool lineIntersectFilter = false, lineOccludedFilter = false; // the same for flat linear curves (reported with the meshes' flags)
   // the same for what lies below this scene's mesh instances (inst_filters=1; build_instance_accel, at this scene's commit): an enabled
   // geometry with an intersect / occluded filter in the scene of a placed instance
   bool instIntersectFilter = false, instOccludedFilter = false;
@@ -410,11 +417,12 @@ struct Scene : RefCounted
   Accel quadAccel;   // quads with one time step (QuadRecord[] in `blobs`); traced after the triangles, before the motion-blur quads
   Accel quadMBAccel; // quads with several time steps (QuadMBRecord[] in `blobs`); traced after the static quads, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
+  Accel lineAccel;   // flat linear curves (LineRecord[] in `blobs`); traced after the subdivision patches, before the instances (scene.cpp:650-663)
   Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle and quad trees behind the top-level tree); traced last (scene.cpp:661-665)
   Accel instSubdivAccel; // instances of scenes that hold subdivision meshes only (InstanceRecord[] and the instanced scenes' leaf blobs in `blobs`, their BVH8s behind the top-level tree); traced after the mesh instances
-  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / INST / INSTSUBDIV index whatever a path keeps per accel
-  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, INST = 5, INSTSUBDIV = 6, NUM_ACCELS = 7 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &instAccel, &instSubdivAccel}; }
+  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / LINE / INST / INSTSUBDIV index whatever a path keeps per accel
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, LINE = 5, INST = 6, INSTSUBDIV = 7, NUM_ACCELS = 8 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &lineAccel, &instAccel, &instSubdivAccel}; }
   bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
   // records the layout of instAccel placed in `blobs` behind the InstanceRecords, as build_instance_accel counted them (host only: the
   // verbose line of commit prints them)

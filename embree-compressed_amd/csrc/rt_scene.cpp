@@ -58,7 +58,8 @@ void Geometry::bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size
 {
   // argument checks follow rtcSetGeometryBuffer (rtcore.cpp:1236-1290) and TriangleMesh::setBuffer
   // (scene_triangle_mesh.cpp): 4-byte aligned offset/stride, matching formats per slot type.
-  if ((off & 3) || (stride & 3)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "buffer offset and stride must be 4-byte aligned");
+  const bool lineFlags = type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && t == RTC_BUFFER_TYPE_FLAGS; // bytes (scene_line_segments.cpp:63)
+  if (!lineFlags && ((off & 3) || (stride & 3))) RT_THROW(RTC_ERROR_INVALID_OPERATION, "buffer offset and stride must be 4-byte aligned");
   if (b && off + (count ? (count - 1) * stride + format_bytes(f) : 0) > b->bytes && !b->shared)
     RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "buffer range out of bounds");
   switch (type) {
@@ -76,6 +77,18 @@ void Geometry::bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size
     if (t == RTC_BUFFER_TYPE_VERTEX && f != RTC_FORMAT_FLOAT3) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid vertex buffer format");
     if ((t == RTC_BUFFER_TYPE_INDEX || t == RTC_BUFFER_TYPE_FACE) && f != RTC_FORMAT_UINT)
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid index/face buffer format");
+    break;
+  case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE: // LineSegments::setBuffer (scene_line_segments.cpp)
+    if (t == RTC_BUFFER_TYPE_VERTEX) {
+      if (f != RTC_FORMAT_FLOAT4) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid vertex buffer format");
+    } else if (t == RTC_BUFFER_TYPE_INDEX) {
+      if (slot != 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid buffer slot");
+      if (f != RTC_FORMAT_UINT) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid index buffer format");
+    } else if (t == RTC_BUFFER_TYPE_FLAGS) { // kept; no effect on the flat linear intersector
+      if (slot != 0) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "invalid buffer slot");
+      if (f != RTC_FORMAT_UCHAR) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid flag buffer format");
+    } else if (t != RTC_BUFFER_TYPE_VERTEX_ATTRIBUTE)
+      RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown buffer type");
     break;
   default: break;
   }
@@ -142,6 +155,25 @@ bool Geometry::validQuad(size_t i, unsigned slot) const
   unsigned idx[4];
   quad(i, idx);
   return valid_vertices(*this, idx, 4, slot);
+}
+
+unsigned Geometry::segment(size_t i) const { return *(const unsigned*)view(RTC_BUFFER_TYPE_INDEX, 0)->at(i); }
+
+// LineSegments::valid (scene_line_segments.h): both vertices in range, all eight floats finite and within FLT_LARGE (the bound of
+// valid_vertices), both radii >= 0
+bool Geometry::validSegment(size_t i) const
+{
+  const BufferView* vv = view(RTC_BUFFER_TYPE_VERTEX, 0);
+  const size_t nv = vv && vv->valid() ? vv->count : 0;
+  const size_t i0 = segment(i);
+  if (i0 + 1 >= nv) return false;
+  for (size_t k = i0; k < i0 + 2; k++) {
+    const float* p = (const float*)vv->at(k);
+    for (int c = 0; c < 4; c++)
+      if (!std::isfinite(p[c]) || fabsf(p[c]) > 1.844e18f) return false;
+    if (p[3] < 0.0f) return false;
+  }
+  return true;
 }
 
 // ---- Accel -------------------------------------------------------------------------------------------------
@@ -388,6 +420,76 @@ static void build_quad_accel(Scene* s)
   A.robust = pluecker ? 1 : 0;
   A.blobStride = sizeof(QuadRecord);
   A.blobs.resize(recs.size() * sizeof(QuadRecord));
+  memcpy(A.blobs.data(), recs.data(), A.blobs.size());
+}
+
+// Flat linear curves (Scene::createLineAccel, scene.cpp:444-468: bvh8.line4i; BVHNBuilderSAH<8,LineSegments,Line4i>(..., 4, 1.0f, 4, inf)):
+// one BVH8 with the triangle settings over the valid segments of the scene's enabled line geometries, the sibling of build_mesh_bvh8 for
+// a primitive that is read through one index word and whose box is not the box of its vertices: merge(p0, p1) enlarged on every side
+// by max(r0, r1) (LineMi::bounds).  Every name builds the same accel; the reference has one line intersector, so the kind only tells
+// the traversal: robust for a robust scene, fast otherwise.
+static void build_line_accel(Scene* s)
+{
+  Accel& A = s->lineAccel;
+  A.clear();
+  const std::string& name = s->device->line_accel;
+  if (name != "default" && name != "bvh8.line4i" && name != "bvh4.line4i") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown line segment acceleration structure " + name);
+
+  struct Src { unsigned geomID, primID; };
+  std::vector<Src> src;
+  std::vector<BuildPrim> bp;
+  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
+    Geometry* g = s->geometries[gid];
+    if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE) continue;
+    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur of line segments is not supported");
+    const size_t n = g->numSegments();
+    for (size_t i = 0; i < n; i++) {
+      if (!g->validSegment(i)) continue;
+      const float* p0 = (const float*)g->view(RTC_BUFFER_TYPE_VERTEX, 0)->at(g->segment(i));
+      const float* p1 = (const float*)g->view(RTC_BUFFER_TYPE_VERTEX, 0)->at(g->segment(i) + 1);
+      const float r = std::max(p0[3], p1[3]);
+      BuildPrim p;
+      p.box.extend(V3(std::min(p0[0], p1[0]) - r, std::min(p0[1], p1[1]) - r, std::min(p0[2], p1[2]) - r));
+      p.box.extend(V3(std::max(p0[0], p1[0]) + r, std::max(p0[1], p1[1]) + r, std::max(p0[2], p1[2]) + r));
+      p.id = (uint32_t)src.size();
+      src.push_back({gid, (unsigned)i});
+      bp.push_back(p);
+    }
+  }
+  if (bp.empty()) return;
+  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many line segments for the 26-bit leaf reference");
+
+  std::vector<LineRecord> recs;
+  recs.reserve(bp.size());
+  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
+    const uint32_t first = (uint32_t)recs.size();
+    for (size_t i = begin; i < end; i++) {
+      const Src& sr = src[prims[i].id];
+      const Geometry* g = s->geometries[sr.geomID];
+      const float* p0 = (const float*)g->view(RTC_BUFFER_TYPE_VERTEX, 0)->at(g->segment(sr.primID));
+      const float* p1 = (const float*)g->view(RTC_BUFFER_TYPE_VERTEX, 0)->at(g->segment(sr.primID) + 1);
+      LineRecord r;
+      memset(&r, 0, sizeof(r));
+      r.v0x = p0[0]; r.v0y = p0[1]; r.v0z = p0[2]; r.r0 = p0[3];
+      r.v1x = p1[0]; r.v1y = p1[1]; r.v1z = p1[2]; r.r1 = p1[3];
+      r.geomID = sr.geomID;
+      r.primID = sr.primID;
+      recs.push_back(r);
+    }
+    return make_tri_leaf(first, (uint32_t)(end - begin));
+  };
+  BuildSettings cfg;
+  cfg.threads = host_threads(s->device);
+  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
+  A.nodes = std::move(r.nodes);
+  A.root = r.root;
+  A.maxDepth = r.maxDepth;
+  A.leafCount = r.leafCount;
+  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  A.kind = s->isRobust() ? ACCEL_LINE_ROBUST : ACCEL_LINE_FAST; // only once there are segments
+  A.robust = s->isRobust() ? 1 : 0;
+  A.blobStride = sizeof(LineRecord);
+  A.blobs.resize(recs.size() * sizeof(LineRecord));
   memcpy(A.blobs.data(), recs.data(), A.blobs.size());
 }
 
@@ -666,17 +768,22 @@ void Scene::commit()
     case RTC_GEOMETRY_TYPE_TRIANGLE:
     case RTC_GEOMETRY_TYPE_QUAD:
     case RTC_GEOMETRY_TYPE_SUBDIVISION:
+    case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE:
     case RTC_GEOMETRY_TYPE_INSTANCE: break;
     default: // scene.cpp:25-30: geometry types compiled out raise INVALID_OPERATION
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry type not supported by the MI355X traversal path");
     }
   }
   triIntersectFilter = triOccludedFilter = subdivFilter = false;
+  lineIntersectFilter = lineOccludedFilter = false;
   for (Geometry* geo : geometries) {
     if (!geo || !geo->enabled) continue;
     if (geo->type == RTC_GEOMETRY_TYPE_TRIANGLE || geo->type == RTC_GEOMETRY_TYPE_QUAD) {
       triIntersectFilter |= geo->intersectFilter != nullptr;
       triOccludedFilter |= geo->occludedFilter != nullptr;
+    } else if (geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE) {
+      lineIntersectFilter |= geo->intersectFilter != nullptr;
+      lineOccludedFilter |= geo->occludedFilter != nullptr;
     } else if (geo->type == RTC_GEOMETRY_TYPE_SUBDIVISION)
       subdivFilter |= geo->intersectFilter != nullptr || geo->occludedFilter != nullptr;
   }
@@ -687,6 +794,7 @@ void Scene::commit()
   build_quad_accel(this);
   build_quadmb_accel(this);
   build_subdiv_accel(this);
+  build_line_accel(this);
   build_instance_accel(this);
   build_instance_subdiv_accel(this);
   for (Accel* a : accels()) a->upload(device);
@@ -705,6 +813,9 @@ void Scene::commit()
       fprintf(stderr, "embree3-amd: motion blur quad accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", quadMBAccel.kind, quadMBAccel.nodeCount(),
               quadMBAccel.nodeCount() * quadMBAccel.nodeStride(), quadMBAccel.blobs.size() / sizeof(QuadMBRecord), quadMBAccel.blobs.size(), quadMBAccel.maxDepth);
   }
+  if (lineAccel.kind != ACCEL_NONE && device->verbose >= 2)
+    fprintf(stderr, "embree3-amd: line accel kind %u: %zu nodes (%zu B), %zu segments (%zu B), depth %u\n", lineAccel.kind, lineAccel.nodes.size(),
+            lineAccel.nodes.size() * sizeof(QNode8), lineAccel.blobs.size() / sizeof(LineRecord), lineAccel.blobs.size(), lineAccel.maxDepth);
   if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
   {
     // the record counts of the layout (build_instance_accel).  Below the kinds ACCEL_INSTMESHMB_* "instanced quads" has always counted

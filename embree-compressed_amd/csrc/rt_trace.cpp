@@ -145,7 +145,8 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   p.survivors = nullptr;
   // (never on the kinds of mb_bounds=linear: the pre-pass decodes a QNode8 root, and a root of time-dependent boxes would have to be
   // culled per ray time)
-  if (dev->tuneCull && !p.poolKernel && !instKernel && !is_mb_linear_kind(A.kind) && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
+  // (nor on the line accel: launch_cull derives the node test from the mesh kinds)
+  if (dev->tuneCull && !p.poolKernel && !instKernel && !is_mb_linear_kind(A.kind) && !is_line_kind(A.kind) &&!x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
     const size_t need = ((size_t)(M + TRACE_QUEUES - 1) / TRACE_QUEUES) * TRACE_QUEUES * 4u;
     if (need > ctx.survivorsBytes) { // first batch of this size on this context (an allocation synchronises the device)
       HIP_CHECK(hipStreamSynchronize(stream));
@@ -304,7 +305,8 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
   const bool subdivFilters = s->subdivFilter && s->subdivAccel.kind == ACCEL_GRIDSOA;
   // (instIntersectFilter / instOccludedFilter: filters below mesh instances, set only under inst_filters=1)
   const bool instFilters = occluded ? s->instOccludedFilter : s->instIntersectFilter;
-  if (!countersOut && ((ctx && ctx->filter) || subdivFilters || instFilters || (occluded ? s->triOccludedFilter : s->triIntersectFilter))) {
+  const bool lineFilters = occluded ? s->lineOccludedFilter : s->lineIntersectFilter;
+  if (!countersOut && ((ctx && ctx->filter) || subdivFilters || instFilters || lineFilters || (occluded ? s->triOccludedFilter : s->triIntersectFilter))) {
     trace_filtered(s, rays, M, byteStride, occluded, ctx);
     return;
   }

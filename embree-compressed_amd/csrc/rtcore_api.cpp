@@ -87,7 +87,7 @@ API ssize_t rtcGetDeviceProperty(RTCDevice h, enum RTCDeviceProperty prop)
   case RTC_DEVICE_PROPERTY_TRIANGLE_GEOMETRY_SUPPORTED: return 1;
   case RTC_DEVICE_PROPERTY_QUAD_GEOMETRY_SUPPORTED: return D(h)->quads_enabled() ? 1 : 0;
   case RTC_DEVICE_PROPERTY_SUBDIVISION_GEOMETRY_SUPPORTED: return 1;
-  case RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED: return 0;
+  case RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED: return 0; // speaks for all five curve types: only RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE is taken
   case RTC_DEVICE_PROPERTY_USER_GEOMETRY_SUPPORTED: return 0;
   case RTC_DEVICE_PROPERTY_TASKING_SYSTEM: return 0; // "internal"
   case RTC_DEVICE_PROPERTY_JOIN_COMMIT_SUPPORTED: return 1;
@@ -159,8 +159,8 @@ API RTCGeometry rtcNewGeometry(RTCDevice h, enum RTCGeometryType type)
     if (!D(h)->quads_enabled()) unsupported("RTC_GEOMETRY_TYPE_QUAD on a host-only device without quad_accel=");
     return (RTCGeometry) new Geometry(D(h), type);
   case RTC_GEOMETRY_TYPE_INSTANCE: return (RTCGeometry) new Geometry(D(h), type); // every device, host-only ones included
+  case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE: return (RTCGeometry) new Geometry(D(h), type); // line segments (trace_line.hip): every device, host-only ones included
   case RTC_GEOMETRY_TYPE_USER: unsupported("RTC_GEOMETRY_TYPE_USER");
-  case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE:
   case RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE:
   case RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE:
   case RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE:
@@ -434,6 +434,7 @@ API void rtcInterpolate(const struct RTCInterpolateArguments* args)
   Geometry* g = G(args->geometry);
   if (g->type == RTC_GEOMETRY_TYPE_TRIANGLE) interpolate_triangles(g, args);
   else if (g->type == RTC_GEOMETRY_TYPE_QUAD) interpolate_quads(g, args);
+  else if (g->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE) interpolate_lines(g, args);
   else if (g->type == RTC_GEOMETRY_TYPE_SUBDIVISION) interpolate_subdiv(g, args);
   else unsupported("rtcInterpolate on this geometry type");
   CATCH_END(args && args->geometry ? devOf(args->geometry) : nullptr)
@@ -827,9 +828,13 @@ API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 
 // the accel the inspection calls describe: the subdivision accel if there is one, else the triangle accel, else the motion-blur triangle
 // accel, else the quad accel, else (a scene of nothing but quads with time steps) the motion-blur quad accel, else (a scene of nothing
-// but instances) the instance accel, else (nothing but instances of subdivision scenes) the subdivision instance accel
+// but instances) the instance accel, else (nothing but instances of subdivision scenes) the subdivision instance accel.  The line accel
+// is described when the scene has neither a subdivision nor a mesh accel, in front of the instance accels.
 static const Accel& exported_accel(const Scene* s)
 {
+  if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
+      s->quadMBAccel.kind == ACCEL_NONE && s->lineAccel.kind != ACCEL_NONE)
+    return s->lineAccel;
   if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
       s->quadMBAccel.kind == ACCEL_NONE && s->instAccel.kind == ACCEL_NONE && s->instSubdivAccel.kind != ACCEL_NONE)
     return s->instSubdivAccel;
@@ -966,7 +971,8 @@ API unsigned int rtcamdGetSceneFilterFlags(RTCScene h)
   CATCH_BEGIN
   VERIFY(h);
   const Scene* s = S(h);
-  return (s->triIntersectFilter ? RTCAMD_SCENE_FILTER_MESH_INTERSECT : 0u) | (s->triOccludedFilter ? RTCAMD_SCENE_FILTER_MESH_OCCLUDED : 0u) |
+  // (line geometries report with the meshes' flags, as quad meshes do)
+  return (s->triIntersectFilter || s->lineIntersectFilter ? RTCAMD_SCENE_FILTER_MESH_INTERSECT : 0u) | (s->triOccludedFilter || s->lineOccludedFilter ? RTCAMD_SCENE_FILTER_MESH_OCCLUDED : 0u) |
          (s->subdivFilter ? RTCAMD_SCENE_FILTER_SUBDIV : 0u) | (s->instIntersectFilter ? RTCAMD_SCENE_FILTER_INSTANCED_INTERSECT : 0u) |
          (s->instOccludedFilter ? RTCAMD_SCENE_FILTER_INSTANCED_OCCLUDED : 0u);
   CATCH_END(devOf(h))

@@ -999,6 +999,25 @@ void interpolate_quads(const Geometry* geom, const RTCInterpolateArguments* args
   }
 }
 
+// Flat linear curves (LineSegments::interpolate, scene_line_segments.cpp:228-263): P = lerp(a[index], a[index + 1], u), dPdu their
+// difference; v plays no part - dPdv and the second derivatives are zero.
+void interpolate_lines(const Geometry* geom, const RTCInterpolateArguments* args)
+{
+  const BufferView* src = geom->view(args->bufferType, args->bufferSlot);
+  if (!src || !src->valid()) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: buffer slot is not bound");
+  if (args->primID >= geom->numSegments()) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: invalid primID");
+  const size_t i0 = geom->segment(args->primID);
+  if (i0 + 1 >= src->count) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: segment index out of range");
+  const float u = args->u;
+  for (unsigned i = 0; i < args->valueCount; i++) {
+    const float p0 = ((const float*)src->at(i0))[i], p1 = ((const float*)src->at(i0 + 1))[i];
+    if (args->P) args->P[i] = fmaf(1.0f - u, p0, u * p1);
+    if (args->dPdu) args->dPdu[i] = p1 - p0;
+    if (args->dPdv) args->dPdv[i] = 0.f;
+    if (args->ddPdudu) { args->ddPdudu[i] = 0.f; args->ddPdvdv[i] = 0.f; args->ddPdudv[i] = 0.f; }
+  }
+}
+
 // Subdivision meshes: Catmull-Clark limit surface of any vertex / vertex-attribute buffer at (primID, u, v).
 // The reference evaluates through patch classification, bicubic B-spline patches, feature-adaptive subdivision and
 // Gregory patches (scene_subdiv_mesh.cpp:757-864, patch_eval.h).  Here the buffer is refined K = 3 times with the

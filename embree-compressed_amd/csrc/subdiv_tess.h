@@ -37,6 +37,7 @@ void tessellate_subdiv(const Geometry* geom, unsigned geomID, unsigned L, std::v
 // vertex / vertex-attribute buffer with first and second derivatives; scene_subdiv_mesh.cpp:757-864).
 void interpolate_triangles(const Geometry* geom, const RTCInterpolateArguments* args);
 void interpolate_quads(const Geometry* geom, const RTCInterpolateArguments* args);
+void interpolate_lines(const Geometry* geom, const RTCInterpolateArguments* args);
 void interpolate_subdiv(Geometry* geom, const RTCInterpolateArguments* args);
 
 } // namespace rtamd

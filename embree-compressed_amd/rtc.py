@@ -18,6 +18,7 @@ RTC_INVALID_GEOMETRY_ID = 0xFFFFFFFF
 RTC_GEOMETRY_TYPE_TRIANGLE = 0
 RTC_GEOMETRY_TYPE_QUAD = 1
 RTC_GEOMETRY_TYPE_SUBDIVISION = 8
+RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE = 17
 RTC_GEOMETRY_TYPE_INSTANCE = 121
 RTC_BUFFER_TYPE_INDEX = 0
 RTC_BUFFER_TYPE_VERTEX = 1
@@ -28,6 +29,9 @@ RTC_BUFFER_TYPE_EDGE_CREASE_INDEX = 18
 RTC_BUFFER_TYPE_EDGE_CREASE_WEIGHT = 19
 RTC_BUFFER_TYPE_VERTEX_CREASE_INDEX = 20
 RTC_BUFFER_TYPE_VERTEX_CREASE_WEIGHT = 21
+RTC_BUFFER_TYPE_FLAGS = 32
+RTC_FORMAT_UCHAR = 0x1001
+RTC_FORMAT_FLOAT4 = 0x9004
 RTC_FORMAT_UINT = 0x5001
 RTC_FORMAT_UINT3 = 0x5003
 RTC_FORMAT_UINT4 = 0x5004
@@ -178,6 +182,9 @@ def load_library(path=LIB_PATH):
         "rtcSetGeometryTessellationRate": (None, [vp, C.c_float]),
         "rtcSetGeometryTimeStepCount": (None, [vp, u]),
         "rtcSetGeometryUserData": (None, [vp, vp]),
+        "rtcGetGeometryUserData": (vp, [vp]),
+        "rtcSetGeometryMask": (None, [vp, u]),
+        "rtcUpdateGeometryBuffer": (None, [vp, C.c_int, u]),
         "rtcSetGeometryIntersectFilterFunction": (None, [vp, vp]),
         "rtcSetGeometryOccludedFilterFunction": (None, [vp, vp]),
         "rtcSetGeometryInstancedScene": (None, [vp, vp]),
@@ -389,6 +396,34 @@ class Scene:
         L.rtcReleaseGeometry(g)
         self._keep += [vpad, q]
         self.device.check("add_quads")
+        return gid
+
+    def add_lines(self, verts4, first_index, geom_id=None, flags=None):
+        """Line segments (RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE): verts4 float32 [nv,4] = (x, y, z, radius), first_index uint32 [ns]: segment i
+        runs from vertex first_index[i] to vertex first_index[i] + 1; flags optional uint8 [ns] (RTC_BUFFER_TYPE_FLAGS, kept, no effect on
+        flat linear curves); shared buffers like add_quads."""
+        L = self.lib
+        v = np.ascontiguousarray(verts4, dtype=np.float32).reshape(-1, 4)
+        vpad = np.zeros((v.shape[0] + 1, 4), dtype=np.float32)
+        vpad[: v.shape[0]] = v
+        idx = np.ascontiguousarray(first_index, dtype=np.uint32).reshape(-1)
+        g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE)
+        self.device.check("rtcNewGeometry(FLAT_LINEAR_CURVE)")
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_VERTEX, 0, RTC_FORMAT_FLOAT4, vpad.ctypes.data, 0, 16, v.shape[0])
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_INDEX, 0, RTC_FORMAT_UINT, idx.ctypes.data, 0, 4, idx.shape[0])
+        self._keep += [vpad, idx]
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_FLAGS, 0, RTC_FORMAT_UCHAR, fl.ctypes.data, 0, 1, fl.shape[0])
+            self._keep.append(fl)
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self.device.check("add_lines")
         return gid
 
     def add_quads_mb(self, verts_per_step, quads, geom_id=None):

@@ -9,6 +9,7 @@
 //                            or TriMBRecord[] (96-byte motion-blur triangle records, leaf-contiguous) for triangle meshes with time steps,
 //                            or QuadMBRecord[] (128-byte motion-blur quad records, leaf-contiguous) for quad meshes with time steps,
 //                            or LineRecord[] (48-byte line segment records, leaf-contiguous) for flat linear curves,
+//                            or LineMBRecord[] (80-byte motion-blur line segment records, leaf-contiguous) for flat linear curves with time steps,
 //                            or InstanceRecord[] (64-byte instance records, one per top-level leaf) for instances, followed in
 //                            the kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER by the instanced scenes' QuadRecord[], in the kinds
 //                            ACCEL_INSTMESHMB_* also by InstanceSceneRecord[], TriMBRecord[] and QuadMBRecord[] (see InstanceRecord)
@@ -31,6 +32,7 @@ namespace rtamd {
 // MB tri leaf : the same form, counting TriMBRecords (one per triangle and time segment)
 // MB quad leaf: the same form, counting QuadMBRecords (one per quad and time segment)
 // line leaf   : the same form, counting LineRecords
+// MB line leaf: the same form, counting LineMBRecords (one per segment and time segment)
 // subdiv leaf : bits 0..30 = blob index (one blob per leaf, like encodeTypedLeaf(ptr,1) bvh_builder_subdiv.cpp:728)
 static const uint32_t REF_EMPTY = 0xFFFFFFFFu; // no child (reference: BVH::emptyNode, bvh.h:117-132)
 static const uint32_t REF_LEAF = 0x80000000u;
@@ -140,6 +142,24 @@ struct alignas(16) LineRecord
   uint32_t pad[2];
 };
 static_assert(sizeof(LineRecord) == 48, "LineRecord must be 48 bytes");
+
+// ---- motion-blur line segment record, 80 bytes = 5 x dwordx4 ------------------------------------------------------------
+// One segment of a flat linear curve with time steps at both ends of ONE time segment of its geometry: the end points with their
+// radii at step `segment` (v0a, v1a) and at step `segment` + 1 (v0b, v1b).  Time segments, record selection and blocks as for
+// TriMBRecord; the end points are interpolated in ALL FOUR components, the radius included (the reference lerps Vec4vf, LineMi::gather
+// with a time, linei.h:276-277), and go through the test of the static line leaf.  The radius fills the w of every vertex, so the four
+// id words have a dwordx4 of their own (TriMBRecord keeps them in the vertices' w).
+struct alignas(16) LineMBRecord
+{
+  float v0ax, v0ay, v0az, r0a;
+  float v1ax, v1ay, v1az, r1a;
+  float v0bx, v0by, v0bz, r0b;
+  float v1bx, v1by, v1bz, r1b;
+  uint32_t geomID, primID;
+  uint32_t segment;     // itime this record serves
+  uint32_t numSegments; // S of the geometry
+};
+static_assert(sizeof(LineMBRecord) == 80, "LineMBRecord must be 80 bytes");
 
 // ---- motion-blur triangle record, 96 bytes = 6 x dwordx4 -------------------------------------------------------------
 // The three vertices of a triangle at both ends of ONE time segment of its mesh (a0..c0 at step `segment`, a1..c1 at step `segment` + 1).
@@ -458,7 +478,15 @@ enum AccelKind : uint32_t
   // flat linear curves (Scene::lineAccel, line_accel=default / bvh8.line4i / bvh4.line4i): LineRecord[] in `blobs`, one leaf arithmetic;
   // robust traversal for RTC_SCENE_FLAG_ROBUST scenes, fast traversal otherwise.  Neither instance nor motion-blur kinds.
   ACCEL_LINE_ROBUST = 36,
-  ACCEL_LINE_FAST = 37
+  ACCEL_LINE_FAST = 37,
+  // flat linear curves with time steps (Scene::lineMBAccel, line_accel_mb=default / bvh8.line4imb / bvh4.line4imb): LineMBRecord[] in
+  // `blobs`, the static line leaf's arithmetic on the interpolated end points; robust / fast traversal as for the kinds 36 / 37.
+  // Motion-blur kinds (lane kernel only, no service kernel), NOT line kinds in the sense of is_line_kind (no pool form).
+  ACCEL_LINEMB_ROBUST = 38,
+  ACCEL_LINEMB_FAST = 39,
+  // the same under mb_bounds=linear: QNodeMB8[] in `nodes`, 144-byte stride, as the kinds 26..29
+  ACCEL_LINEMB_LINEAR_ROBUST = 40,
+  ACCEL_LINEMB_LINEAR_FAST = 41
 };
 inline bool is_line_kind(uint32_t kind) { return kind == ACCEL_LINE_ROBUST || kind == ACCEL_LINE_FAST; } // traced by trace_line.hip: lane and pool kernels, no service kernel
 inline bool is_inst_linear_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_LINEAR_PLUECKER || kind == ACCEL_INSTMESHMB_LINEAR_MOELLER; } // traced by trace_instance_mesh_mb_linear.hip
@@ -472,20 +500,28 @@ inline bool is_inst_general_kind(uint32_t kind) { return kind == ACCEL_INSTMESHM
 // trace_instance_subdiv_top_linear.hip
 inline bool is_instance_kind(uint32_t kind) { return (kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF) || is_inst_two_section_kind(kind); }
 
-inline bool is_mb_linear_kind(uint32_t kind) { return kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER; } // nodes are QNodeMB8
+// traced by trace_line_mb.hip: lane kernel only
+inline bool is_line_mb_kind(uint32_t kind) { return kind >= ACCEL_LINEMB_ROBUST && kind <= ACCEL_LINEMB_LINEAR_FAST; }
+// nodes are QNodeMB8: node stride, no root-cull pre-pass.  (The instance builder asks this of the triangle and quad motion-blur accels of
+// an instanced scene only; a scene with a line accel of either kind is refused below an instance before it gets there.)
+inline bool is_mb_linear_kind(uint32_t kind)
+{
+  return (kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER) || kind == ACCEL_LINEMB_LINEAR_ROBUST || kind == ACCEL_LINEMB_LINEAR_FAST;
+}
 // the arithmetic of a motion-blur mesh accel, under swept and under linear bounds
 inline bool is_mb_pluecker_kind(uint32_t kind)
 {
   return kind == ACCEL_TRIMB_PLUECKER || kind == ACCEL_QUADMB_PLUECKER || kind == ACCEL_TRIMB_LINEAR_PLUECKER || kind == ACCEL_QUADMB_LINEAR_PLUECKER;
 }
-inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKER && kind <= ACCEL_QUADMB_MOELLER) || is_mb_linear_kind(kind); } // lane kernel only, no service kernel
+// the motion-blur accels of triangles, quads and line segments, under swept and under linear bounds: lane kernel only, no service kernel
+inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKER && kind <= ACCEL_QUADMB_MOELLER) || is_mb_linear_kind(kind) || is_line_mb_kind(kind); }
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
 {
   const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_*
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the LineRecord[] of a line accel, or the TriMBRecord[] / QuadMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the LineRecord[] of a line accel, or the TriMBRecord[] / QuadMBRecord[] / LineMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind
@@ -504,7 +540,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel of a scene: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, lines, instances, subdivision instances)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel of a scene: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, lines, motion-blur lines, instances, subdivision instances)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

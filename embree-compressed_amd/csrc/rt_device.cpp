@@ -41,6 +41,7 @@ void Device::parse(const std::string& cfg)
     else if (key == "tri_accel_mb") { tri_accel_mb = val; triAccelMBNamed = true; }
     else if (key == "quad_accel_mb") { quad_accel_mb = val; quadAccelMBNamed = true; }
     else if (key == "line_accel") line_accel = val;
+    else if (key == "line_accel_mb") { line_accel_mb = val; lineAccelMBNamed = true; }
     else if (key == "inst_accel") { inst_accel = val; instAccelNamed = true; }
     else if (key == "mb_bounds") {
       if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "mb_bounds=: unknown value '" + val + "' (swept or linear)");

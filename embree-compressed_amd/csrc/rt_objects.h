@@ -36,6 +36,8 @@ struct Device : RefCounted
   std::string inst_subdiv_bounds = "swept"; // top-level boxes of moving subdivision instances (Scene::instSubdivAccel): "swept" (QNode8, kinds 24 / 25) or "linear" (a top-level tree of QNodeMB8s, kinds ACCEL_INSTSUBDIV_TOP_LINEAR_*)
   bool inst_filters = false; // "inst_filters=1": filter functions run on hits below mesh instances (geometry filters inside instanced mesh scenes, RTCIntersectContext::filter on scenes with mesh instances); 0, the default: both are refused as before
   std::string line_accel = "default"; // flat linear curves: default / bvh8.line4i / bvh4.line4i, all the one BVH8 over LineRecords (build_line_accel raises for any other at commit)
+  std::string line_accel_mb = "default"; // flat linear curves with time steps: default / bvh8.line4imb / bvh4.line4imb, all the one BVH8 over LineMBRecords (build_linemb_accel raises for any other at commit)
+  bool lineAccelMBNamed = false; // "line_accel_mb=" given (a host-only device builds the motion-blur line accel only then, lines_mb_enabled())
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel, rt_instance_build.cpp, raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
@@ -221,6 +223,9 @@ struct Device : RefCounted
   // Quad meshes with time steps follow the same rule with their own key: a host-only device whose config does not name quad_accel_mb=
   // raises INVALID_OPERATION at commit for them, as before the motion-blur quad accel existed.
   bool quads_mb_enabled() const { return gpu >= 0 || quadAccelMBNamed; }
+  // Line segments with time steps, the same rule with the key line_accel_mb=: a host-only device without it raises "motion blur of line
+  // segments is not supported" at commit, as before the motion-blur line accel existed.
+  bool lines_mb_enabled() const { return gpu >= 0 || lineAccelMBNamed; }
   // Quad meshes inside an instanced scene, the same rule with the key inst_accel=: a host-only device without it refuses them at the top
   // scene's commit, as before the instance accel took quads.
   bool inst_quads_enabled() const { return gpu >= 0 || instAccelNamed; }
@@ -338,7 +343,7 @@ struct Geometry : RefCounted
   // index[i] to vertex index[i] + 1; vertices are (x, y, z, radius)
   size_t numSegments() const { return numTriangles(); } // index buffer records (UINT)
   unsigned segment(size_t i) const;
-  bool validSegment(size_t i) const;
+  bool validSegment(size_t i, unsigned slot = 0) const; // LineSegments::valid(i, itime): against the vertex buffer of time step `slot`
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -418,11 +423,12 @@ struct Scene : RefCounted
   Accel quadMBAccel; // quads with several time steps (QuadMBRecord[] in `blobs`); traced after the static quads, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
   Accel lineAccel;   // flat linear curves (LineRecord[] in `blobs`); traced after the subdivision patches, before the instances (scene.cpp:650-663)
+  Accel lineMBAccel; // flat linear curves with several time steps (LineMBRecord[] in `blobs`); traced right after the static lines (scene.cpp: createLineAccel, createLineMBAccel)
   Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle and quad trees behind the top-level tree); traced last (scene.cpp:661-665)
   Accel instSubdivAccel; // instances of scenes that hold subdivision meshes only (InstanceRecord[] and the instanced scenes' leaf blobs in `blobs`, their BVH8s behind the top-level tree); traced after the mesh instances
-  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / LINE / INST / INSTSUBDIV index whatever a path keeps per accel
-  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, LINE = 5, INST = 6, INSTSUBDIV = 7, NUM_ACCELS = 8 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &lineAccel, &instAccel, &instSubdivAccel}; }
+  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / LINE / LINEMB / INST / INSTSUBDIV index whatever a path keeps per accel
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, LINE = 5, LINEMB = 6, INST = 7, INSTSUBDIV = 8, NUM_ACCELS = 9 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &lineAccel, &lineMBAccel, &instAccel, &instSubdivAccel}; }
   bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
   // records the layout of instAccel placed in `blobs` behind the InstanceRecords, as build_instance_accel counted them (host only: the
   // verbose line of commit prints them)

@@ -159,11 +159,11 @@ bool Geometry::validQuad(size_t i, unsigned slot) const
 
 unsigned Geometry::segment(size_t i) const { return *(const unsigned*)view(RTC_BUFFER_TYPE_INDEX, 0)->at(i); }
 
-// LineSegments::valid (scene_line_segments.h): both vertices in range, all eight floats finite and within FLT_LARGE (the bound of
-// valid_vertices), both radii >= 0
-bool Geometry::validSegment(size_t i) const
+// LineSegments::valid(i, itime) (scene_line_segments.h): both vertices in range of the time step's buffer, all eight floats finite and
+// within FLT_LARGE (the bound of valid_vertices), both radii >= 0
+bool Geometry::validSegment(size_t i, unsigned slot) const
 {
-  const BufferView* vv = view(RTC_BUFFER_TYPE_VERTEX, 0);
+  const BufferView* vv = view(RTC_BUFFER_TYPE_VERTEX, slot);
   const size_t nv = vv && vv->valid() ? vv->count : 0;
   const size_t i0 = segment(i);
   if (i0 + 1 >= nv) return false;
@@ -441,7 +441,10 @@ static void build_line_accel(Scene* s)
   for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
     Geometry* g = s->geometries[gid];
     if (!g || !g->enabled || g->type != RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE) continue;
-    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur of line segments is not supported");
+    if (g->timeSteps != 1) {
+      if (s->device->lines_mb_enabled()) continue; // build_linemb_accel
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur of line segments is not supported");
+    }
     const size_t n = g->numSegments();
     for (size_t i = 0; i < n; i++) {
       if (!g->validSegment(i)) continue;
@@ -498,7 +501,6 @@ static void build_line_accel(Scene* s)
 // of the primitive's boxes at the two ends of the segment - the vertices move on straight lines in between, so the box holds the
 // primitive at every time of the segment (and, by the same argument, NOT at extrapolated times: a ray with a time outside [0, 1] sees
 // the first / last segment only where it still is inside its box).  A pair gets a record only when the primitive is valid at both ends.
-// fill(rec, v) writes the 2 * NV vertices (segment start, then segment end) into a zeroed record; the four id words are set here.
 // false (and `A` untouched): no record.
 // mb_bounds=linear (Device::mb_bounds): the same pairs, records and leaf conventions under time-dependent nodes (accel.h QNodeMB8, `A.nodesMB`).
 //  * Topology: the SAH build runs over every pair's box at ONE instant, the midpoint of its segment (the box of the vertices'
@@ -511,8 +513,13 @@ static void build_line_accel(Scene* s)
 //    sticks out, and the result is exactly the bounds at step 0 and at step 1.  Computed in double and rounded outward to fp32; what
 //    double loses is covered, far over, by the quantizer's one-step padding.
 //  * Scene::bounds is extended by the swept boxes, as in the swept build.
-template <int NV, class Rec, class Fill>
-static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* tooMany, std::vector<Rec>& recs, const Fill& fill)
+// Where a primitive's end boxes and record come from is the Source's business (MeshMBSource: NV vertices through an index record;
+// LineMBSource: two FLOAT4 vertices through one index word, boxes enlarged by the radius):
+//   valid(g, i, step)              the primitive at a time step (TriangleMesh / QuadMesh / LineSegments::valid(i, itime))
+//   boxes(g, i, seg, a, b, mid)    its boxes at steps seg and seg + 1 and at mid-segment
+//   fill(rec, g, i, seg)           the geometry of the record; the four id words are set here
+template <class Rec, class Source>
+static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* tooMany, std::vector<Rec>& recs, const Source& source)
 {
   const bool linear = s->device->mb_bounds == "linear";
   struct Src { unsigned geomID, primID, segment; };
@@ -521,10 +528,6 @@ static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* 
   std::vector<Ends> ends;
   std::vector<BuildPrim> bp;
   Box3 swept;
-  auto vertices = [](const Geometry* g, size_t i, unsigned slot, V3* v) {
-    const unsigned* idx = (const unsigned*)g->view(RTC_BUFFER_TYPE_INDEX, 0)->at(i);
-    for (int k = 0; k < NV; k++) v[k] = g->vertex(idx[k], slot);
-  };
   for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
     Geometry* g = s->geometries[gid];
     if (!g || !g->enabled || g->type != type || g->timeSteps == 1) continue;
@@ -535,28 +538,25 @@ static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* 
     const size_t n = g->numTriangles(); // index buffer records
     std::vector<char> ok(g->timeSteps);
     for (size_t i = 0; i < n; i++) {
-      for (unsigned t = 0; t < g->timeSteps; t++) ok[t] = NV == 4 ? g->validQuad(i, t) : g->validTriangle(i, t);
+      for (unsigned t = 0; t < g->timeSteps; t++) ok[t] = source.valid(g, i, t);
       for (unsigned seg = 0; seg + 1 < g->timeSteps; seg++) {
         if (!ok[seg] || !ok[seg + 1]) continue; // invalid at either end of the segment: no record for it
-        V3 v[2 * NV];
-        vertices(g, i, seg, v);
-        vertices(g, i, seg + 1, v + NV);
+        Ends e;
+        Box3 mid;
+        source.boxes(g, i, seg, e.a, e.b, mid);
         BuildPrim p;
         if (linear) {
-          Ends e;
-          for (int k = 0; k < NV; k++) {
-            e.a.extend(v[k]);
-            e.b.extend(v[NV + k]);
-            p.box.extend((v[k] + v[NV + k]) * 0.5f);
-          }
+          p.box = mid;
           const double S = (double)(g->timeSteps - 1);
           e.ta = (double)seg / S;
           e.tb = (double)(seg + 1) / S;
           swept.extend(e.a);
           swept.extend(e.b);
           ends.push_back(e);
-        } else
-          for (int k = 0; k < 2 * NV; k++) p.box.extend(v[k]);
+        } else {
+          p.box.extend(e.a);
+          p.box.extend(e.b);
+        }
         p.id = (uint32_t)src.size();
         src.push_back({gid, (unsigned)i, seg});
         bp.push_back(p);
@@ -572,12 +572,9 @@ static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* 
     for (size_t i = begin; i < end; i++) {
       const Src& sr = src[prims[i].id];
       const Geometry* g = s->geometries[sr.geomID];
-      V3 v[2 * NV];
-      vertices(g, sr.primID, sr.segment, v);
-      vertices(g, sr.primID, sr.segment + 1, v + NV);
       Rec r;
       memset(&r, 0, sizeof(r));
-      fill(r, v);
+      source.fill(r, g, sr.primID, sr.segment);
       r.geomID = sr.geomID;
       r.primID = sr.primID;
       r.segment = sr.segment;
@@ -639,6 +636,38 @@ static bool build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const char* 
   return true;
 }
 
+// The Source of the triangle and quad meshes: NV vertices through the index record (UINT3 / UINT4), a box is the box of the vertices, the
+// mid-segment box the box of the vertices' midpoints; fill(rec, v) writes the 2 * NV vertices (segment start, then segment end) into the
+// zeroed record.
+template <int NV, class Rec, class Fill> struct MeshMBSource
+{
+  const Fill& fillVertices;
+  static void vertices(const Geometry* g, size_t i, unsigned slot, V3* v)
+  {
+    const unsigned* idx = (const unsigned*)g->view(RTC_BUFFER_TYPE_INDEX, 0)->at(i);
+    for (int k = 0; k < NV; k++) v[k] = g->vertex(idx[k], slot);
+  }
+  bool valid(const Geometry* g, size_t i, unsigned step) const { return NV == 4 ? g->validQuad(i, step) : g->validTriangle(i, step); }
+  void boxes(const Geometry* g, size_t i, unsigned seg, Box3& a, Box3& b, Box3& mid) const
+  {
+    V3 v[2 * NV];
+    vertices(g, i, seg, v);
+    vertices(g, i, seg + 1, v + NV);
+    for (int k = 0; k < NV; k++) {
+      a.extend(v[k]);
+      b.extend(v[NV + k]);
+      mid.extend((v[k] + v[NV + k]) * 0.5f);
+    }
+  }
+  void fill(Rec& r, const Geometry* g, size_t i, unsigned seg) const
+  {
+    V3 v[2 * NV];
+    vertices(g, i, seg, v);
+    vertices(g, i, seg + 1, v + NV);
+    fillVertices(r, v);
+  }
+};
+
 // Triangle meshes with more than one time step (scene.cpp:213-247).  Every name is served by the one TriMBRecord layout: default =
 // Pluecker + robust traversal for a robust scene, Moeller + fast traversal otherwise; an explicit triangle4imb / triangle4vmb accel is
 // the fast (Moeller) variant.
@@ -661,7 +690,7 @@ static void build_trimb_accel(Scene* s)
     r.b1x = v[4].x; r.b1y = v[4].y; r.b1z = v[4].z;
     r.c1x = v[5].x; r.c1y = v[5].y; r.c1z = v[5].z;
   };
-  if (!build_mb_bvh8<3>(s, A, RTC_GEOMETRY_TYPE_TRIANGLE, "too many motion blur triangle segments for the 26-bit leaf reference", recs, fill)) return;
+  if (!build_mb_bvh8(s, A, RTC_GEOMETRY_TYPE_TRIANGLE, "too many motion blur triangle segments for the 26-bit leaf reference", recs, MeshMBSource<3, TriMBRecord, decltype(fill)>{fill})) return;
   A.kind = pluecker ? ACCEL_TRIMB_PLUECKER : ACCEL_TRIMB_MOELLER; // only once there are records
   if (s->device->mb_bounds == "linear") A.kind = pluecker ? ACCEL_TRIMB_LINEAR_PLUECKER : ACCEL_TRIMB_LINEAR_MOELLER;
   A.robust = pluecker ? 1 : 0;
@@ -691,10 +720,74 @@ static void build_quadmb_accel(Scene* s)
     q.v2bx = v[6].x; q.v2by = v[6].y; q.v2bz = v[6].z;
     q.v3bx = v[7].x; q.v3by = v[7].y; q.v3bz = v[7].z;
   };
-  if (!build_mb_bvh8<4>(s, A, RTC_GEOMETRY_TYPE_QUAD, "too many motion blur quad segments for the 26-bit leaf reference", recs, fill)) return;
+  if (!build_mb_bvh8(s, A, RTC_GEOMETRY_TYPE_QUAD, "too many motion blur quad segments for the 26-bit leaf reference", recs, MeshMBSource<4, QuadMBRecord, decltype(fill)>{fill})) return;
   A.kind = pluecker ? ACCEL_QUADMB_PLUECKER : ACCEL_QUADMB_MOELLER; // only once there are records
   if (s->device->mb_bounds == "linear") A.kind = pluecker ? ACCEL_QUADMB_LINEAR_PLUECKER : ACCEL_QUADMB_LINEAR_MOELLER;
   A.robust = pluecker ? 1 : 0;
+}
+
+// The Source of the line segments: two FLOAT4 vertices (x, y, z, radius) through one index word.  A segment's box at a step is
+// LineMi::bounds(i, itime): merge(p0, p1) enlarged on every side by max(r0, r1) of that step; the mid-segment box is that of the
+// midpoint vertices with the midpoint radii.
+// Containment (swept and linear): at ftime f the leaf tests the segment lerp(p0a, p0b, f) - lerp(p1a, p1b, f) with the radii
+// lerp(r0a, r0b, f), lerp(r1a, r1b, f).  Per axis its box is min(x0(f), x1(f)) - max(r0(f), r1(f)) below and max(x0(f), x1(f)) +
+// max(r0(f), r1(f)) above, with all four functions linear in f.  min is concave and max is convex, so the lower plane is a concave
+// function of f and lies ON OR ABOVE the chord of its end values, the upper plane a convex one ON OR BELOW its chord: the box of the
+// interpolated segment with interpolated radii lies inside the interpolation of the two end boxes, which is what linear_bounds needs
+// of a pair's ends (and the interpolation lies inside their union, the swept box).  In fp32 (the budget of accel.h QNodeMB8, one grid
+// step s >= 2^-21 R): the radius is at most half a box's extent, so |r| <= R, and its lerp adds three roundings of at most 2^-24 R to
+// the three of the coordinate; with the plane's own two (2^-17 s + 2^-24 R) and time_segment's 2^-9 s on coordinate and radius that is
+// 7 * 2^-24 R + 2^-8 s + 2^-17 s <= 7 s / 8 + s / 256 + 2^-17 s < s: still inside the quantizer's one-step padding.
+struct LineMBSource
+{
+  static const float* vertex(const Geometry* g, size_t i, unsigned slot, int end) { return (const float*)g->view(RTC_BUFFER_TYPE_VERTEX, slot)->at((size_t)g->segment(i) + end); }
+  static void box_of(const float* p0, const float* p1, Box3& b)
+  {
+    const float r = std::max(p0[3], p1[3]);
+    b.extend(V3(std::min(p0[0], p1[0]) - r, std::min(p0[1], p1[1]) - r, std::min(p0[2], p1[2]) - r));
+    b.extend(V3(std::max(p0[0], p1[0]) + r, std::max(p0[1], p1[1]) + r, std::max(p0[2], p1[2]) + r));
+  }
+  bool valid(const Geometry* g, size_t i, unsigned step) const { return g->validSegment(i, step); }
+  void boxes(const Geometry* g, size_t i, unsigned seg, Box3& a, Box3& b, Box3& mid) const
+  {
+    const float *p0a = vertex(g, i, seg, 0), *p1a = vertex(g, i, seg, 1), *p0b = vertex(g, i, seg + 1, 0), *p1b = vertex(g, i, seg + 1, 1);
+    box_of(p0a, p1a, a);
+    box_of(p0b, p1b, b);
+    float m0[4], m1[4];
+    for (int c = 0; c < 4; c++) {
+      m0[c] = (p0a[c] + p0b[c]) * 0.5f;
+      m1[c] = (p1a[c] + p1b[c]) * 0.5f;
+    }
+    box_of(m0, m1, mid);
+  }
+  void fill(LineMBRecord& r, const Geometry* g, size_t i, unsigned seg) const
+  {
+    memcpy(&r.v0ax, vertex(g, i, seg, 0), 16);
+    memcpy(&r.v1ax, vertex(g, i, seg, 1), 16);
+    memcpy(&r.v0bx, vertex(g, i, seg + 1, 0), 16);
+    memcpy(&r.v1bx, vertex(g, i, seg + 1, 1), 16);
+  }
+};
+
+// Flat linear curves with more than one time step (Scene::createLineMBAccel, scene.cpp:470-494: bvh8.line4imb): LineMBRecords under the
+// frame of the motion-blur meshes.  Every name builds the same accel; the kind tells the traversal (robust for a robust scene) and the
+// node type (mb_bounds).  A host-only device builds this accel only when its config names line_accel_mb= (Device::lines_mb_enabled;
+// build_line_accel raises otherwise).
+static void build_linemb_accel(Scene* s)
+{
+  Accel& A = s->lineMBAccel;
+  A.clear();
+  if (!s->device->lines_mb_enabled()) return;
+  const std::string& name = s->device->line_accel_mb;
+  if (name != "default" && name != "bvh8.line4imb" && name != "bvh4.line4imb")
+    RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown motion blur line segment acceleration structure " + name);
+
+  std::vector<LineMBRecord> recs;
+  if (!build_mb_bvh8(s, A, RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE, "too many motion blur line segments for the 26-bit leaf reference", recs, LineMBSource())) return;
+  const bool robust = s->isRobust();
+  A.kind = robust ? ACCEL_LINEMB_ROBUST : ACCEL_LINEMB_FAST; // only once there are records
+  if (s->device->mb_bounds == "linear") A.kind = robust ? ACCEL_LINEMB_LINEAR_ROBUST : ACCEL_LINEMB_LINEAR_FAST;
+  A.robust = robust ? 1 : 0;
 }
 
 // world2local = inverse(local2world), both as the columns vx, vy, vz, p: inverted in double precision and rounded once to fp32
@@ -795,6 +888,7 @@ void Scene::commit()
   build_quadmb_accel(this);
   build_subdiv_accel(this);
   build_line_accel(this);
+  build_linemb_accel(this);
   build_instance_accel(this);
   build_instance_subdiv_accel(this);
   for (Accel* a : accels()) a->upload(device);
@@ -816,6 +910,9 @@ void Scene::commit()
   if (lineAccel.kind != ACCEL_NONE && device->verbose >= 2)
     fprintf(stderr, "embree3-amd: line accel kind %u: %zu nodes (%zu B), %zu segments (%zu B), depth %u\n", lineAccel.kind, lineAccel.nodes.size(),
             lineAccel.nodes.size() * sizeof(QNode8), lineAccel.blobs.size() / sizeof(LineRecord), lineAccel.blobs.size(), lineAccel.maxDepth);
+  if (lineMBAccel.kind != ACCEL_NONE && device->verbose >= 2)
+    fprintf(stderr, "embree3-amd: motion blur line accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", lineMBAccel.kind, lineMBAccel.nodeCount(),
+            lineMBAccel.nodeCount() * lineMBAccel.nodeStride(), lineMBAccel.blobs.size() / sizeof(LineMBRecord), lineMBAccel.blobs.size(), lineMBAccel.maxDepth);
   if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
   {
     // the record counts of the layout (build_instance_accel).  Below the kinds ACCEL_INSTMESHMB_* "instanced quads" has always counted

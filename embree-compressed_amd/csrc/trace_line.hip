@@ -9,6 +9,7 @@
 // One arithmetic serves the robust and the fast accel; only the node test differs.
 // A ray exactly parallel to a segment's axis has d1 == 0 and takes its u from 0 * inf, as in the reference.
 #include "trace_leaf.hip.h"
+#include "trace_line.hip.h"
 
 namespace rtamd {
 namespace dev {
@@ -17,67 +18,6 @@ namespace dev {
 #ifndef LINE_FETCH
 #define LINE_FETCH 4
 #endif
-
-// ray_space = frame(s * dir).transposed() (common/math/linearspace3.h:126-133) as its three rows, and the depth scale s
-struct LineSpace
-{
-  float dxx, dxy, dxz; // dx
-  float dyx, dyy, dyz; // dy
-  float nx, ny, nz;    // N = s * dir
-  float s;
-};
-
-// Vec3fa dot (vec3fa.h:289: dpps), normalize = a * rsqrt(dot(a, a)), cross = msub(a0, b0, a1 * b1) shuffled (vec3fa.h:298-305);
-// rsqrt is 1 / sqrt, both correctly rounded
-__device__ __forceinline__ float dot3_plain(float ax, float ay, float az, float bx, float by, float bz) { return ax * bx + ay * by + az * bz; }
-
-__device__ __forceinline__ LineSpace line_space(const RayState& r)
-{
-  LineSpace S;
-  S.s = 1.0f / sqrtf(dot3_plain(r.dx, r.dy, r.dz, r.dx, r.dy, r.dz));
-  S.nx = S.s * r.dx; S.ny = S.s * r.dy; S.nz = S.s * r.dz;
-  // dx0 = (0, N.z, -N.y), dx1 = (-N.z, 0, N.x): the longer one, normalized
-  const float l0 = dot3_plain(0.0f, S.nz, -S.ny, 0.0f, S.nz, -S.ny);
-  const float l1 = dot3_plain(-S.nz, 0.0f, S.nx, -S.nz, 0.0f, S.nx);
-  const bool first = l0 > l1;
-  const float ax = first ? 0.0f : -S.nz, ay = first ? S.nz : 0.0f, az = first ? -S.ny : S.nx;
-  const float ra = 1.0f / sqrtf(dot3_plain(ax, ay, az, ax, ay, az));
-  S.dxx = ax * ra; S.dxy = ay * ra; S.dxz = az * ra;
-  // dy = normalize(cross(N, dx))
-  const float cx = msub(S.ny, S.dxz, S.nz * S.dxy), cy = msub(S.nz, S.dxx, S.nx * S.dxz), cz = msub(S.nx, S.dxy, S.ny * S.dxx);
-  const float rc = 1.0f / sqrtf(dot3_plain(cx, cy, cz, cx, cy, cz));
-  S.dyx = cx * rc; S.dyy = cy * rc; S.dyz = cz * rc;
-  return S;
-}
-
-// LineIntersector1::intersect on one record: V0 = (v0.xyz, r0), V1 = (v1.xyz, r1).  xfmVector(ray_space, a) = madd(a.x, vx, madd(a.y, vy,
-// a.z * vz)) with the transposed frame's columns, i.e. per component dot3(a, row) in the order of vec3.h:193.
-__device__ __forceinline__ bool line_test(const RayState& r, const LineSpace& S, const float4 V0, const float4 V1, float tfarBlock, TriHit& h)
-{
-  const float a0x = V0.x - r.ox, a0y = V0.y - r.oy, a0z = V0.z - r.oz;
-  const float a1x = V1.x - r.ox, a1y = V1.y - r.oy, a1z = V1.z - r.oz;
-  const float p0x = dot3(a0x, a0y, a0z, S.dxx, S.dxy, S.dxz), p0y = dot3(a0x, a0y, a0z, S.dyx, S.dyy, S.dyz), p0z = dot3(a0x, a0y, a0z, S.nx, S.ny, S.nz);
-  const float p1x = dot3(a1x, a1y, a1z, S.dxx, S.dxy, S.dxz), p1y = dot3(a1x, a1y, a1z, S.dyx, S.dyy, S.dyz), p1z = dot3(a1x, a1y, a1z, S.nx, S.ny, S.nz);
-  // approximative intersection with cone
-  const float vx = p1x - p0x, vy = p1y - p0y, vz = p1z - p0z, vw = V1.w - V0.w;
-  const float wx = -p0x, wy = -p0y;
-  const float d0 = madd(wx, vx, wy * vy);
-  const float d1 = madd(vx, vx, vy * vy);
-  const float u = fminf(fmaxf(d0 * (1.0f / d1), 0.0f), 1.0f);
-  const float px = madd(u, vx, p0x), py = madd(u, vy, p0y), pz = madd(u, vz, p0z), pw = madd(u, vw, V0.w);
-  const float t = pz * S.s;
-  const float d2 = madd(px, px, py * py);
-  const float r2 = pw * pw;
-  h.t = t;
-  if (!((d2 <= r2) & (r.tnear < t) & (t <= tfarBlock))) return false;
-  if (!(t > r.tnear + 2.0f * pw * S.s)) return false; // ignore self intersections
-  // ignore denormalized segments
-  const float Tx = V1.x - V0.x, Ty = V1.y - V0.y, Tz = V1.z - V0.z;
-  if (!((Tx != 0.0f) | (Ty != 0.0f) | (Tz != 0.0f))) return false;
-  h.u = u; h.v = 0.0f;
-  h.ngx = Tx; h.ngy = Ty; h.ngz = Tz;
-  return true;
-}
 
 struct LineLeaf : LeafTraits
 {
@@ -120,6 +60,8 @@ struct LineLeaf : LeafTraits
         }
         continue;
       }
+      // (line_octet_winner of trace_line.hip.h is this selection; written out here because the counted twins of this leaf do not stay the
+      // same instructions with the helper)
       const float tq = quad_min4(ok ? h.t : RT_INF); // the minimum of this lane's own block
       const float tqm = dpp_f32<DPP_HALF_MIRROR>(tq); // and of the other one
       const float tA = k < 4u ? tq : tqm, tB = k < 4u ? tqm : tq;

@@ -64,6 +64,12 @@ ACCEL_INSTTOP_LINEAR_MOELLER = 33
 # scenes' BVH8s lead the node buffer, the top-level tree of time-dependent nodes is its second section; blobOffsets has four words
 ACCEL_INSTSUBDIV_TOP_LINEAR_GRID = 34
 ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF = 35
+# line segments with time steps (Scene.add_lines_mb): 80-byte records, one per segment and time segment; robust / fast traversal, and the
+# same over time-dependent nodes under mb_bounds=linear (144-byte nodes)
+ACCEL_LINEMB_ROBUST = 38
+ACCEL_LINEMB_FAST = 39
+ACCEL_LINEMB_LINEAR_ROBUST = 40
+ACCEL_LINEMB_LINEAR_FAST = 41
 # Scene.accel_data(kind + ACCEL_DATA_INSTSUBDIV): the arrays of that second instance accel, whatever else the scene holds
 ACCEL_DATA_INSTSUBDIV = 16
 RTC_SCENE_FLAG_NONE = 0
@@ -424,6 +430,37 @@ class Scene:
             gid = geom_id
         L.rtcReleaseGeometry(g)
         self.device.check("add_lines")
+        return gid
+
+    def add_lines_mb(self, verts4_per_step, first_index, geom_id=None, flags=None):
+        """Motion-blur line segments: verts4_per_step is a sequence of N >= 2 float32 [nv,4] arrays = (x, y, z, radius) per time step
+        (vertex buffer slots 0..N-1 after rtcSetGeometryTimeStepCount), first_index uint32 [ns] and flags as in add_lines; shared buffers
+        like add_lines."""
+        L = self.lib
+        steps = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 4) for v in verts4_per_step]
+        idx = np.ascontiguousarray(first_index, dtype=np.uint32).reshape(-1)
+        g = L.rtcNewGeometry(self.device.handle, RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE)
+        self.device.check("rtcNewGeometry(FLAT_LINEAR_CURVE)")
+        L.rtcSetGeometryTimeStepCount(g, len(steps))
+        for slot, v in enumerate(steps):
+            vpad = np.zeros((v.shape[0] + 1, 4), dtype=np.float32)
+            vpad[: v.shape[0]] = v
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_VERTEX, slot, RTC_FORMAT_FLOAT4, vpad.ctypes.data, 0, 16, v.shape[0])
+            self._keep.append(vpad)
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_INDEX, 0, RTC_FORMAT_UINT, idx.ctypes.data, 0, 4, idx.shape[0])
+        self._keep.append(idx)
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_FLAGS, 0, RTC_FORMAT_UCHAR, fl.ctypes.data, 0, 1, fl.shape[0])
+            self._keep.append(fl)
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self.device.check("add_lines_mb")
         return gid
 
     def add_quads_mb(self, verts_per_step, quads, geom_id=None):

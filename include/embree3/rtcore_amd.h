@@ -78,10 +78,13 @@ struct RTCAMDSceneStats
                                under the device config inst_subdiv_bounds=linear (default swept; independent of inst_bounds): the
                                instanced scenes' 96-byte nodes lead the buffer (nodeCount / nodeBytes), the top-level tree of 144-byte
                                time-dependent nodes follows from a multiple of 144 bytes on; rtcamdGetAccelData(scene, 3) returns four
-                               words - leaf blobs, index of the first blob, 144-byte nodes, index of the first one in 144-byte units */
+                               words - leaf blobs, index of the first blob, 144-byte nodes, index of the first one in 144-byte units,
+                               36 / 37 line segments (robust / fast traversal; 48-byte records),
+                               38 / 39 motion blur line segments (robust / fast traversal; 80-byte records, one per segment and time
+                               segment), 40 / 41 the same over time-dependent node boxes (mb_bounds=linear; nodeBytes is 144 there) */
   unsigned int branching;   /* 8 */
   size_t nodeCount;         /* quantized BVH8 nodes */
-  size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29) */
+  size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29 and 40 / 41) */
   size_t primCount;         /* triangles, quads, or cBVH / GridSOA leaves */
   size_t primBytes;         /* bytes per triangle record (48), per quad record (64) or mean bytes per subdiv leaf blob */
   size_t leafCount;         /* BVH8 leaves */

@@ -10,6 +10,7 @@
 //                            or QuadMBRecord[] (128-byte motion-blur quad records, leaf-contiguous) for quad meshes with time steps,
 //                            or LineRecord[] (48-byte line segment records, leaf-contiguous) for flat linear curves,
 //                            or LineMBRecord[] (80-byte motion-blur line segment records, leaf-contiguous) for flat linear curves with time steps,
+//                            or CurveRecord[] (80-byte flat cubic curve records, leaf-contiguous) for flat Bezier and B-spline curves,
 //                            or InstanceRecord[] (64-byte instance records, one per top-level leaf) for instances, followed in
 //                            the kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER by the instanced scenes' QuadRecord[], in the kinds
 //                            ACCEL_INSTMESHMB_* also by InstanceSceneRecord[], TriMBRecord[] and QuadMBRecord[] (see InstanceRecord)
@@ -33,6 +34,7 @@ namespace rtamd {
 // MB quad leaf: the same form, counting QuadMBRecords (one per quad and time segment)
 // line leaf   : the same form, counting LineRecords
 // MB line leaf: the same form, counting LineMBRecords (one per segment and time segment)
+// curve leaf  : the same form, counting CurveRecords (one per curve)
 // subdiv leaf : bits 0..30 = blob index (one blob per leaf, like encodeTypedLeaf(ptr,1) bvh_builder_subdiv.cpp:728)
 static const uint32_t REF_EMPTY = 0xFFFFFFFFu; // no child (reference: BVH::emptyNode, bvh.h:117-132)
 static const uint32_t REF_LEAF = 0x80000000u;
@@ -160,6 +162,24 @@ struct alignas(16) LineMBRecord
   uint32_t numSegments; // S of the geometry
 };
 static_assert(sizeof(LineMBRecord) == 80, "LineMBRecord must be 80 bytes");
+
+// ---- flat cubic curve record, 80 bytes = 5 x dwordx4 -------------------------------------------------------------------
+// One curve of a flat Bezier or B-spline geometry (RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE / _FLAT_BSPLINE_CURVE) as its four NATIVE control
+// points, Bezier ones, with their radii in w: B-spline input is converted at commit (convert(BSplineCurveT, BezierCurveT),
+// kernels/subdiv/bspline_curve.h:180-187), so every curve has four points of its own - control points are shared between curves in the
+// user's buffer only.  N is the geometry's tessellation rate, clamp((int)rate, 1, 16): the leaf cuts the curve into N ribbon quads and
+// has no geometry table to look the rate up in.
+struct alignas(16) CurveRecord
+{
+  float v0x, v0y, v0z, r0;
+  float v1x, v1y, v1z, r1;
+  float v2x, v2y, v2z, r2;
+  float v3x, v3y, v3z, r3;
+  uint32_t geomID, primID;
+  uint32_t N;   // ribbon quads per curve, 1..16
+  uint32_t pad;
+};
+static_assert(sizeof(CurveRecord) == 80, "CurveRecord must be 80 bytes");
 
 // ---- motion-blur triangle record, 96 bytes = 6 x dwordx4 -------------------------------------------------------------
 // The three vertices of a triangle at both ends of ONE time segment of its mesh (a0..c0 at step `segment`, a1..c1 at step `segment` + 1).
@@ -486,8 +506,14 @@ enum AccelKind : uint32_t
   ACCEL_LINEMB_FAST = 39,
   // the same under mb_bounds=linear: QNodeMB8[] in `nodes`, 144-byte stride, as the kinds 26..29
   ACCEL_LINEMB_LINEAR_ROBUST = 40,
-  ACCEL_LINEMB_LINEAR_FAST = 41
+  ACCEL_LINEMB_LINEAR_FAST = 41,
+  // flat Bezier and B-spline curves (Scene::curveAccel, hair_accel=default / bvh4.bezier1v / ...): CurveRecord[] in `blobs`, one leaf
+  // arithmetic (the ribbon intersector); robust traversal for RTC_SCENE_FLAG_ROBUST scenes, fast traversal otherwise.  Neither instance nor
+  // motion-blur kinds; lane kernel only (lane and octet form), no pool form and no service kernel.
+  ACCEL_CURVE_ROBUST = 42,
+  ACCEL_CURVE_FAST = 43
 };
+inline bool is_curve_kind(uint32_t kind) { return kind == ACCEL_CURVE_ROBUST || kind == ACCEL_CURVE_FAST; } // traced by trace_curve.hip: lane kernel only
 inline bool is_line_kind(uint32_t kind) { return kind == ACCEL_LINE_ROBUST || kind == ACCEL_LINE_FAST; } // traced by trace_line.hip: lane and pool kernels, no service kernel
 inline bool is_inst_linear_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_LINEAR_PLUECKER || kind == ACCEL_INSTMESHMB_LINEAR_MOELLER; } // traced by trace_instance_mesh_mb_linear.hip
 inline bool is_inst_top_linear_kind(uint32_t kind) { return kind == ACCEL_INSTTOP_LINEAR_PLUECKER || kind == ACCEL_INSTTOP_LINEAR_MOELLER; } // traced by trace_instance_top_linear.hip
@@ -521,7 +547,7 @@ struct AccelDesc
 {
   const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_*
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the LineRecord[] of a line accel, or the TriMBRecord[] / QuadMBRecord[] / LineMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the LineRecord[] of a line accel, or the CurveRecord[] of a curve accel, or the TriMBRecord[] / QuadMBRecord[] / LineMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind
@@ -540,7 +566,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel of a scene: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, lines, motion-blur lines, instances, subdivision instances)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel of a scene: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, curves, lines, motion-blur lines, instances, subdivision instances)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

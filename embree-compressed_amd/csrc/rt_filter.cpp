@@ -24,6 +24,8 @@ namespace rtamd {
 //    by (geomID, primID, bits of t); a ray through the diagonal v1-v3 hits both triangles at one t, and rejecting one rejects both.
 //  * line segments (LineMiIntersector1<4,4,true>) offer one candidate per segment: identified by (geomID, primID) and, as the shared scan
 //    compares it too, the bits of t.  Line segments with time steps (LineMiMBIntersector1) likewise, in a list of their own.
+//  * flat Bezier / B-spline curves (Ribbon1Intersector1 with Intersect1EpilogMU) offer one candidate per ribbon quad, all with the curve's
+//    geomID / primID: identified by (geomID, primID, bits of t), in a list of their own.
 //  * the fork's compressed modes never call a filter: CompressedBVHIntersector1::intersect writes the hit itself and occluded()
 //    is a stub (compressed.h:454-756, no runIntersectionFilter1 anywhere in compressed*.h).  Hits on such an accel are accepted
 //    without a callback, geometry and context filter alike; for any-hit queries the stub pass runs first, unfiltered.
@@ -126,6 +128,9 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
   excl[Scene::QUAD].keyedByT = excl[Scene::QUADMB].keyedByT = excl[Scene::SUBDIV].keyedByT = true;
   excl[Scene::LINE].keyedByT = true; // the line leaf scans with candidate_excluded(), which compares t as well (one candidate per segment and ray: t adds nothing, and takes nothing away)
   excl[Scene::LINEMB].keyedByT = true; // the motion-blur line leaf scans the same way: one record per time segment and a ray sees one segment, so (geomID, primID) names the candidate
+  // the ribbon leaf offers up to N candidates per curve and ray, one per ribbon quad, all with the curve's (geomID, primID): t tells them apart,
+  // so a second quad of a rejected curve can still be found (the retry loop of Intersect1EpilogMU, intersector_epilog.h:488-509)
+  excl[Scene::CURVE].keyedByT = true;
   excl[Scene::INST].keyedByT = excl[Scene::INST].withInst = true; // below a mesh instance: (instance, geomID, primID, bits of t) for every leaf type
   std::vector<uint32_t> next;
   void* dExcl = nullptr;
@@ -224,7 +229,8 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
           const bool onTriMB = geo && geo->type == RTC_GEOMETRY_TYPE_TRIANGLE && geo->timeSteps > 1; // one record per segment, a ray sees one segment: (geomID, primID) names the candidate
           const bool onLine = geo && geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && geo->timeSteps == 1;
           const bool onLineMB = geo && geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && geo->timeSteps > 1;
-          const size_t list = belowMeshInstance ? Scene::INST : onLine ? Scene::LINE : onLineMB ? Scene::LINEMB : onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onQuadMB ? Scene::QUADMB : (onTriMB ? Scene::TRIMB : Scene::TRI)));
+          const bool onCurve = geo && geo->isFlatCubicCurve();
+          const size_t list = belowMeshInstance ? Scene::INST : onCurve ? Scene::CURVE : onLine ? Scene::LINE : onLineMB ? Scene::LINEMB : onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onQuadMB ? Scene::QUADMB : (onTriMB ? Scene::TRIMB : Scene::TRI)));
           excl[list].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb, got.hit.instID[0]});
           next.push_back(i);
         }

@@ -414,6 +414,7 @@ MeshInstances classify_mesh_instances(const Scene* s)
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene with a motion blur accel built under mb_bounds=linear is not supported (instance accels hold swept node boxes: use mb_bounds=swept)");
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
+      if (og->isFlatCubicCurve()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "flat Bezier and B-spline curves inside an instanced scene are not supported");
       const bool mesh = og->type == RTC_GEOMETRY_TYPE_TRIANGLE || (quadsOk && og->type == RTC_GEOMETRY_TYPE_QUAD);
       if (!mesh || (og->timeSteps != 1 && !meshMotionOk)) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
       if (!filtersOk && (og->intersectFilter || og->occludedFilter)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");

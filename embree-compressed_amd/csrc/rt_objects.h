@@ -38,6 +38,8 @@ struct Device : RefCounted
   std::string line_accel = "default"; // flat linear curves: default / bvh8.line4i / bvh4.line4i, all the one BVH8 over LineRecords (build_line_accel raises for any other at commit)
   std::string line_accel_mb = "default"; // flat linear curves with time steps: default / bvh8.line4imb / bvh4.line4imb, all the one BVH8 over LineMBRecords (build_linemb_accel raises for any other at commit)
   bool lineAccelMBNamed = false; // "line_accel_mb=" given (a host-only device builds the motion-blur line accel only then, lines_mb_enabled())
+  std::string hair_accel = "default"; // flat Bezier and B-spline curves: the names of Scene::createHairAccel (default, bvh4.bezier1v, bvh4.bezier1i, bvh4obb.bezier1v, bvh4obb.bezier1i, bvh8obb.bezier1v, bvh8obb.bezier1i), all the one BVH8 over CurveRecords - oriented-box nodes are not built (build_curve_accel raises for any other name at commit)
+  bool hairAccelNamed = false; // "hair_accel=" given (a host-only device takes the flat cubic curve types only then, curves_enabled())
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel, rt_instance_build.cpp, raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
   bool quadAccelMBNamed = false; // "quad_accel_mb=" given (a host-only device builds the motion-blur quad accel only then, quads_mb_enabled())
@@ -226,6 +228,9 @@ struct Device : RefCounted
   // Line segments with time steps, the same rule with the key line_accel_mb=: a host-only device without it raises "motion blur of line
   // segments is not supported" at commit, as before the motion-blur line accel existed.
   bool lines_mb_enabled() const { return gpu >= 0 || lineAccelMBNamed; }
+  // Flat Bezier and B-spline curves, the same rule with the key hair_accel=: a host-only device without it refuses the two types at
+  // rtcNewGeometry ("RTC_GEOMETRY_TYPE_*_CURVE not supported"), as before the curve accel existed.
+  bool curves_enabled() const { return gpu >= 0 || hairAccelNamed; }
   // Quad meshes inside an instanced scene, the same rule with the key inst_accel=: a host-only device without it refuses them at the top
   // scene's commit, as before the instance accel took quads.
   bool inst_quads_enabled() const { return gpu >= 0 || instAccelNamed; }
@@ -344,6 +349,13 @@ struct Geometry : RefCounted
   size_t numSegments() const { return numTriangles(); } // index buffer records (UINT)
   unsigned segment(size_t i) const;
   bool validSegment(size_t i, unsigned slot = 0) const; // LineSegments::valid(i, itime): against the vertex buffer of time step `slot`
+  // flat cubic curve accessors (reference: NativeCurves, kernels/common/scene_bezier_curves.h): curve i uses the vertices index[i] ..
+  // index[i] + 3 = (x, y, z, radius), control points of the geometry's own basis
+  bool isFlatCubicCurve() const { return type == RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE || type == RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE; }
+  size_t numCurves() const { return numTriangles(); } // index buffer records (UINT)
+  bool validCurve(size_t i) const;                    // NativeCurves::valid (scene_bezier_curves.h:193-218)
+  unsigned curveRate() const;                         // NativeCurves::setTessellationRate: clamp((int)rate, 1, 16)
+  void nativeCurve(size_t i, float out[16]) const;    // the four Bezier control points of curve i (B-spline input converted in float32)
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -408,7 +420,7 @@ struct Scene : RefCounted
   // filter callbacks present at commit time (Scene::hasGeometryFilterFunction, scene.h): they route a batch through the
   // host filter loop of rt_filter.cpp (the tri* flags cover quad meshes too)
   bool triIntersectFilter = false, triOccludedFilter = false, subdivFilter = false;
-  bool lineIntersectFilter = false, lineOccludedFilter = false; // the same for flat linear curves (reported with the meshes' flags)
+  bool lineIntersectFilter = false, lineOccludedFilter = false; // the same for flat linear and flat cubic curves (reported with the meshes' flags)
   // the same for what lies below this scene's mesh instances (inst_filters=1; build_instance_accel, at this scene's commit): an enabled
   // geometry with an intersect / occluded filter in the scene of a placed instance
   bool instIntersectFilter = false, instOccludedFilter = false;
@@ -422,13 +434,14 @@ struct Scene : RefCounted
   Accel quadAccel;   // quads with one time step (QuadRecord[] in `blobs`); traced after the triangles, before the motion-blur quads
   Accel quadMBAccel; // quads with several time steps (QuadMBRecord[] in `blobs`); traced after the static quads, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
+  Accel curveAccel;  // flat Bezier and B-spline curves (CurveRecord[] in `blobs`); traced after the subdivision patches and before the line segments (scene.cpp:654-658: createSubdivAccel, createHairAccel, createLineAccel)
   Accel lineAccel;   // flat linear curves (LineRecord[] in `blobs`); traced after the subdivision patches, before the instances (scene.cpp:650-663)
   Accel lineMBAccel; // flat linear curves with several time steps (LineMBRecord[] in `blobs`); traced right after the static lines (scene.cpp: createLineAccel, createLineMBAccel)
   Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle and quad trees behind the top-level tree); traced last (scene.cpp:661-665)
   Accel instSubdivAccel; // instances of scenes that hold subdivision meshes only (InstanceRecord[] and the instanced scenes' leaf blobs in `blobs`, their BVH8s behind the top-level tree); traced after the mesh instances
-  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / LINE / LINEMB / INST / INSTSUBDIV index whatever a path keeps per accel
-  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, LINE = 5, LINEMB = 6, INST = 7, INSTSUBDIV = 8, NUM_ACCELS = 9 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &lineAccel, &lineMBAccel, &instAccel, &instSubdivAccel}; }
+  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / CURVE / LINE / LINEMB / INST / INSTSUBDIV index whatever a path keeps per accel
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, CURVE = 5, LINE = 6, LINEMB = 7, INST = 8, INSTSUBDIV = 9, NUM_ACCELS = 10 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &curveAccel, &lineAccel, &lineMBAccel, &instAccel, &instSubdivAccel}; }
   bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
   // records the layout of instAccel placed in `blobs` behind the InstanceRecords, as build_instance_accel counted them (host only: the
   // verbose line of commit prints them)

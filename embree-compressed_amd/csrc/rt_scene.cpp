@@ -11,7 +11,11 @@
 namespace rtamd {
 
 // ---- Geometry -------------------------------------------------------------------------------------------
-Geometry::Geometry(Device* d, RTCGeometryType t) : device(d), type(t) { device->retain(); }
+Geometry::Geometry(Device* d, RTCGeometryType t) : device(d), type(t)
+{
+  if (isFlatCubicCurve()) tessellationRate = 4.0f; // NativeCurves (scene_bezier_curves.cpp:28)
+  device->retain();
+}
 
 Geometry::~Geometry()
 {
@@ -58,7 +62,7 @@ void Geometry::bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size
 {
   // argument checks follow rtcSetGeometryBuffer (rtcore.cpp:1236-1290) and TriangleMesh::setBuffer
   // (scene_triangle_mesh.cpp): 4-byte aligned offset/stride, matching formats per slot type.
-  const bool lineFlags = type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && t == RTC_BUFFER_TYPE_FLAGS; // bytes (scene_line_segments.cpp:63)
+  const bool lineFlags = (type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE || isFlatCubicCurve()) && t == RTC_BUFFER_TYPE_FLAGS; // bytes (scene_line_segments.cpp:63, scene_bezier_curves.cpp:63)
   if (!lineFlags && ((off & 3) || (stride & 3))) RT_THROW(RTC_ERROR_INVALID_OPERATION, "buffer offset and stride must be 4-byte aligned");
   if (b && off + (count ? (count - 1) * stride + format_bytes(f) : 0) > b->bytes && !b->shared)
     RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "buffer range out of bounds");
@@ -78,6 +82,8 @@ void Geometry::bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size
     if ((t == RTC_BUFFER_TYPE_INDEX || t == RTC_BUFFER_TYPE_FACE) && f != RTC_FORMAT_UINT)
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid index/face buffer format");
     break;
+  case RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE:
+  case RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE: // NativeCurves::setBuffer (scene_bezier_curves.cpp:60-110): the same formats and messages
   case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE: // LineSegments::setBuffer (scene_line_segments.cpp)
     if (t == RTC_BUFFER_TYPE_VERTEX) {
       if (f != RTC_FORMAT_FLOAT4) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid vertex buffer format");
@@ -174,6 +180,50 @@ bool Geometry::validSegment(size_t i, unsigned slot) const
     if (p[3] < 0.0f) return false;
   }
   return true;
+}
+
+// NativeCurves::valid (scene_bezier_curves.h:193-218): index + 3 inside the vertex buffer, all sixteen floats finite, no radius negative
+bool Geometry::validCurve(size_t i) const
+{
+  const BufferView* vv = view(RTC_BUFFER_TYPE_VERTEX, 0);
+  const size_t nv = vv && vv->valid() ? vv->count : 0;
+  const size_t i0 = segment(i);
+  if (i0 + 3 >= nv) return false;
+  for (size_t k = i0; k < i0 + 4; k++) {
+    const float* p = (const float*)vv->at(k);
+    for (int c = 0; c < 4; c++)
+      if (!std::isfinite(p[c]) || fabsf(p[c]) > 1.844e18f) return false; // isvalid: FLT_LARGE
+    if (p[3] < 0.0f) return false;
+  }
+  return true;
+}
+
+unsigned Geometry::curveRate() const
+{
+  const float r = tessellationRate;
+  const int n = r >= 16.0f ? 16 : (r >= 1.0f ? (int)r : 1); // clamp((int)rate, 1, 16); a NaN gives 1
+  return (unsigned)n;
+}
+
+// The native control points of curve i: the user's four for a Bezier geometry, convert(BSplineCurveT, BezierCurveT)
+// (kernels/subdiv/bspline_curve.h:180-187) of them for a B-spline geometry - the reference's madd sequence in float32 on all four
+// components, the radius included (Vec3fa arithmetic works on the whole register).
+void Geometry::nativeCurve(size_t i, float out[16]) const
+{
+  const BufferView* vv = view(RTC_BUFFER_TYPE_VERTEX, 0);
+  const size_t i0 = segment(i);
+  const float *a = (const float*)vv->at(i0), *b = (const float*)vv->at(i0 + 1), *c = (const float*)vv->at(i0 + 2), *d = (const float*)vv->at(i0 + 3);
+  if (type != RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE) {
+    memcpy(out, a, 16); memcpy(out + 4, b, 16); memcpy(out + 8, c, 16); memcpy(out + 12, d, 16);
+    return;
+  }
+  const float s6 = 1.0f / 6.0f, s3 = 1.0f / 3.0f, t3 = 2.0f / 3.0f;
+  for (int k = 0; k < 4; k++) {
+    out[k] = fmaf(s6, a[k], fmaf(t3, b[k], s6 * c[k]));
+    out[4 + k] = fmaf(t3, b[k], s3 * c[k]);
+    out[8 + k] = fmaf(s3, b[k], t3 * c[k]);
+    out[12 + k] = fmaf(s6, b[k], fmaf(t3, c[k], s6 * d[k]));
+  }
 }
 
 // ---- Accel -------------------------------------------------------------------------------------------------
@@ -493,6 +543,115 @@ static void build_line_accel(Scene* s)
   A.robust = s->isRobust() ? 1 : 0;
   A.blobStride = sizeof(LineRecord);
   A.blobs.resize(recs.size() * sizeof(LineRecord));
+  memcpy(A.blobs.data(), recs.data(), A.blobs.size());
+}
+
+// BezierBasis::eval (kernels/subdiv/bezier_curve.h:27-37) in float32, the products in the reference's order
+static void bezier_basis_eval(float u, float B[4])
+{
+  const float t1 = u, t0 = 1.0f - t1;
+  B[0] = t0 * t0 * t0;
+  B[1] = 3.0f * t1 * (t0 * t0);
+  B[2] = 3.0f * (t1 * t1) * t0;
+  B[3] = t1 * t1 * t1;
+}
+
+// BezierCurve3fa::tessellatedBounds(N) (bezier_curve.h:298-331) in float32: the N tessellation points eval0(j, N), j = 0 .. N - 1 - the
+// nested madd over the basis at float(j) / float(N) - and v3, enlarged on every side by the largest |radius| among them.
+// Containment.  The leaf cuts the curve into the N quads between the points P_j = eval(float(j) / float(N)), j = 0 .. N, all four
+// components with this very arithmetic (P_N: the basis at 1 is (0, 0, 0, 1), so the madd chain returns v3 itself, bit for bit).  The
+// corners of quad j are P_j -+ w_j n_j and P_j+1 -+ w_j+1 n_j+1 with unit normals n (the normal is formed in ray space, which is an
+// isometry of the x / y plane and keeps world distances).  So every corner lies within |w| of a point of this box's core, the box of
+// P_0 .. P_N, and the enlargement by max |w_j| covers it; a quad is the convex hull of its corners and a box is convex.  In float32
+// the leaf's corners carry the roundings of the ray-space transform, at most a few ulp of the coordinates: far inside the quantizer's
+// one-step padding (accel.h QNode8), the argument of every other leaf.
+static Box3 curve_tessellated_bounds(const float cp[16], unsigned N)
+{
+  Box3 b;
+  float rmax = 0.0f;
+  for (unsigned j = 0; j <= N; j++) {
+    float p[4];
+    if (j < N) {
+      float B[4];
+      bezier_basis_eval((float)j / (float)N, B);
+      for (int c = 0; c < 4; c++) p[c] = fmaf(B[0], cp[c], fmaf(B[1], cp[4 + c], fmaf(B[2], cp[8 + c], B[3] * cp[12 + c])));
+    } else
+      memcpy(p, cp + 12, 16);
+    b.extend(V3(p[0], p[1], p[2]));
+    rmax = std::max(rmax, fabsf(p[3]));
+  }
+  Box3 e;
+  e.extend(V3(b.lo.x - rmax, b.lo.y - rmax, b.lo.z - rmax));
+  e.extend(V3(b.hi.x + rmax, b.hi.y + rmax, b.hi.z + rmax));
+  return e;
+}
+
+// Flat Bezier and B-spline curves (Scene::createHairAccel, scene.cpp:370-416): one BVH8 with the line accel's builder settings over the
+// valid curves of the scene's enabled flat cubic curve geometries, CurveRecords in `blobs`.  Every name the reference accepts builds
+// this accel; its oriented-box nodes (bvh4obb / bvh8obb) are not built.  The reference has one ribbon intersector, so the kind only
+// tells the traversal: robust for a robust scene, fast otherwise.
+static void build_curve_accel(Scene* s)
+{
+  Accel& A = s->curveAccel;
+  A.clear();
+  if (!s->device->curves_enabled()) return; // (no curve geometry can exist on such a device)
+  const std::string& name = s->device->hair_accel;
+  if (name != "default" && name != "bvh4.bezier1v" && name != "bvh4.bezier1i" && name != "bvh4obb.bezier1v" && name != "bvh4obb.bezier1i" && name != "bvh8obb.bezier1v" &&
+      name != "bvh8obb.bezier1i")
+    RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown hair acceleration structure " + name);
+
+  struct Src { unsigned geomID, primID; };
+  std::vector<Src> src;
+  std::vector<BuildPrim> bp;
+  for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
+    Geometry* g = s->geometries[gid];
+    if (!g || !g->enabled || !g->isFlatCubicCurve()) continue;
+    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur of flat Bezier and B-spline curves is not supported");
+    const unsigned N = g->curveRate();
+    const size_t n = g->numCurves();
+    for (size_t i = 0; i < n; i++) {
+      if (!g->validCurve(i)) continue;
+      float cp[16];
+      g->nativeCurve(i, cp);
+      BuildPrim p;
+      p.box = curve_tessellated_bounds(cp, N);
+      p.id = (uint32_t)src.size();
+      src.push_back({gid, (unsigned)i});
+      bp.push_back(p);
+    }
+  }
+  if (bp.empty()) return;
+  if (bp.size() >= ((size_t)1 << TRI_START_BITS)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "too many curves for the 26-bit leaf reference");
+
+  std::vector<CurveRecord> recs;
+  recs.reserve(bp.size());
+  auto makeLeaf = [&](const BuildPrim* prims, size_t begin, size_t end) -> uint32_t {
+    const uint32_t first = (uint32_t)recs.size();
+    for (size_t i = begin; i < end; i++) {
+      const Src& sr = src[prims[i].id];
+      const Geometry* g = s->geometries[sr.geomID];
+      CurveRecord r;
+      memset(&r, 0, sizeof(r));
+      g->nativeCurve(sr.primID, &r.v0x);
+      r.geomID = sr.geomID;
+      r.primID = sr.primID;
+      r.N = g->curveRate();
+      recs.push_back(r);
+    }
+    return make_tri_leaf(first, (uint32_t)(end - begin));
+  };
+  BuildSettings cfg;
+  cfg.threads = host_threads(s->device);
+  BuildResult r = build_bvh8(bp, cfg, makeLeaf);
+  A.nodes = std::move(r.nodes);
+  A.root = r.root;
+  A.maxDepth = r.maxDepth;
+  A.leafCount = r.leafCount;
+  for (const BuildPrim& p : bp) s->bounds.extend(p.box);
+  A.kind = s->isRobust() ? ACCEL_CURVE_ROBUST : ACCEL_CURVE_FAST; // only once there are curves
+  A.robust = s->isRobust() ? 1 : 0;
+  A.blobStride = sizeof(CurveRecord);
+  A.blobs.resize(recs.size() * sizeof(CurveRecord));
   memcpy(A.blobs.data(), recs.data(), A.blobs.size());
 }
 
@@ -862,6 +1021,8 @@ void Scene::commit()
     case RTC_GEOMETRY_TYPE_QUAD:
     case RTC_GEOMETRY_TYPE_SUBDIVISION:
     case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE:
+    case RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE:
+    case RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE:
     case RTC_GEOMETRY_TYPE_INSTANCE: break;
     default: // scene.cpp:25-30: geometry types compiled out raise INVALID_OPERATION
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry type not supported by the MI355X traversal path");
@@ -874,7 +1035,7 @@ void Scene::commit()
     if (geo->type == RTC_GEOMETRY_TYPE_TRIANGLE || geo->type == RTC_GEOMETRY_TYPE_QUAD) {
       triIntersectFilter |= geo->intersectFilter != nullptr;
       triOccludedFilter |= geo->occludedFilter != nullptr;
-    } else if (geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE) {
+    } else if (geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE || geo->isFlatCubicCurve()) {
       lineIntersectFilter |= geo->intersectFilter != nullptr;
       lineOccludedFilter |= geo->occludedFilter != nullptr;
     } else if (geo->type == RTC_GEOMETRY_TYPE_SUBDIVISION)
@@ -887,6 +1048,7 @@ void Scene::commit()
   build_quad_accel(this);
   build_quadmb_accel(this);
   build_subdiv_accel(this);
+  build_curve_accel(this);
   build_line_accel(this);
   build_linemb_accel(this);
   build_instance_accel(this);
@@ -907,6 +1069,9 @@ void Scene::commit()
       fprintf(stderr, "embree3-amd: motion blur quad accel kind %u: %zu nodes (%zu B), %zu segment records (%zu B), depth %u\n", quadMBAccel.kind, quadMBAccel.nodeCount(),
               quadMBAccel.nodeCount() * quadMBAccel.nodeStride(), quadMBAccel.blobs.size() / sizeof(QuadMBRecord), quadMBAccel.blobs.size(), quadMBAccel.maxDepth);
   }
+  if (curveAccel.kind != ACCEL_NONE && device->verbose >= 2)
+    fprintf(stderr, "embree3-amd: curve accel kind %u: %zu nodes (%zu B), %zu curves (%zu B), depth %u\n", curveAccel.kind, curveAccel.nodes.size(),
+            curveAccel.nodes.size() * sizeof(QNode8), curveAccel.blobs.size() / sizeof(CurveRecord), curveAccel.blobs.size(), curveAccel.maxDepth);
   if (lineAccel.kind != ACCEL_NONE && device->verbose >= 2)
     fprintf(stderr, "embree3-amd: line accel kind %u: %zu nodes (%zu B), %zu segments (%zu B), depth %u\n", lineAccel.kind, lineAccel.nodes.size(),
             lineAccel.nodes.size() * sizeof(QNode8), lineAccel.blobs.size() / sizeof(LineRecord), lineAccel.blobs.size(), lineAccel.maxDepth);

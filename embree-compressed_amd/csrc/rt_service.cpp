@@ -118,6 +118,7 @@ static bool service_trace(Scene* s, char* rays, uint32_t M, size_t byteStride, b
   if (is_mb_mesh_kind(A.kind)) return false; // no service kernel for motion blur (triangles, quads, line segments): the combiner traces these calls with the batch kernels
   if (is_instance_kind(A.kind)) return false; // nor for instances (trace_instance.hip)
   if (is_line_kind(A.kind)) return false; // nor for line segments (trace_line.hip)
+  if (is_curve_kind(A.kind)) return false; // nor for flat cubic curves (trace_curve.hip)
   const uint32_t worst = 7u * (A.maxDepth + 1u) + 2u;
   const uint32_t need = worst > (uint32_t)TRACE_LDS_STACK ? worst - TRACE_LDS_STACK : 0u;
   if (need > Device::Service::SPILL_DEPTH) return false;

@@ -70,6 +70,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   p.poolKernel = dev->tunePoolKernel == 2u ? (poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel;
   if (is_mb_mesh_kind(A.kind))
     p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip, trace_line_mb.hip), under swept and under linear bounds
+  if (is_curve_kind(A.kind)) p.poolKernel = 0u; // the ribbon leaf exists in the lane kernel only (trace_curve.hip)
   const bool instKernel = is_instance_kind(A.kind);
   if (instKernel) p.poolKernel = 0u; // the two-level kernel is a lane-per-ray kernel of its own (trace_instance.hip, trace_instance_subdiv.hip and their linear forms): no pool form, no root cull pre-pass
   // worst-case stack: 7 siblings per level plus the entry being expanded.  The overflow area is sized for it, so a push
@@ -145,8 +146,8 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   p.survivors = nullptr;
   // (never on the kinds of mb_bounds=linear: the pre-pass decodes a QNode8 root, and a root of time-dependent boxes would have to be
   // culled per ray time)
-  // (nor on the line accels, static and motion blur: launch_cull derives the node test from the mesh kinds)
-  if (dev->tuneCull && !p.poolKernel && !instKernel && !is_mb_linear_kind(A.kind) && !is_line_kind(A.kind) && !is_line_mb_kind(A.kind) && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
+  // (nor on the line accels, static and motion blur, and the curve accel: launch_cull derives the node test from the mesh kinds)
+  if (dev->tuneCull && !p.poolKernel && !instKernel && !is_mb_linear_kind(A.kind) && !is_line_kind(A.kind) && !is_line_mb_kind(A.kind) && !is_curve_kind(A.kind) && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
     const size_t need = ((size_t)(M + TRACE_QUEUES - 1) / TRACE_QUEUES) * TRACE_QUEUES * 4u;
     if (need > ctx.survivorsBytes) { // first batch of this size on this context (an allocation synchronises the device)
       HIP_CHECK(hipStreamSynchronize(stream));
@@ -305,7 +306,7 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
   const bool subdivFilters = s->subdivFilter && s->subdivAccel.kind == ACCEL_GRIDSOA;
   // (instIntersectFilter / instOccludedFilter: filters below mesh instances, set only under inst_filters=1)
   const bool instFilters = occluded ? s->instOccludedFilter : s->instIntersectFilter;
-  const bool lineFilters = occluded ? s->lineOccludedFilter : s->lineIntersectFilter; // static and moving line geometries
+  const bool lineFilters = occluded ? s->lineOccludedFilter : s->lineIntersectFilter; // static and moving line geometries, flat cubic curves
   if (!countersOut && ((ctx && ctx->filter) || subdivFilters || instFilters || lineFilters || (occluded ? s->triOccludedFilter : s->triIntersectFilter))) {
     trace_filtered(s, rays, M, byteStride, occluded, ctx);
     return;

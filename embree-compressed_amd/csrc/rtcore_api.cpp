@@ -87,7 +87,7 @@ API ssize_t rtcGetDeviceProperty(RTCDevice h, enum RTCDeviceProperty prop)
   case RTC_DEVICE_PROPERTY_TRIANGLE_GEOMETRY_SUPPORTED: return 1;
   case RTC_DEVICE_PROPERTY_QUAD_GEOMETRY_SUPPORTED: return D(h)->quads_enabled() ? 1 : 0;
   case RTC_DEVICE_PROPERTY_SUBDIVISION_GEOMETRY_SUPPORTED: return 1;
-  case RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED: return 0; // speaks for all five curve types: only RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE is taken
+  case RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED: return 0; // speaks for all five curve types: the flat ones are taken, the round ones are not
   case RTC_DEVICE_PROPERTY_USER_GEOMETRY_SUPPORTED: return 0;
   case RTC_DEVICE_PROPERTY_TASKING_SYSTEM: return 0; // "internal"
   case RTC_DEVICE_PROPERTY_JOIN_COMMIT_SUPPORTED: return 1;
@@ -161,10 +161,12 @@ API RTCGeometry rtcNewGeometry(RTCDevice h, enum RTCGeometryType type)
   case RTC_GEOMETRY_TYPE_INSTANCE: return (RTCGeometry) new Geometry(D(h), type); // every device, host-only ones included
   case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE: return (RTCGeometry) new Geometry(D(h), type); // line segments (trace_line.hip): every device, host-only ones included
   case RTC_GEOMETRY_TYPE_USER: unsupported("RTC_GEOMETRY_TYPE_USER");
-  case RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE:
   case RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE:
-  case RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE:
-  case RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE: unsupported("RTC_GEOMETRY_TYPE_*_CURVE");
+  case RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE: // ribbon curves (trace_curve.hip): a host-only device takes them only when its config names hair_accel=
+    if (!D(h)->curves_enabled()) unsupported("RTC_GEOMETRY_TYPE_*_CURVE");
+    return (RTCGeometry) new Geometry(D(h), type);
+  case RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE:
+  case RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE: unsupported("RTC_GEOMETRY_TYPE_*_CURVE");
   default: RT_THROW(RTC_ERROR_UNKNOWN, "invalid geometry type");
   }
   CATCH_END(D(h))
@@ -435,6 +437,7 @@ API void rtcInterpolate(const struct RTCInterpolateArguments* args)
   if (g->type == RTC_GEOMETRY_TYPE_TRIANGLE) interpolate_triangles(g, args);
   else if (g->type == RTC_GEOMETRY_TYPE_QUAD) interpolate_quads(g, args);
   else if (g->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE) interpolate_lines(g, args);
+  else if (g->isFlatCubicCurve()) interpolate_curves(g, args);
   else if (g->type == RTC_GEOMETRY_TYPE_SUBDIVISION) interpolate_subdiv(g, args);
   else unsupported("rtcInterpolate on this geometry type");
   CATCH_END(args && args->geometry ? devOf(args->geometry) : nullptr)
@@ -832,9 +835,13 @@ API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 // is described when the scene has neither a subdivision nor a mesh accel, in front of the instance accels; the motion-blur line accel
 // right behind it, when the scene holds nothing in front of it (no static lines either).  In full, first match: lines, motion-blur
 // lines (both only without subdivision and mesh accels), subdivision instances alone, subdivision, motion-blur triangles, quads,
-// motion-blur quads, mesh instances, triangles.
+// motion-blur quads, mesh instances, triangles.  The curve accel (flat Bezier / B-spline curves) stands in front of all of these, under the
+// lines' condition: no subdivision and no mesh accel.
 static const Accel& exported_accel(const Scene* s)
 {
+  if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
+      s->quadMBAccel.kind == ACCEL_NONE && s->curveAccel.kind != ACCEL_NONE)
+    return s->curveAccel;
   if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
       s->quadMBAccel.kind == ACCEL_NONE && s->lineAccel.kind != ACCEL_NONE)
     return s->lineAccel;

@@ -1018,6 +1018,42 @@ void interpolate_lines(const Geometry* geom, const RTCInterpolateArguments* args
   }
 }
 
+// Flat Bezier and B-spline curves (NativeCurvesISA::interpolate_helper, scene_bezier_curves.cpp:241-281, with BezierCurveT / BSplineCurveT
+// by the geometry's own type, :339-357): the four values at index[primID] .. + 3 of the USER's buffer under the basis of the geometry's
+// type - eval, eval_du, eval_dudu = madd(b.x, v0, madd(b.y, v1, madd(b.z, v2, b.w * v3))) with BezierBasis (bezier_curve.h:27-61) or
+// BSplineBasis2 (bspline_curve.h:28-62).  v plays no part; the derivatives in v are not written by the reference and are zero here.
+void interpolate_curves(const Geometry* geom, const RTCInterpolateArguments* args)
+{
+  const BufferView* src = geom->view(args->bufferType, args->bufferSlot);
+  if (!src || !src->valid()) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: buffer slot is not bound");
+  if (args->primID >= geom->numCurves()) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: invalid primID");
+  const size_t i0 = geom->segment(args->primID);
+  if (i0 + 3 >= src->count) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: curve index out of range");
+  const float t = args->u, s = 1.0f - t;
+  float b[4], d[4], dd[4];
+  if (geom->type == RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE) {
+    const float n1 = (4.0f * (s * s * s) + (t * t * t)) + (12.0f * ((s * t) * s) + 6.0f * ((t * s) * t));
+    const float n2 = (4.0f * (t * t * t) + (s * s * s)) + (12.0f * ((t * s) * t) + 6.0f * ((s * t) * s));
+    const float sixth = 1.0f / 6.0f;
+    b[0] = sixth * (s * s * s); b[1] = sixth * n1; b[2] = sixth * n2; b[3] = sixth * (t * t * t);
+    d[0] = 0.5f * (-s * s); d[1] = 0.5f * (-t * t - 4.0f * (t * s)); d[2] = 0.5f * (s * s + 4.0f * (s * t)); d[3] = 0.5f * (t * t);
+    dd[0] = s; dd[1] = t - 2.0f * s; dd[2] = s - 2.0f * t; dd[3] = t;
+  } else {
+    b[0] = s * s * s; b[1] = 3.0f * t * (s * s); b[2] = 3.0f * (t * t) * s; b[3] = t * t * t;
+    d[0] = 3.0f * -(s * s); d[1] = 3.0f * fmaf(-2.0f, s * t, s * s); d[2] = 3.0f * fmaf(2.0f, s * t, -(t * t)); d[3] = 3.0f * (t * t);
+    dd[0] = 6.0f * s; dd[1] = 6.0f * fmaf(-2.0f, s, t); dd[2] = 6.0f * fmaf(-2.0f, t, s); dd[3] = 6.0f * t;
+  }
+  for (unsigned i = 0; i < args->valueCount; i++) {
+    const float p0 = ((const float*)src->at(i0))[i], p1 = ((const float*)src->at(i0 + 1))[i], p2 = ((const float*)src->at(i0 + 2))[i], p3 = ((const float*)src->at(i0 + 3))[i];
+    if (args->P) args->P[i] = fmaf(b[0], p0, fmaf(b[1], p1, fmaf(b[2], p2, b[3] * p3)));
+    if (args->dPdu) args->dPdu[i] = fmaf(d[0], p0, fmaf(d[1], p1, fmaf(d[2], p2, d[3] * p3)));
+    if (args->dPdv) args->dPdv[i] = 0.f;
+    if (args->ddPdudu) args->ddPdudu[i] = fmaf(dd[0], p0, fmaf(dd[1], p1, fmaf(dd[2], p2, dd[3] * p3)));
+    if (args->ddPdvdv) args->ddPdvdv[i] = 0.f;
+    if (args->ddPdudv) args->ddPdudv[i] = 0.f;
+  }
+}
+
 // Subdivision meshes: Catmull-Clark limit surface of any vertex / vertex-attribute buffer at (primID, u, v).
 // The reference evaluates through patch classification, bicubic B-spline patches, feature-adaptive subdivision and
 // Gregory patches (scene_subdiv_mesh.cpp:757-864, patch_eval.h).  Here the buffer is refined K = 3 times with the

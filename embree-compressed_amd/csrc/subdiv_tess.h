@@ -38,6 +38,7 @@ void tessellate_subdiv(const Geometry* geom, unsigned geomID, unsigned L, std::v
 void interpolate_triangles(const Geometry* geom, const RTCInterpolateArguments* args);
 void interpolate_quads(const Geometry* geom, const RTCInterpolateArguments* args);
 void interpolate_lines(const Geometry* geom, const RTCInterpolateArguments* args);
+void interpolate_curves(const Geometry* geom, const RTCInterpolateArguments* args);
 void interpolate_subdiv(Geometry* geom, const RTCInterpolateArguments* args);
 
 } // namespace rtamd

@@ -19,6 +19,8 @@ RTC_GEOMETRY_TYPE_TRIANGLE = 0
 RTC_GEOMETRY_TYPE_QUAD = 1
 RTC_GEOMETRY_TYPE_SUBDIVISION = 8
 RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE = 17
+RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE = 25
+RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE = 33
 RTC_GEOMETRY_TYPE_INSTANCE = 121
 RTC_BUFFER_TYPE_INDEX = 0
 RTC_BUFFER_TYPE_VERTEX = 1
@@ -70,6 +72,9 @@ ACCEL_LINEMB_ROBUST = 38
 ACCEL_LINEMB_FAST = 39
 ACCEL_LINEMB_LINEAR_ROBUST = 40
 ACCEL_LINEMB_LINEAR_FAST = 41
+# flat Bezier / B-spline curves (Scene.add_curves): 80-byte records, one per curve, with the geometry's tessellation rate; robust / fast traversal
+ACCEL_CURVE_ROBUST = 42
+ACCEL_CURVE_FAST = 43
 # Scene.accel_data(kind + ACCEL_DATA_INSTSUBDIV): the arrays of that second instance accel, whatever else the scene holds
 ACCEL_DATA_INSTSUBDIV = 16
 RTC_SCENE_FLAG_NONE = 0
@@ -430,6 +435,40 @@ class Scene:
             gid = geom_id
         L.rtcReleaseGeometry(g)
         self.device.check("add_lines")
+        return gid
+
+    def add_curves(self, verts4, first_index, basis="bezier", tessellation_rate=None, geom_id=None, flags=None):
+        """Flat cubic curves, ribbons (RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE for basis="bezier", RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE for
+        basis="bspline"): verts4 float32 [nv,4] = (x, y, z, radius) control points of that basis, first_index uint32 [nc]: curve i uses the
+        vertices first_index[i] .. first_index[i] + 3; tessellation_rate: rtcSetGeometryTessellationRate (ribbon quads per curve, clamped to
+        1..16 at commit; None keeps the default 4); flags optional uint8 [nc] (kept, no effect); shared buffers padded like add_lines."""
+        L = self.lib
+        types = {"bezier": RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE, "bspline": RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE}
+        if basis not in types:
+            raise ValueError("add_curves: basis must be 'bezier' or 'bspline'")
+        v = np.ascontiguousarray(verts4, dtype=np.float32).reshape(-1, 4)
+        vpad = np.zeros((v.shape[0] + 1, 4), dtype=np.float32)
+        vpad[: v.shape[0]] = v
+        idx = np.ascontiguousarray(first_index, dtype=np.uint32).reshape(-1)
+        g = L.rtcNewGeometry(self.device.handle, types[basis])
+        self.device.check("rtcNewGeometry(FLAT_%s_CURVE)" % basis.upper())
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_VERTEX, 0, RTC_FORMAT_FLOAT4, vpad.ctypes.data, 0, 16, v.shape[0])
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_INDEX, 0, RTC_FORMAT_UINT, idx.ctypes.data, 0, 4, idx.shape[0])
+        self._keep += [vpad, idx]
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_FLAGS, 0, RTC_FORMAT_UCHAR, fl.ctypes.data, 0, 1, fl.shape[0])
+            self._keep.append(fl)
+        if tessellation_rate is not None:
+            L.rtcSetGeometryTessellationRate(g, float(tessellation_rate))
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self.device.check("add_curves")
         return gid
 
     def add_lines_mb(self, verts4_per_step, first_index, geom_id=None, flags=None):

@@ -81,7 +81,9 @@ struct RTCAMDSceneStats
                                words - leaf blobs, index of the first blob, 144-byte nodes, index of the first one in 144-byte units,
                                36 / 37 line segments (robust / fast traversal; 48-byte records),
                                38 / 39 motion blur line segments (robust / fast traversal; 80-byte records, one per segment and time
-                               segment), 40 / 41 the same over time-dependent node boxes (mb_bounds=linear; nodeBytes is 144 there) */
+                               segment), 40 / 41 the same over time-dependent node boxes (mb_bounds=linear; nodeBytes is 144 there),
+                               42 / 43 flat Bezier and B-spline curves (robust / fast traversal; 80-byte records: the four Bezier
+                               control points with their radii, geomID, primID and the tessellation rate of the curve's geometry) */
   unsigned int branching;   /* 8 */
   size_t nodeCount;         /* quantized BVH8 nodes */
   size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29 and 40 / 41) */

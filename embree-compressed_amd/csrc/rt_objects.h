@@ -330,15 +330,28 @@ struct Geometry : RefCounted
   Geometry(Device* d, RTCGeometryType t);
   ~Geometry() override;
 
-  BufferView* view(RTCBufferType t, unsigned slot);
-  const BufferView* view(RTCBufferType t, unsigned slot) const;
+  // (view, vertex and segment are defined here: the builders of other files read every primitive through them)
+  BufferView* view(RTCBufferType t, unsigned slot)
+  {
+    auto it = views.find({(int)t, slot});
+    return it == views.end() ? nullptr : &it->second;
+  }
+  const BufferView* view(RTCBufferType t, unsigned slot) const
+  {
+    auto it = views.find({(int)t, slot});
+    return it == views.end() ? nullptr : &it->second;
+  }
   void bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size_t off, size_t stride, size_t count);
 
   // triangle mesh accessors (reference: TriangleMesh, kernels/common/scene_triangle_mesh.h)
   size_t numTriangles() const;
   size_t numVertices() const;
   void triangle(size_t i, unsigned idx[3]) const;
-  V3 vertex(size_t i, unsigned slot = 0) const; // slot = time step
+  V3 vertex(size_t i, unsigned slot = 0) const // slot = time step
+  {
+    const float* p = (const float*)view(RTC_BUFFER_TYPE_VERTEX, slot)->at(i);
+    return V3(p[0], p[1], p[2]);
+  }
   bool validTriangle(size_t i, unsigned slot = 0) const;
   // quad mesh accessors (reference: QuadMesh, kernels/common/scene_quad_mesh.h)
   size_t numQuads() const { return numTriangles(); } // index buffer records (UINT4 for quads)
@@ -347,7 +360,7 @@ struct Geometry : RefCounted
   // flat linear curve accessors (reference: LineSegments, kernels/common/scene_line_segments.h): segment i runs from vertex
   // index[i] to vertex index[i] + 1; vertices are (x, y, z, radius)
   size_t numSegments() const { return numTriangles(); } // index buffer records (UINT)
-  unsigned segment(size_t i) const;
+  unsigned segment(size_t i) const { return *(const unsigned*)view(RTC_BUFFER_TYPE_INDEX, 0)->at(i); }
   bool validSegment(size_t i, unsigned slot = 0) const; // LineSegments::valid(i, itime): against the vertex buffer of time step `slot`
   // flat cubic curve accessors (reference: NativeCurves, kernels/common/scene_bezier_curves.h): curve i uses the vertices index[i] ..
   // index[i] + 3 = (x, y, z, radius), control points of the geometry's own basis
@@ -462,6 +475,16 @@ struct Scene : RefCounted
 // affine maps as the columns vx, vy, vz, p (rt_scene.cpp): the inverse, false for a singular map; xfmPoint
 bool invert_affine(const float* m, float* out);
 V3 xfm_point(const float* m, V3 q);
+
+// the seven primitive accels of a scene (rt_prim_build.cpp), in Scene::commit's order (build_subdiv_accel, subdiv_build.h, runs between
+// the quads and the curves): where a scene has several faults, the order decides which refusal is reported
+void build_triangle_accel(Scene* s);
+void build_trimb_accel(Scene* s);
+void build_quad_accel(Scene* s);
+void build_quadmb_accel(Scene* s);
+void build_curve_accel(Scene* s);
+void build_line_accel(Scene* s);
+void build_linemb_accel(Scene* s);
 
 // the two instance accels of a scene (rt_instance_build.cpp), in Scene::commit's order: the second relies on the first having refused
 // instances without a committed scene

@@ -829,33 +829,13 @@ API void rtcamdSynchronizeDevice(RTCDevice h)
 
 API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 
-// the accel the inspection calls describe: the subdivision accel if there is one, else the triangle accel, else the motion-blur triangle
-// accel, else the quad accel, else (a scene of nothing but quads with time steps) the motion-blur quad accel, else (a scene of nothing
-// but instances) the instance accel, else (nothing but instances of subdivision scenes) the subdivision instance accel.  The line accel
-// is described when the scene has neither a subdivision nor a mesh accel, in front of the instance accels; the motion-blur line accel
-// right behind it, when the scene holds nothing in front of it (no static lines either).  In full, first match: lines, motion-blur
-// lines (both only without subdivision and mesh accels), subdivision instances alone, subdivision, motion-blur triangles, quads,
-// motion-blur quads, mesh instances, triangles.  The curve accel (flat Bezier / B-spline curves) stands in front of all of these, under the
-// lines' condition: no subdivision and no mesh accel.
+// the accel the inspection calls describe: the first of the scene's accels that is not empty, in the order subdivision, triangles,
+// motion-blur triangles, quads, motion-blur quads, curves, lines, motion-blur lines, mesh instances, subdivision instances; the (empty)
+// triangle accel when all are empty
 static const Accel& exported_accel(const Scene* s)
 {
-  if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
-      s->quadMBAccel.kind == ACCEL_NONE && s->curveAccel.kind != ACCEL_NONE)
-    return s->curveAccel;
-  if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
-      s->quadMBAccel.kind == ACCEL_NONE && s->lineAccel.kind != ACCEL_NONE)
-    return s->lineAccel;
-  if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
-      s->quadMBAccel.kind == ACCEL_NONE && s->lineMBAccel.kind != ACCEL_NONE)
-    return s->lineMBAccel;
-  if (s->subdivAccel.kind == ACCEL_NONE && s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind == ACCEL_NONE && s->quadAccel.kind == ACCEL_NONE &&
-      s->quadMBAccel.kind == ACCEL_NONE && s->instAccel.kind == ACCEL_NONE && s->instSubdivAccel.kind != ACCEL_NONE)
-    return s->instSubdivAccel;
-  if (s->subdivAccel.kind != ACCEL_NONE) return s->subdivAccel;
-  if (s->triAccel.kind == ACCEL_NONE && s->triMBAccel.kind != ACCEL_NONE) return s->triMBAccel;
-  if (s->triAccel.kind == ACCEL_NONE && s->quadAccel.kind != ACCEL_NONE) return s->quadAccel;
-  if (s->triAccel.kind == ACCEL_NONE && s->quadMBAccel.kind != ACCEL_NONE) return s->quadMBAccel;
-  if (s->triAccel.kind == ACCEL_NONE && s->instAccel.kind != ACCEL_NONE) return s->instAccel;
+  for (const Accel* a : {&s->subdivAccel, &s->triAccel, &s->triMBAccel, &s->quadAccel, &s->quadMBAccel, &s->curveAccel, &s->lineAccel, &s->lineMBAccel, &s->instAccel, &s->instSubdivAccel})
+    if (a->kind != ACCEL_NONE) return *a;
   return s->triAccel;
 }
 

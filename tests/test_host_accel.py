@@ -201,6 +201,43 @@ def test_invalid_triangles_are_skipped(rtc):
     dev.release()
 
 
+def test_inspection_calls_describe_the_first_accel_in_priority_order(rtc):
+    """rtcamdGetSceneStats describes the first non-empty accel in the order triangles, motion-blur triangles, quads, motion-blur quads,
+    curves, lines, motion-blur lines: every single type, every pair of them (added in both orders) and all seven in one scene."""
+    tri = (np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), np.array([[0, 1, 2]], np.uint32))
+    quad = (np.array([[0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]], np.float32), np.array([[0, 1, 2, 3]], np.uint32))
+    pts = (np.array([[0, 0, 2, 0.1], [1, 0, 2, 0.1], [1, 1, 2, 0.1], [0, 1, 2, 0.1]], np.float32), np.array([0], np.uint32))
+    steps = lambda v: [v, v + np.float32(0.5)]  # noqa: E731
+    # in priority order: (kind of a default, non-robust scene, how to add one primitive of the type)
+    table = [
+        (2, lambda sc: sc.add_triangles(*tri)),
+        (11, lambda sc: sc.add_triangles_mb(steps(tri[0]), tri[1])),
+        (9, lambda sc: sc.add_quads(*quad)),
+        (13, lambda sc: sc.add_quads_mb(steps(quad[0]), quad[1])),
+        (43, lambda sc: sc.add_curves(*pts)),
+        (37, lambda sc: sc.add_lines(*pts)),
+        (39, lambda sc: sc.add_lines_mb(steps(pts[0]), pts[1])),
+    ]
+    dev = rtc.Device("gpu=none,quad_accel=default,quad_accel_mb=default,tri_accel_mb=default,line_accel_mb=default,hair_accel=default")
+
+    def kind_of(entries):
+        sc = rtc.Scene(dev)
+        for _, add in entries:
+            add(sc)
+        sc.commit()
+        kind = sc.stats()["accelKind"]
+        sc.release()
+        return kind
+
+    assert kind_of([]) == 0
+    for i, a in enumerate(table):
+        assert kind_of([a]) == a[0]
+        for b in table[i + 1:]:
+            assert kind_of([a, b]) == a[0] and kind_of([b, a]) == a[0], (a[0], b[0])
+    assert kind_of(table[::-1]) == table[0][0]
+    dev.release()
+
+
 def test_host_pool_of_the_staging_pipeline(rtc):
     """The pool of staging threads behind the chunked pipeline of large host-pointer batches (rt_device.cpp HostPool: helpers that
     poll a ticket word while a batch runs, the caller works too) through its test hook on a gpu=none device: every part of every job

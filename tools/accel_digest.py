@@ -1,8 +1,11 @@
-"""Development check, CPU only: digest of what the two instance builders (csrc/rt_instance_build.cpp) make of a fixed list of host-only
-scenes.  One line per case: accel kind, root, every field of rtcamdGetSceneStats, rtcGetSceneBounds, and a SHA-256 per exported array
-(rtcamdGetAccelData 0..3 and 16..19); one line per refusal: error code and the full message; and the verbose=2 lines of one scene each of
+"""Development check, CPU only: digest of what the seven primitive builders (csrc/rt_prim_build.cpp: triangles, quads, curves and lines,
+static and with time steps) and the two instance builders (csrc/rt_instance_build.cpp) make of a fixed list of host-only scenes.  One line
+per case: accel kind, root, every field of rtcamdGetSceneStats, rtcGetSceneBounds, and a SHA-256 per exported array (rtcamdGetAccelData
+0..3 and 16..19); one line per refusal: error code and the full message; and the verbose=2 lines of one scene per record accel and of
 the kinds 21, 23, 25 and 31 (printed by a child process, which this tool starts).  Run it once per library build (RTAMD_LIB=...) and
-`diff` the listings: no difference = byte-identical accels, the same refusals.  The scenes come from the helper modules of tests/.
+`diff` the listings: no difference = byte-identical accels, the same refusals.  The primitive scenes are generated here (sizes around the
+leaf limits, skipped primitives, gaps in the geometry IDs, mixed time-step counts, every pair of types, recommits); the instance scenes
+come from the helper modules of tests/.
 usage: accel_digest.py > listing"""
 import ctypes as C
 import hashlib
@@ -370,8 +373,267 @@ def refusals():
             lambda dev: over(dev, [subdiv_inner(dev, beside=quad), subdiv_inner(dev, filt=keep_fn)]))
 
 
+# ---- the primitive builders: triangles, quads, curves, lines; static and with time steps ------------------------------------------------------
+PRIM_KEYS = dict(quad_accel='default', quad_accel_mb='default', tri_accel_mb='default', line_accel_mb='default', hair_accel='default')
+# type -> (device key, the names its builder accepts, moving)
+PRIM_TYPES = {
+    'tri': ('tri_accel', ('default', 'bvh8.triangle4v', 'bvh4.triangle4v', 'bvh8.triangle4', 'bvh4.triangle4', 'qbvh8.triangle4'), False),
+    'trimb': ('tri_accel_mb', ('default', 'bvh8.triangle4imb', 'bvh4.triangle4imb', 'bvh8.triangle4vmb', 'bvh4.triangle4vmb'), True),
+    'quad': ('quad_accel', ('default', 'bvh8.quad4v', 'bvh4.quad4v', 'bvh8.quad4i', 'bvh4.quad4i', 'qbvh8.quad4i'), False),
+    'quadmb': ('quad_accel_mb', ('default', 'bvh8.quad4imb', 'bvh4.quad4imb'), True),
+    'curve': ('hair_accel', ('default', 'bvh4.bezier1v', 'bvh4.bezier1i', 'bvh4obb.bezier1v', 'bvh4obb.bezier1i', 'bvh8obb.bezier1v', 'bvh8obb.bezier1i'), False),
+    'line': ('line_accel', ('default', 'bvh8.line4i', 'bvh4.line4i'), False),
+    'linemb': ('line_accel_mb', ('default', 'bvh8.line4imb', 'bvh4.line4imb'), True),
+}
+SIZES = (1, 4, 5, 29, 300)  # the root is a leaf; a full block; one over it; one over the largest leaf; several levels
+FLAGS = (rtc.RTC_SCENE_FLAG_NONE, rtc.RTC_SCENE_FLAG_ROBUST)
+
+
+def prim_cfg(*extra, **keys):
+    """a host-only device config that names every key a host-only device needs, `keys` replacing the defaults"""
+    k = dict(PRIM_KEYS, **keys)
+    return ','.join(['gpu=none'] + ['%s=%s' % kv for kv in k.items()] + list(extra))
+
+
+def prim_gen(typ, n, seed, steps=2):
+    """(vertices, index) of n primitives of a type; vertices of a moving type: one array per time step (the radius moves too)"""
+    rng = np.random.RandomState(1000 + seed)
+    base = typ.replace('mb', '')
+    if base == 'tri':
+        v, idx = random_soup(n, seed)
+    elif base == 'quad':
+        v, idx = random_quads(n, seed)
+    else:
+        k = 2 if base == 'line' else 4
+        c = rng.rand(n, 1, 3) * 10.0
+        v = np.concatenate([c + (rng.rand(n, k, 3) - 0.5), 0.01 + 0.2 * rng.rand(n, k, 1)], 2).reshape(-1, 4).astype(np.float32)
+        idx = np.arange(0, k * n, k, dtype=np.uint32)
+    if not PRIM_TYPES[typ][2]:
+        return v, idx
+    shift = np.zeros(v.shape[1], np.float32)
+    shift[:3] = rng.rand(3) * 0.5
+    if v.shape[1] == 4:
+        shift[3] = 0.03
+    return [(v + s * shift * (1.0 + 0.25 * s)).astype(np.float32) for s in range(steps)], idx
+
+
+def prim_put(sc, typ, v, idx, geom_id=None, **kw):
+    add = {'tri': sc.add_triangles, 'trimb': sc.add_triangles_mb, 'quad': sc.add_quads, 'quadmb': sc.add_quads_mb, 'curve': sc.add_curves, 'line': sc.add_lines,
+           'linemb': sc.add_lines_mb}[typ]
+    return add(v, idx, geom_id=geom_id, **kw)
+
+
+def prim_scene(label, cfg, parts, flags=0, after=None):
+    """parts: [(type, vertices, index, keywords of the add call)]; after(scene): further set-up in front of the commit"""
+    dev = rtc.Device(cfg)
+    sc = rtc.Scene(dev, flags)
+    for typ, v, idx, kw in parts:
+        prim_put(sc, typ, v, idx, **kw)
+    if after:
+        after(sc)
+    sc.commit()
+    digest('%s [%s] flags %d' % (label, cfg, flags), sc)
+    return dev, sc
+
+
+def prim_case(label, cfg, parts, flags=0, after=None):
+    dev, sc = prim_scene(label, cfg, parts, flags, after)
+    sc.release()
+    dev.release()
+
+
+def bounds_modes(typ):
+    return ((), ('mb_bounds=linear',)) if PRIM_TYPES[typ][2] else ((),)
+
+
+def prim_size_cases():
+    for typ, (key, names, moving) in PRIM_TYPES.items():
+        for name in names:
+            for extra in bounds_modes(typ):
+                for n in SIZES:
+                    for flags in FLAGS:
+                        v, idx = prim_gen(typ, n, n, steps=3 if n == 29 else 2)
+                        prim_case('%s: %d primitives' % (typ, n), prim_cfg(*extra, **{key: name}), [(typ, v, idx, {})], flags)
+
+
+def prim_skipped_cases():
+    """12 primitives: 1 has a NaN coordinate, 3 the first index that reaches past the vertex buffer, 4 an index far outside, 5 a value above
+    FLT_LARGE, 7 (lines, curves) a negative radius, and with time steps 9 is invalid at the middle step 1 of four only"""
+    for typ, (key, names, moving) in PRIM_TYPES.items():
+        v, idx = prim_gen(typ, 12, 77, steps=4)
+        idx = idx.copy()
+        steps = v if moving else [v]
+        per = len(steps[0]) // 12  # vertices per primitive
+        nv = len(steps[0])
+        for s, a in enumerate(steps):
+            a[1 * per, 1] = np.nan
+            a[5 * per + per - 1, 2] = 1.0e19
+            if a.shape[1] == 4:
+                a[7 * per, 3] = -0.01
+            if moving and s == 1:
+                a[9 * per, 0] = np.inf
+        if idx.ndim == 2:
+            idx[3, 1] = nv
+            idx[4, 2] = nv + 1000
+        else:
+            idx[3] = nv - per + 1
+            idx[4] = nv + 1000
+        for extra in bounds_modes(typ):
+            for flags in FLAGS:
+                prim_case('%s: skipped primitives' % typ, prim_cfg(*extra), [(typ, v, idx, {})], flags)
+
+
+def prim_shape_cases():
+    for typ, (key, names, moving) in PRIM_TYPES.items():
+        static = typ.replace('mb', '') if typ != 'curve' else 'curve'
+        for extra in bounds_modes(typ):
+            def some(n, seed, gid, steps=2, t=typ):
+                v, idx = prim_gen(t, n, seed, steps)
+                return (t, v, idx, dict(geom_id=gid))
+            ev, eidx = prim_gen(typ, 3, 5)
+            empty = (typ, ev, eidx[:0], dict(geom_id=6))
+            # gaps in the IDs, a disabled geometry (ID 2), a geometry without primitives (ID 6)
+            prim_case('%s: gaps, disabled, empty' % typ, prim_cfg(*extra), [some(9, 1, 1), some(7, 2, 2), some(40, 3, 4), empty, some(5, 4, 9)],
+                      after=lambda sc: sc.set_enabled(2, False))
+            prim_case('%s: nothing but a disabled and an empty geometry' % typ, prim_cfg(*extra), [some(7, 2, 2), empty], after=lambda sc: sc.set_enabled(2, False))
+            if moving:
+                # time-step counts 2, 3 and 5 under interleaved IDs, alone and with static geometries of the type in between
+                mixed = [some(11, 1, 0, 2), some(13, 2, 2, 3), some(17, 3, 5, 5)]
+                prim_case('%s: time steps 2, 3, 5' % typ, prim_cfg(*extra), mixed)
+                prim_case('%s: time steps 2, 3, 5 between static geometries' % typ, prim_cfg(*extra), mixed + [some(6, 4, 1, t=static), some(8, 5, 3, t=static)])
+    # Bezier beside B-spline, tessellation rates 1, 4, 16 and NaN (and what the clamp makes of others)
+    rates = (1, 4, 16, float('nan'), 0.5, 7.9, 100, None)
+    both = []
+    for i, rate in enumerate(rates):
+        for j, basis in enumerate(('bezier', 'bspline')):
+            v, idx = prim_gen('curve', 9 + i, 10 * i + j)
+            kw = dict(basis=basis, tessellation_rate=rate)
+            prim_case('curve: %s, tessellation rate %s' % (basis, rate), prim_cfg(), [('curve', v, idx, kw)])
+            both.append(('curve', v, idx, dict(kw, geom_id=3 * len(both) + 1)))
+    for flags in FLAGS:
+        prim_case('curve: Bezier beside B-spline, all rates', prim_cfg(), both, flags)
+
+
+def prim_exported_cases():
+    """what the inspection calls describe: every pair of the seven types, and all of them"""
+    types = list(PRIM_TYPES)
+    part = {t: (t,) + prim_gen(t, 6 + i, 20 + i) + ({},) for i, t in enumerate(types)}
+    for i, a in enumerate(types):
+        for b in types[i + 1:]:
+            prim_case('exported: %s + %s' % (a, b), prim_cfg(), [part[b], part[a]])
+    for extra in ((), ('mb_bounds=linear',)):
+        prim_case('exported: all seven types', prim_cfg(*extra), [part[t] for t in reversed(types)])
+
+
+def prim_recommit_cases():
+    """commit; disable the type's geometry (its accel becomes empty), commit; enable it and move a vertex, commit: alone in the scene and beside
+    a geometry of the type behind it in the order of the inspection calls"""
+    types = list(PRIM_TYPES)
+    for i, typ in enumerate(types):
+        for other in (None, types[(i + 1) % len(types)]):
+            v, idx = prim_gen(typ, 33, 40 + i, steps=3)
+            parts = [(typ, v, idx, dict(geom_id=0))]
+            if other:
+                parts.append((other,) + prim_gen(other, 10, 50 + i) + (dict(geom_id=1),))
+            label = 'recommit: %s%s' % (typ, ' beside ' + other if other else '')
+            dev, sc = prim_scene(label + ', first commit', prim_cfg(), parts)
+            sc.set_enabled(0, False)
+            sc.commit()
+            digest(label + ', disabled', sc)
+            sc._keep[0][0, :3] += 25.0  # the first vertex of geometry 0 (at its first time step), in the shared buffer the geometry reads in place
+            sc.set_enabled(0, True)
+            sc.commit()
+            digest(label + ', enabled and changed', sc)
+            sc.release()
+            dev.release()
+
+
+def raw_geometry(sc, gtype, steps, vertex, index, bound_steps=None, fmt=None):
+    """a geometry with `steps` time steps of which only the first `bound_steps` get a vertex buffer (the wrappers of rtc.py always bind all)"""
+    L, dev = sc.lib, sc.device
+    g = L.rtcNewGeometry(dev.handle, gtype)
+    dev.check('rtcNewGeometry')
+    L.rtcSetGeometryTimeStepCount(g, steps)
+    wide = vertex.shape[1] == 4
+    for slot in range(steps if bound_steps is None else bound_steps):
+        vpad = np.zeros((vertex.shape[0] + 2, vertex.shape[1]), np.float32)
+        vpad[:vertex.shape[0]] = vertex + np.float32(0.25 * slot)
+        L.rtcSetSharedGeometryBuffer(g, rtc.RTC_BUFFER_TYPE_VERTEX, slot, rtc.RTC_FORMAT_FLOAT4 if wide else rtc.RTC_FORMAT_FLOAT3, vpad.ctypes.data, 0, 4 * vertex.shape[1],
+                                     vertex.shape[0])
+        sc._keep.append(vpad)
+    idx = np.ascontiguousarray(index, np.uint32)
+    L.rtcSetSharedGeometryBuffer(g, rtc.RTC_BUFFER_TYPE_INDEX, 0, fmt, idx.ctypes.data, 0, idx.itemsize * (idx.shape[1] if idx.ndim == 2 else 1), idx.shape[0])
+    sc._keep.append(idx)
+    L.rtcCommitGeometry(g)
+    L.rtcAttachGeometry(sc.handle, g)
+    L.rtcReleaseGeometry(g)
+    dev.check('raw_geometry')
+
+
+def prim_refusals():
+    def scene(*types, raw=()):
+        def make(dev):
+            sc = rtc.Scene(dev)
+            for i, t in enumerate(types):
+                prim_put(sc, t, *prim_gen(t, 6, 60 + i))
+            for r in raw:
+                r(sc)
+            return sc, []
+        return make
+
+    def curves_with_steps(sc):
+        v, idx = prim_gen('curve', 5, 70)
+        raw_geometry(sc, rtc.RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE, 2, v, idx, fmt=rtc.RTC_FORMAT_UINT)
+
+    def step_without_buffer(typ):
+        gtype, fmt = {'trimb': (rtc.RTC_GEOMETRY_TYPE_TRIANGLE, rtc.RTC_FORMAT_UINT3), 'quadmb': (rtc.RTC_GEOMETRY_TYPE_QUAD, rtc.RTC_FORMAT_UINT4),
+                      'linemb': (rtc.RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE, rtc.RTC_FORMAT_UINT)}[typ]
+        v, idx = prim_gen(typ.replace('mb', ''), 5, 71)
+        return lambda sc: raw_geometry(sc, gtype, 3, v, idx, bound_steps=2, fmt=fmt)
+
+    bad = 'bvh7.nonsense'
+    for typ, (key, names, moving) in PRIM_TYPES.items():
+        refusal('unknown %s' % key, prim_cfg(**{key: bad}), scene(typ))
+        refusal('unknown %s, no geometry of the type' % key, prim_cfg(**{key: bad}), scene('tri' if typ != 'tri' else 'quad'))
+    # time steps on a device that lacks the key
+    refusal('quads with time steps, no quad_accel_mb', 'gpu=none,quad_accel=default', scene('quadmb'))
+    refusal('lines with time steps, no line_accel_mb', 'gpu=none', scene('linemb'))
+    refusal('lines with time steps beside static lines, no line_accel_mb', 'gpu=none,hair_accel=default', scene('line', 'linemb'))
+    refusal('curves with time steps', prim_cfg(), scene('curve', raw=[curves_with_steps]))
+    for typ in ('trimb', 'quadmb', 'linemb'):
+        for extra in bounds_modes(typ):
+            refusal('%s: a time step without a vertex buffer' % typ, prim_cfg(*extra), scene(typ, raw=[step_without_buffer(typ)]))
+    # two faults in one scene: the builder that runs first reports (triangles, motion-blur triangles, quads, motion-blur quads, subdivision,
+    # curves, lines, motion-blur lines)
+    refusal('unknown tri_accel and unknown line_accel', prim_cfg(tri_accel=bad, line_accel=bad + '2'), scene('line', 'tri'))
+    refusal('unknown line_accel_mb and unknown tri_accel_mb', prim_cfg(line_accel_mb=bad, tri_accel_mb=bad + '2'), scene('linemb', 'trimb'))
+    refusal('quad time steps and unknown hair_accel', 'gpu=none,quad_accel=default,hair_accel=' + bad, scene('curve', 'quadmb'))
+    refusal('unknown quad_accel and line time steps', 'gpu=none,quad_accel=' + bad, scene('linemb', 'quad'))
+    refusal('unknown hair_accel and line time steps', 'gpu=none,hair_accel=' + bad, scene('linemb', 'curve'))
+    refusal('curve time steps and unknown line_accel', prim_cfg(line_accel=bad), scene('line', raw=[curves_with_steps]))
+    refusal('line time steps and unknown quad_accel_mb', 'gpu=none,quad_accel_mb=' + bad, scene('quad', 'linemb'))
+    refusal('a time step without a vertex buffer (triangles) and unknown quad_accel', prim_cfg(quad_accel=bad), scene('quad', raw=[step_without_buffer('trimb')]))
+    refusal('unknown tri_accel_mb and a time step without a vertex buffer (lines)', prim_cfg(tri_accel_mb=bad), scene('tri', raw=[step_without_buffer('linemb')]))
+
+
+def prim_verbose_child(typ, linear):
+    prim_case('verbose', prim_cfg('verbose=2', *(['mb_bounds=linear'] if linear else [])), [(typ,) + prim_gen(typ, 50, 9) + ({},)])
+
+
+def prim_cases():
+    prim_size_cases()
+    prim_skipped_cases()
+    prim_shape_cases()
+    prim_exported_cases()
+    prim_recommit_cases()
+    prim_refusals()
+
+
 # ---- the verbose=2 lines ------------------------------------------------------------------------------------------------------------------------
 def verbose_child(kind):
+    if kind.split('+')[0] in PRIM_TYPES:
+        return prim_verbose_child(kind.split('+')[0], kind.endswith('+linear'))
+    kind = int(kind)
     if kind == 25:
         dev, top, inner = isd.build(rtc, isd.LEAF, {'c': isd.cube() + (3, 2)}, placed(4, ('c',), True), SUBDIV + ',verbose=2')
     elif kind == 21:  # (below the kinds 22 / 23 the line's "instanced quads" counts the InstanceSteps too)
@@ -383,16 +645,17 @@ def verbose_child(kind):
 
 
 def verbose_lines():
-    for kind in (21, 23, 25, 31):
+    for kind in list(PRIM_TYPES) + [t + '+linear' for t in PRIM_TYPES if PRIM_TYPES[t][2]] + [21, 23, 25, 31]:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), '--verbose-child', str(kind)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, check=True)
         for line in r.stderr.splitlines():
-            print('verbose=2, kind %d | %s' % (kind, line), flush=True)
+            print('verbose=2, %s | %s' % ('kind %d' % kind if isinstance(kind, int) else kind, line), flush=True)
 
 
 if __name__ == '__main__':
     if len(sys.argv) > 2 and sys.argv[1] == '--verbose-child':
-        verbose_child(int(sys.argv[2]))
+        verbose_child(sys.argv[2])
         sys.exit(0)
+    prim_cases()
     static_and_instance_mb_cases()
     mesh_mb_cases()
     layout_cases()

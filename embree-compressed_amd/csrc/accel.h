@@ -11,6 +11,7 @@
 //                            or LineRecord[] (48-byte line segment records, leaf-contiguous) for flat linear curves,
 //                            or LineMBRecord[] (80-byte motion-blur line segment records, leaf-contiguous) for flat linear curves with time steps,
 //                            or CurveRecord[] (80-byte flat cubic curve records, leaf-contiguous) for flat Bezier and B-spline curves,
+//                            or CurveMBRecord[] (160-byte motion-blur flat cubic curve records, leaf-contiguous) for such curves with time steps,
 //                            or InstanceRecord[] (64-byte instance records, one per top-level leaf) for instances, followed in
 //                            the kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER by the instanced scenes' QuadRecord[], in the kinds
 //                            ACCEL_INSTMESHMB_* also by InstanceSceneRecord[], TriMBRecord[] and QuadMBRecord[] (see InstanceRecord)
@@ -35,6 +36,7 @@ namespace rtamd {
 // line leaf   : the same form, counting LineRecords
 // MB line leaf: the same form, counting LineMBRecords (one per segment and time segment)
 // curve leaf  : the same form, counting CurveRecords (one per curve)
+// MB curve leaf: the same form, counting CurveMBRecords (one per curve and time segment)
 // subdiv leaf : bits 0..30 = blob index (one blob per leaf, like encodeTypedLeaf(ptr,1) bvh_builder_subdiv.cpp:728)
 static const uint32_t REF_EMPTY = 0xFFFFFFFFu; // no child (reference: BVH::emptyNode, bvh.h:117-132)
 static const uint32_t REF_LEAF = 0x80000000u;
@@ -180,6 +182,36 @@ struct alignas(16) CurveRecord
   uint32_t pad;
 };
 static_assert(sizeof(CurveRecord) == 80, "CurveRecord must be 80 bytes");
+
+// ---- motion-blur flat cubic curve record, 160 bytes = 10 x dwordx4 ----------------------------------------------------------
+// One curve of a flat Bezier or B-spline geometry with time steps at both ends of ONE time segment of its geometry: the four native
+// control points with their radii at step `segment` (v0a .. v3a) and at step `segment` + 1 (v0b .. v3b); B-spline input is converted per
+// time step at commit.  Time segments and record selection as for TriMBRecord; the control points are interpolated in ALL FOUR
+// components, the radius included (NativeCurves::gather with a time, scene_bezier_curves.h:138-158), and go through the ribbon test of
+// the static curve leaf.
+// Layout: the plain 160 bytes, not the 144 that packing N (<= 16) and numSegments (<= 128) into one word would give.  The ninth row is
+// word for word the id row of LineMBRecord - geomID, primID, segment, numSegments - so the build frame writes the ids of every
+// motion-blur record type alike, and the leaf decides from this ONE row, read first, whether the record serves the ray's time segment:
+// a record of another segment (S - 1 of S below a leaf under swept boxes) costs one dwordx4 and no unpacking.  N has the tenth row; it
+// is read with the control points.  A leaf reads whole 16-byte rows either way, so 144 bytes would save a row of memory per record but
+// no request on the records that are skipped.
+struct alignas(16) CurveMBRecord
+{
+  float v0ax, v0ay, v0az, r0a;
+  float v1ax, v1ay, v1az, r1a;
+  float v2ax, v2ay, v2az, r2a;
+  float v3ax, v3ay, v3az, r3a;
+  float v0bx, v0by, v0bz, r0b;
+  float v1bx, v1by, v1bz, r1b;
+  float v2bx, v2by, v2bz, r2b;
+  float v3bx, v3by, v3bz, r3b;
+  uint32_t geomID, primID;
+  uint32_t segment;     // itime this record serves
+  uint32_t numSegments; // S of the geometry
+  uint32_t N;           // ribbon quads per curve, 1..16
+  uint32_t pad[3];
+};
+static_assert(sizeof(CurveMBRecord) == 160, "CurveMBRecord must be 160 bytes");
 
 // ---- motion-blur triangle record, 96 bytes = 6 x dwordx4 -------------------------------------------------------------
 // The three vertices of a triangle at both ends of ONE time segment of its mesh (a0..c0 at step `segment`, a1..c1 at step `segment` + 1).
@@ -511,7 +543,15 @@ enum AccelKind : uint32_t
   // arithmetic (the ribbon intersector); robust traversal for RTC_SCENE_FLAG_ROBUST scenes, fast traversal otherwise.  Neither instance nor
   // motion-blur kinds; lane kernel only (lane and octet form), no pool form and no service kernel.
   ACCEL_CURVE_ROBUST = 42,
-  ACCEL_CURVE_FAST = 43
+  ACCEL_CURVE_FAST = 43,
+  // flat Bezier and B-spline curves with time steps (Scene::curveMBAccel, hair_accel_mb=default / bvh4.bezier1imb / bvh8.bezier1imb):
+  // CurveMBRecord[] in `blobs`, the static curve leaf's arithmetic on the interpolated control points; robust / fast traversal as for the
+  // kinds 42 / 43.  Motion-blur kinds (lane kernel only, no service kernel), NOT curve kinds in the sense of is_curve_kind.
+  ACCEL_CURVEMB_ROBUST = 44,
+  ACCEL_CURVEMB_FAST = 45,
+  // the same under mb_bounds=linear: QNodeMB8[] in `nodes`, 144-byte stride, as the kinds 26..29
+  ACCEL_CURVEMB_LINEAR_ROBUST = 46,
+  ACCEL_CURVEMB_LINEAR_FAST = 47
 };
 inline bool is_curve_kind(uint32_t kind) { return kind == ACCEL_CURVE_ROBUST || kind == ACCEL_CURVE_FAST; } // traced by trace_curve.hip: lane kernel only
 inline bool is_line_kind(uint32_t kind) { return kind == ACCEL_LINE_ROBUST || kind == ACCEL_LINE_FAST; } // traced by trace_line.hip: lane and pool kernels, no service kernel
@@ -528,26 +568,29 @@ inline bool is_instance_kind(uint32_t kind) { return (kind >= ACCEL_INST_TRI_PLU
 
 // traced by trace_line_mb.hip: lane kernel only
 inline bool is_line_mb_kind(uint32_t kind) { return kind >= ACCEL_LINEMB_ROBUST && kind <= ACCEL_LINEMB_LINEAR_FAST; }
+// traced by trace_curve_mb.hip: lane kernel only
+inline bool is_curve_mb_kind(uint32_t kind) { return kind >= ACCEL_CURVEMB_ROBUST && kind <= ACCEL_CURVEMB_LINEAR_FAST; }
 // nodes are QNodeMB8: node stride, no root-cull pre-pass.  (The instance builder asks this of the triangle and quad motion-blur accels of
-// an instanced scene only; a scene with a line accel of either kind is refused below an instance before it gets there.)
+// an instanced scene only; a scene with a line or curve accel of either kind is refused below an instance before it gets there.)
 inline bool is_mb_linear_kind(uint32_t kind)
 {
-  return (kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER) || kind == ACCEL_LINEMB_LINEAR_ROBUST || kind == ACCEL_LINEMB_LINEAR_FAST;
+  return (kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER) || kind == ACCEL_LINEMB_LINEAR_ROBUST || kind == ACCEL_LINEMB_LINEAR_FAST ||
+         kind == ACCEL_CURVEMB_LINEAR_ROBUST || kind == ACCEL_CURVEMB_LINEAR_FAST;
 }
 // the arithmetic of a motion-blur mesh accel, under swept and under linear bounds
 inline bool is_mb_pluecker_kind(uint32_t kind)
 {
   return kind == ACCEL_TRIMB_PLUECKER || kind == ACCEL_QUADMB_PLUECKER || kind == ACCEL_TRIMB_LINEAR_PLUECKER || kind == ACCEL_QUADMB_LINEAR_PLUECKER;
 }
-// the motion-blur accels of triangles, quads and line segments, under swept and under linear bounds: lane kernel only, no service kernel
-inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKER && kind <= ACCEL_QUADMB_MOELLER) || is_mb_linear_kind(kind) || is_line_mb_kind(kind); }
+// the motion-blur accels of triangles, quads, line segments and flat cubic curves, under swept and under linear bounds: lane kernel only, no service kernel
+inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKER && kind <= ACCEL_QUADMB_MOELLER) || is_mb_linear_kind(kind) || is_line_mb_kind(kind) || is_curve_mb_kind(kind); }
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
 {
   const QNode8* nodes;         // QNodeMB8[] in the kinds ACCEL_*MB_LINEAR_*; QNode8[] | padding | QNodeMB8[] in the kinds ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_*
   const TriRecord* prims;
-  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the LineRecord[] of a line accel, or the CurveRecord[] of a curve accel, or the TriMBRecord[] / QuadMBRecord[] / LineMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
+  const uint8_t* blobs;        // subdivision blobs, or the QuadRecord[] of a quad accel, or the LineRecord[] of a line accel, or the CurveRecord[] of a curve accel, or the TriMBRecord[] / QuadMBRecord[] / LineMBRecord[] / CurveMBRecord[] of a motion-blur accel, or InstanceRecord[] (+ QuadRecord[] ...)
   const uint32_t* blobOffsets; // blob index -> byte offset / 16
   uint32_t root;               // REF_EMPTY for an empty scene
   uint32_t kind;               // AccelKind
@@ -566,7 +609,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel of a scene: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, curves, lines, motion-blur lines, instances, subdivision instances)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel of a scene: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, curves, motion-blur curves, lines, motion-blur lines, instances, subdivision instances)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

@@ -43,6 +43,7 @@ void Device::parse(const std::string& cfg)
     else if (key == "line_accel") line_accel = val;
     else if (key == "line_accel_mb") { line_accel_mb = val; lineAccelMBNamed = true; }
     else if (key == "hair_accel") { hair_accel = val; hairAccelNamed = true; }
+    else if (key == "hair_accel_mb") { hair_accel_mb = val; hairAccelMBNamed = true; }
     else if (key == "inst_accel") { inst_accel = val; instAccelNamed = true; }
     else if (key == "mb_bounds") {
       if (val != "swept" && val != "linear") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "mb_bounds=: unknown value '" + val + "' (swept or linear)");

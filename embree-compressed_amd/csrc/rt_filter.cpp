@@ -131,6 +131,7 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
   // the ribbon leaf offers up to N candidates per curve and ray, one per ribbon quad, all with the curve's (geomID, primID): t tells them apart,
   // so a second quad of a rejected curve can still be found (the retry loop of Intersect1EpilogMU, intersector_epilog.h:488-509)
   excl[Scene::CURVE].keyedByT = true;
+  excl[Scene::CURVEMB].keyedByT = true; // the motion-blur ribbon leaf: a ray sees one time segment's record of a curve, and that record offers up to N candidates told apart by t
   excl[Scene::INST].keyedByT = excl[Scene::INST].withInst = true; // below a mesh instance: (instance, geomID, primID, bits of t) for every leaf type
   std::vector<uint32_t> next;
   void* dExcl = nullptr;
@@ -229,8 +230,9 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
           const bool onTriMB = geo && geo->type == RTC_GEOMETRY_TYPE_TRIANGLE && geo->timeSteps > 1; // one record per segment, a ray sees one segment: (geomID, primID) names the candidate
           const bool onLine = geo && geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && geo->timeSteps == 1;
           const bool onLineMB = geo && geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && geo->timeSteps > 1;
-          const bool onCurve = geo && geo->isFlatCubicCurve();
-          const size_t list = belowMeshInstance ? Scene::INST : onCurve ? Scene::CURVE : onLine ? Scene::LINE : onLineMB ? Scene::LINEMB : onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onQuadMB ? Scene::QUADMB : (onTriMB ? Scene::TRIMB : Scene::TRI)));
+          const bool onCurve = geo && geo->isFlatCubicCurve() && geo->timeSteps == 1;
+          const bool onCurveMB = geo && geo->isFlatCubicCurve() && geo->timeSteps > 1;
+          const size_t list = belowMeshInstance ? Scene::INST : onCurve ? Scene::CURVE : onCurveMB ? Scene::CURVEMB : onLine ? Scene::LINE : onLineMB ? Scene::LINEMB : onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onQuadMB ? Scene::QUADMB : (onTriMB ? Scene::TRIMB : Scene::TRI)));
           excl[list].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb, got.hit.instID[0]});
           next.push_back(i);
         }

@@ -39,6 +39,8 @@ struct Device : RefCounted
   std::string line_accel_mb = "default"; // flat linear curves with time steps: default / bvh8.line4imb / bvh4.line4imb, all the one BVH8 over LineMBRecords (build_linemb_accel raises for any other at commit)
   bool lineAccelMBNamed = false; // "line_accel_mb=" given (a host-only device builds the motion-blur line accel only then, lines_mb_enabled())
   std::string hair_accel = "default"; // flat Bezier and B-spline curves: the names of Scene::createHairAccel (default, bvh4.bezier1v, bvh4.bezier1i, bvh4obb.bezier1v, bvh4obb.bezier1i, bvh8obb.bezier1v, bvh8obb.bezier1i), all the one BVH8 over CurveRecords - oriented-box nodes are not built (build_curve_accel raises for any other name at commit)
+  std::string hair_accel_mb = "default"; // flat Bezier and B-spline curves with time steps: the names of Scene::createHairMBAccel (default, bvh4.bezier1imb, bvh8.bezier1imb), all the one BVH8 over CurveMBRecords - oriented-box nodes are not built (build_curvemb_accel raises for any other name at commit)
+  bool hairAccelMBNamed = false; // "hair_accel_mb=" given (a host-only device builds the motion-blur curve accel only then, curves_mb_enabled())
   bool hairAccelNamed = false; // "hair_accel=" given (a host-only device takes the flat cubic curve types only then, curves_enabled())
   std::string inst_accel = "default"; // instances: "default" is the only name (build_instance_accel, rt_instance_build.cpp, raises for any other at commit)
   bool instAccelNamed = false; // "inst_accel=" given (a host-only device takes quad meshes inside an instanced scene only then, inst_quads_enabled())
@@ -231,6 +233,9 @@ struct Device : RefCounted
   // Flat Bezier and B-spline curves, the same rule with the key hair_accel=: a host-only device without it refuses the two types at
   // rtcNewGeometry ("RTC_GEOMETRY_TYPE_*_CURVE not supported"), as before the curve accel existed.
   bool curves_enabled() const { return gpu >= 0 || hairAccelNamed; }
+  // Flat cubic curves with time steps, the rule of lines_mb_enabled() with the key hair_accel_mb=: a host-only device without it raises
+  // "motion blur of flat Bezier and B-spline curves is not supported" at commit, as before the motion-blur curve accel existed.
+  bool curves_mb_enabled() const { return gpu >= 0 || hairAccelMBNamed; }
   // Quad meshes inside an instanced scene, the same rule with the key inst_accel=: a host-only device without it refuses them at the top
   // scene's commit, as before the instance accel took quads.
   bool inst_quads_enabled() const { return gpu >= 0 || instAccelNamed; }
@@ -366,9 +371,9 @@ struct Geometry : RefCounted
   // index[i] + 3 = (x, y, z, radius), control points of the geometry's own basis
   bool isFlatCubicCurve() const { return type == RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE || type == RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE; }
   size_t numCurves() const { return numTriangles(); } // index buffer records (UINT)
-  bool validCurve(size_t i) const;                    // NativeCurves::valid (scene_bezier_curves.h:193-218)
+  bool validCurve(size_t i, unsigned slot = 0) const; // NativeCurves::valid (scene_bezier_curves.h:193-218) at one time step: against the vertex buffer of `slot`
   unsigned curveRate() const;                         // NativeCurves::setTessellationRate: clamp((int)rate, 1, 16)
-  void nativeCurve(size_t i, float out[16]) const;    // the four Bezier control points of curve i (B-spline input converted in float32)
+  void nativeCurve(size_t i, float out[16], unsigned slot = 0) const; // the four Bezier control points of curve i at time step `slot` (B-spline input converted in float32)
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -448,13 +453,14 @@ struct Scene : RefCounted
   Accel quadMBAccel; // quads with several time steps (QuadMBRecord[] in `blobs`); traced after the static quads, before the subdivision patches
   Accel subdivAccel; // subdivision patches (cBVH / GridSOA leaves)
   Accel curveAccel;  // flat Bezier and B-spline curves (CurveRecord[] in `blobs`); traced after the subdivision patches and before the line segments (scene.cpp:654-658: createSubdivAccel, createHairAccel, createLineAccel)
+  Accel curveMBAccel; // flat Bezier and B-spline curves with several time steps (CurveMBRecord[] in `blobs`); traced right after the static curves (scene.cpp:370-441: createHairAccel, createHairMBAccel)
   Accel lineAccel;   // flat linear curves (LineRecord[] in `blobs`); traced after the subdivision patches, before the instances (scene.cpp:650-663)
   Accel lineMBAccel; // flat linear curves with several time steps (LineMBRecord[] in `blobs`); traced right after the static lines (scene.cpp: createLineAccel, createLineMBAccel)
   Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle and quad trees behind the top-level tree); traced last (scene.cpp:661-665)
   Accel instSubdivAccel; // instances of scenes that hold subdivision meshes only (InstanceRecord[] and the instanced scenes' leaf blobs in `blobs`, their BVH8s behind the top-level tree); traced after the mesh instances
-  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / CURVE / LINE / LINEMB / INST / INSTSUBDIV index whatever a path keeps per accel
-  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, CURVE = 5, LINE = 6, LINEMB = 7, INST = 8, INSTSUBDIV = 9, NUM_ACCELS = 10 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &curveAccel, &lineAccel, &lineMBAccel, &instAccel, &instSubdivAccel}; }
+  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / CURVE / CURVEMB / LINE / LINEMB / INST / INSTSUBDIV index whatever a path keeps per accel
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, CURVE = 5, CURVEMB = 6, LINE = 7, LINEMB = 8, INST = 9, INSTSUBDIV = 10, NUM_ACCELS = 11 };
+  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &curveAccel, &curveMBAccel, &lineAccel, &lineMBAccel, &instAccel, &instSubdivAccel}; }
   bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
   // records the layout of instAccel placed in `blobs` behind the InstanceRecords, as build_instance_accel counted them (host only: the
   // verbose line of commit prints them)
@@ -476,13 +482,14 @@ struct Scene : RefCounted
 bool invert_affine(const float* m, float* out);
 V3 xfm_point(const float* m, V3 q);
 
-// the seven primitive accels of a scene (rt_prim_build.cpp), in Scene::commit's order (build_subdiv_accel, subdiv_build.h, runs between
+// the eight primitive accels of a scene (rt_prim_build.cpp), in Scene::commit's order (build_subdiv_accel, subdiv_build.h, runs between
 // the quads and the curves): where a scene has several faults, the order decides which refusal is reported
 void build_triangle_accel(Scene* s);
 void build_trimb_accel(Scene* s);
 void build_quad_accel(Scene* s);
 void build_quadmb_accel(Scene* s);
 void build_curve_accel(Scene* s);
+void build_curvemb_accel(Scene* s);
 void build_line_accel(Scene* s);
 void build_linemb_accel(Scene* s);
 

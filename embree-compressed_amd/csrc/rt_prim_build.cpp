@@ -1,4 +1,4 @@
-// The seven primitive accels of a scene - triangles, quads, flat cubic curves and line segments, static and with time steps - built at
+// The eight primitive accels of a scene - triangles, quads, flat cubic curves and line segments, static and with time steps - built at
 // commit from two frames: build_static_bvh8 and build_mb_bvh8.  A frame gathers the valid primitives of the scene's enabled geometries
 // of one type, builds one BVH8 (block 4, min leaf 4, max leaf 28: bvh_builder_sah.cpp:651-658) over them and stores the leaves' records;
 // where a primitive's box and record come from is the business of a Source.  What a builder keeps is the accel-name check and the kind.
@@ -244,14 +244,16 @@ struct LineSource
 };
 
 // The Source of the flat Bezier and B-spline curves: the record keeps the native (Bezier) control points and the geometry's tessellation
-// rate N, the box is that of the N ribbon quads the leaf tests (curve_tessellated_bounds).  Curves with time steps are refused.
+// rate N, the box is that of the N ribbon quads the leaf tests (curve_tessellated_bounds).  Curves with time steps belong to
+// build_curvemb_accel, and are refused on a host-only device that does not build it (Device::curves_mb_enabled).
 struct CurveSource
 {
-  bool takes(const Scene*, const Geometry* g) const
+  bool takes(const Scene* s, const Geometry* g) const
   {
     if (!g->isFlatCubicCurve()) return false;
-    if (g->timeSteps != 1) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur of flat Bezier and B-spline curves is not supported");
-    return true;
+    if (g->timeSteps == 1) return true;
+    if (!s->device->curves_mb_enabled()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur of flat Bezier and B-spline curves is not supported");
+    return false;
   }
   size_t count(const Geometry* g) const { return g->numCurves(); }
   bool valid(const Geometry* g, size_t i) const { return g->validCurve(i); }
@@ -270,7 +272,7 @@ struct CurveSource
 
 // ---- the motion-blur frame ----------------------------------------------------------------------------------------------------------------
 // The frame of the motion-blur builders, as build_static_bvh8 is the one of the static builders: one BVH8 with the triangle settings over
-// (primitive, time segment) pairs of the scene's enabled geometries of `type` with more than one time step.  A pair's box is the union
+// (primitive, time segment) pairs of the scene's enabled geometries with more than one time step that the Source takes.  A pair's box is the union
 // of the primitive's boxes at the two ends of the segment - the vertices move on straight lines in between, so the box holds the
 // primitive at every time of the segment (and, by the same argument, NOT at extrapolated times: a ray with a time outside [0, 1] sees
 // the first / last segment only where it still is inside its box).  A pair gets a record only when the primitive is valid at both ends.
@@ -287,13 +289,16 @@ struct CurveSource
 //    sticks out, and the result is exactly the bounds at step 0 and at step 1.  Computed in double and rounded outward to fp32; what
 //    double loses is covered, far over, by the quantizer's one-step padding.
 //  * Scene::bounds is extended by the swept boxes, as in the swept build.
-// Where a primitive's end boxes and record come from is the Source's business (MeshMBSource: NV vertices through an index record;
-// LineMBSource: two FLOAT4 vertices through one index word, boxes enlarged by the radius):
+// Which geometries, and where a primitive's end boxes and record come from, is the Source's business (MeshMBSource: NV vertices through
+// an index record; LineMBSource: two FLOAT4 vertices through one index word, boxes enlarged by the radius; CurveMBSource: four native
+// control points through one index word, boxes of the tessellated ribbon):
+//   takes(s, g)                    the geometry is of the Source's type and has more than one time step
+//   count(g)                       its primitives
 //   valid(g, i, step)              the primitive at a time step (TriangleMesh / QuadMesh / LineSegments::valid(i, itime))
 //   boxes(g, i, seg, a, b, mid)    its boxes at steps seg and seg + 1 and at mid-segment
 //   fill(rec, g, i, seg)           the geometry of the record; the four id words are set here
 template <class Rec, class Source>
-static void build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const Source& source, const char* tooMany, uint32_t kindSwept, uint32_t kindLinear, bool robust)
+static void build_mb_bvh8(Scene* s, Accel& A, const Source& source, const char* tooMany, uint32_t kindSwept, uint32_t kindLinear, bool robust)
 {
   const bool linear = s->device->mb_bounds == "linear";
   struct Ends { Box3 a, b; double ta, tb; }; // linear: a pair's boxes at the start / end of its segment and their global times
@@ -303,12 +308,12 @@ static void build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const Source
   Box3 swept;
   for (unsigned gid = 0; gid < s->geometries.size(); gid++) {
     const Geometry* g = s->geometries[gid];
-    if (!g || !g->enabled || g->type != type || g->timeSteps == 1) continue;
+    if (!g || !g->enabled || !source.takes(s, g)) continue;
     for (unsigned t = 0; t < g->timeSteps; t++) {
       const BufferView* vv = g->view(RTC_BUFFER_TYPE_VERTEX, t);
       if (!vv || !vv->valid()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur geometry: a time step has no vertex buffer");
     }
-    const size_t n = g->numTriangles(); // index buffer records
+    const size_t n = source.count(g);
     std::vector<char> ok(g->timeSteps);
     for (size_t i = 0; i < n; i++) {
       for (unsigned t = 0; t < g->timeSteps; t++) ok[t] = source.valid(g, i, t);
@@ -391,6 +396,8 @@ static void build_mb_bvh8(Scene* s, Accel& A, RTCGeometryType type, const Source
 template <int NV, class Rec, class Fill> struct MeshMBSource
 {
   const Fill& fillVertices;
+  bool takes(const Scene*, const Geometry* g) const { return g->type == (NV == 4 ? RTC_GEOMETRY_TYPE_QUAD : RTC_GEOMETRY_TYPE_TRIANGLE) && g->timeSteps != 1; }
+  size_t count(const Geometry* g) const { return g->numTriangles(); } // index buffer records
   bool valid(const Geometry* g, size_t i, unsigned step) const { return NV == 4 ? g->validQuad(i, step) : g->validTriangle(i, step); }
   void boxes(const Geometry* g, size_t i, unsigned seg, Box3& a, Box3& b, Box3& mid) const
   {
@@ -426,6 +433,8 @@ template <int NV, class Rec, class Fill> struct MeshMBSource
 // 7 * 2^-24 R + 2^-8 s + 2^-17 s <= 7 s / 8 + s / 256 + 2^-17 s < s: still inside the quantizer's one-step padding.
 struct LineMBSource
 {
+  bool takes(const Scene*, const Geometry* g) const { return g->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && g->timeSteps != 1; }
+  size_t count(const Geometry* g) const { return g->numSegments(); }
   bool valid(const Geometry* g, size_t i, unsigned step) const { return g->validSegment(i, step); }
   void boxes(const Geometry* g, size_t i, unsigned seg, Box3& a, Box3& b, Box3& mid) const
   {
@@ -445,6 +454,63 @@ struct LineMBSource
     memcpy(&r.v1ax, line_vertex(g, i, seg, 1), 16);
     memcpy(&r.v0bx, line_vertex(g, i, seg + 1, 0), 16);
     memcpy(&r.v1bx, line_vertex(g, i, seg + 1, 1), 16);
+  }
+};
+
+// The Source of the flat Bezier and B-spline curves: four native (Bezier) control points (x, y, z, radius) through one index word, B-spline
+// input converted per time step (Geometry::nativeCurve(i, out, step)).  A curve's box at a step is curve_tessellated_bounds of its native
+// points at that step with the geometry's rate N; the mid-segment box is that of the midpoints of the native points.
+// Containment (swept and linear): at ftime f the leaf interpolates the four native points in all four components and cuts the result
+// into the N quads between the tessellation points P_j(f), j = 0 .. N, with half widths w_j(f) (CurveMBLeaf, trace_curve_mb.hip).  P_j
+// and w_j are Bezier combinations - fixed weights per j - of the control points, hence LINEAR in the control points, and the control
+// points are linear in f: x_j(f) and w_j(f) are linear in f.  Per axis the box of the ribbon (curve_tessellated_bounds' argument) is
+// min_j x_j(f) - max_j |w_j(f)| below and max_j x_j(f) + max_j |w_j(f)| above.  A minimum of linear functions is concave, a maximum of
+// linear functions and of their absolute values convex: the lower plane is a concave function of f and lies ON OR ABOVE the chord of its
+// end values, the upper plane a convex one ON OR BELOW its chord.  So the box at f lies inside the interpolation of the two end boxes,
+// which is what linear_bounds needs of a pair's ends, and the interpolation lies inside their union, the swept box.
+// In fp32 (the budget of accel.h QNodeMB8, one grid step s >= 2^-21 R): interpolating the control points costs what it costs the line
+// leaf - three roundings on the coordinate, three on the radius, the plane's own two and time_segment's 2^-9 s on both: 7 * 2^-24 R +
+// 2^-8 s + 2^-17 s < s (LineMBSource) - and that alone leaves s / 8.  The Bezier combine comes on top, which the line leaf does not
+// have: a basis weight carries at most 4 roundings, the weights are non-negative and sum to 1, so with M the largest |x|, |y|, |z|,
+// |radius| among the four control points the weights' errors move a tessellation point by at most 4 * 2^-24 M and the product and three
+// madds of the combine by another 4 * 2^-24 M; the same again for the half width: 16 * 2^-24 M per evaluation.  It is evaluated twice,
+// on the host for the end boxes and in the leaf for the quads, and the host result is not the exact one either: 32 * 2^-24 M = 2^-19 M,
+// which can be four grid steps.  The padding does not cover that, so the END BOXES are widened here, each by 3 * 2^-20 M of its own
+// step's control points (2^-19 M and half as much again for the subtraction's own rounding and for M being rounded); the quantizer is
+// untouched.  M(f) of the interpolated points is at most the interpolation of M at the two ends (|.| is convex), so the interpolated
+// margin covers the budget at every f.  The mid-segment box only places the pair in the tree and is not widened.
+struct CurveMBSource
+{
+  bool takes(const Scene*, const Geometry* g) const { return g->isFlatCubicCurve() && g->timeSteps != 1; }
+  size_t count(const Geometry* g) const { return g->numCurves(); }
+  bool valid(const Geometry* g, size_t i, unsigned step) const { return g->validCurve(i, step); }
+  static Box3 widened_bounds(const float cp[16], unsigned N)
+  {
+    float M = 0.0f;
+    for (int k = 0; k < 16; k++) M = std::max(M, fabsf(cp[k]));
+    const float e = M * (3.0f / 1048576.0f);
+    const Box3 b = curve_tessellated_bounds(cp, N);
+    Box3 w;
+    w.extend(V3(b.lo.x - e, b.lo.y - e, b.lo.z - e));
+    w.extend(V3(b.hi.x + e, b.hi.y + e, b.hi.z + e));
+    return w;
+  }
+  void boxes(const Geometry* g, size_t i, unsigned seg, Box3& a, Box3& b, Box3& mid) const
+  {
+    float ca[16], cb[16], cm[16];
+    g->nativeCurve(i, ca, seg);
+    g->nativeCurve(i, cb, seg + 1);
+    for (int k = 0; k < 16; k++) cm[k] = (ca[k] + cb[k]) * 0.5f;
+    const unsigned N = g->curveRate();
+    a = widened_bounds(ca, N);
+    b = widened_bounds(cb, N);
+    mid = curve_tessellated_bounds(cm, N);
+  }
+  void fill(CurveMBRecord& r, const Geometry* g, size_t i, unsigned seg) const
+  {
+    g->nativeCurve(i, &r.v0ax, seg);
+    g->nativeCurve(i, &r.v0bx, seg + 1);
+    r.N = g->curveRate();
   }
 };
 
@@ -488,7 +554,7 @@ void build_trimb_accel(Scene* s)
     r.b1x = v[4].x; r.b1y = v[4].y; r.b1z = v[4].z;
     r.c1x = v[5].x; r.c1y = v[5].y; r.c1z = v[5].z;
   };
-  build_mb_bvh8<TriMBRecord>(s, A, RTC_GEOMETRY_TYPE_TRIANGLE, MeshMBSource<3, TriMBRecord, decltype(fill)>{fill}, "too many motion blur triangle segments for the 26-bit leaf reference",
+  build_mb_bvh8<TriMBRecord>(s, A, MeshMBSource<3, TriMBRecord, decltype(fill)>{fill}, "too many motion blur triangle segments for the 26-bit leaf reference",
                              pluecker ? ACCEL_TRIMB_PLUECKER : ACCEL_TRIMB_MOELLER, pluecker ? ACCEL_TRIMB_LINEAR_PLUECKER : ACCEL_TRIMB_LINEAR_MOELLER, pluecker);
 }
 
@@ -528,7 +594,7 @@ void build_quadmb_accel(Scene* s)
     q.v2bx = v[6].x; q.v2by = v[6].y; q.v2bz = v[6].z;
     q.v3bx = v[7].x; q.v3by = v[7].y; q.v3bz = v[7].z;
   };
-  build_mb_bvh8<QuadMBRecord>(s, A, RTC_GEOMETRY_TYPE_QUAD, MeshMBSource<4, QuadMBRecord, decltype(fill)>{fill}, "too many motion blur quad segments for the 26-bit leaf reference",
+  build_mb_bvh8<QuadMBRecord>(s, A, MeshMBSource<4, QuadMBRecord, decltype(fill)>{fill}, "too many motion blur quad segments for the 26-bit leaf reference",
                               pluecker ? ACCEL_QUADMB_PLUECKER : ACCEL_QUADMB_MOELLER, pluecker ? ACCEL_QUADMB_LINEAR_PLUECKER : ACCEL_QUADMB_LINEAR_MOELLER, pluecker);
 }
 
@@ -545,6 +611,22 @@ void build_curve_accel(Scene* s)
   if (!one_of(name, {"default", "bvh4.bezier1v", "bvh4.bezier1i", "bvh4obb.bezier1v", "bvh4obb.bezier1i", "bvh8obb.bezier1v", "bvh8obb.bezier1i"}))
     RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown hair acceleration structure " + name);
   build_static_bvh8<CurveRecord>(s, A, CurveSource(), "too many curves for the 26-bit leaf reference", s->isRobust() ? ACCEL_CURVE_ROBUST : ACCEL_CURVE_FAST, s->isRobust());
+}
+
+// Flat Bezier and B-spline curves with more than one time step (Scene::createHairMBAccel, scene.cpp:418-441): CurveMBRecords under the
+// frame of the motion-blur meshes.  Every name the reference accepts builds this accel; its oriented-box nodes (bvh4obb / bvh8obb under
+// `default`) are not built.  The kind tells the traversal (robust for a robust scene) and the node type (mb_bounds).  A host-only
+// device builds this accel only when its config names hair_accel_mb= (Device::curves_mb_enabled; CurveSource::takes raises otherwise).
+void build_curvemb_accel(Scene* s)
+{
+  Accel& A = s->curveMBAccel;
+  A.clear();
+  if (!s->device->curves_enabled() || !s->device->curves_mb_enabled()) return;
+  const std::string& name = s->device->hair_accel_mb;
+  if (!one_of(name, {"default", "bvh4.bezier1imb", "bvh8.bezier1imb"})) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown motion blur hair acceleration structure " + name);
+  const bool robust = s->isRobust();
+  build_mb_bvh8<CurveMBRecord>(s, A, CurveMBSource(), "too many motion blur curve segments for the 26-bit leaf reference",
+                               robust ? ACCEL_CURVEMB_ROBUST : ACCEL_CURVEMB_FAST, robust ? ACCEL_CURVEMB_LINEAR_ROBUST : ACCEL_CURVEMB_LINEAR_FAST, robust);
 }
 
 // Flat linear curves (Scene::createLineAccel, scene.cpp:444-468: bvh8.line4i; BVHNBuilderSAH<8,LineSegments,Line4i>(..., 4, 1.0f, 4, inf)):
@@ -572,7 +654,7 @@ void build_linemb_accel(Scene* s)
   const std::string& name = s->device->line_accel_mb;
   if (!one_of(name, {"default", "bvh8.line4imb", "bvh4.line4imb"})) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown motion blur line segment acceleration structure " + name);
   const bool robust = s->isRobust();
-  build_mb_bvh8<LineMBRecord>(s, A, RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE, LineMBSource(), "too many motion blur line segments for the 26-bit leaf reference",
+  build_mb_bvh8<LineMBRecord>(s, A, LineMBSource(), "too many motion blur line segments for the 26-bit leaf reference",
                               robust ? ACCEL_LINEMB_ROBUST : ACCEL_LINEMB_FAST, robust ? ACCEL_LINEMB_LINEAR_ROBUST : ACCEL_LINEMB_LINEAR_FAST, robust);
 }
 

@@ -164,8 +164,8 @@ static bool valid_points(const Geometry& g, size_t i, size_t n, unsigned slot)
 // LineSegments::valid(i, itime) (scene_line_segments.h): both end points, against the time step's buffer
 bool Geometry::validSegment(size_t i, unsigned slot) const { return valid_points(*this, i, 2, slot); }
 
-// NativeCurves::valid (scene_bezier_curves.h:193-218): the four control points
-bool Geometry::validCurve(size_t i) const { return valid_points(*this, i, 4, 0); }
+// NativeCurves::valid (scene_bezier_curves.h:193-218) at one time step: the four control points, against the time step's buffer
+bool Geometry::validCurve(size_t i, unsigned slot) const { return valid_points(*this, i, 4, slot); }
 
 unsigned Geometry::curveRate() const
 {
@@ -174,12 +174,12 @@ unsigned Geometry::curveRate() const
   return (unsigned)n;
 }
 
-// The native control points of curve i: the user's four for a Bezier geometry, convert(BSplineCurveT, BezierCurveT)
+// The native control points of curve i at time step `slot`: the user's four for a Bezier geometry, convert(BSplineCurveT, BezierCurveT)
 // (kernels/subdiv/bspline_curve.h:180-187) of them for a B-spline geometry - the reference's madd sequence in float32 on all four
 // components, the radius included (Vec3fa arithmetic works on the whole register).
-void Geometry::nativeCurve(size_t i, float out[16]) const
+void Geometry::nativeCurve(size_t i, float out[16], unsigned slot) const
 {
-  const BufferView* vv = view(RTC_BUFFER_TYPE_VERTEX, 0);
+  const BufferView* vv = view(RTC_BUFFER_TYPE_VERTEX, slot);
   const size_t i0 = segment(i);
   const float *a = (const float*)vv->at(i0), *b = (const float*)vv->at(i0 + 1), *c = (const float*)vv->at(i0 + 2), *d = (const float*)vv->at(i0 + 3);
   if (type != RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE) {
@@ -431,6 +431,7 @@ void Scene::commit()
   build_quadmb_accel(this);
   build_subdiv_accel(this);
   build_curve_accel(this);
+  build_curvemb_accel(this);
   build_line_accel(this);
   build_linemb_accel(this);
   build_instance_accel(this);
@@ -445,6 +446,7 @@ void Scene::commit()
     print_record_accel("quad", quadAccel, "quads", sizeof(QuadRecord));
     print_record_accel("motion blur quad", quadMBAccel, "segment records", sizeof(QuadMBRecord));
     print_record_accel("curve", curveAccel, "curves", sizeof(CurveRecord));
+    print_record_accel("motion blur curve", curveMBAccel, "segment records", sizeof(CurveMBRecord));
     print_record_accel("line", lineAccel, "segments", sizeof(LineRecord));
     print_record_accel("motion blur line", lineMBAccel, "segment records", sizeof(LineMBRecord));
   }

@@ -115,7 +115,7 @@ static bool service_trace(Scene* s, char* rays, uint32_t M, size_t byteStride, b
     if (a->traceable()) { if (only) return false; only = a; } // several accels (AccelN): the general path
   if (!only) return false;
   const Accel& A = *only;
-  if (is_mb_mesh_kind(A.kind)) return false; // no service kernel for motion blur (triangles, quads, line segments): the combiner traces these calls with the batch kernels
+  if (is_mb_mesh_kind(A.kind)) return false; // no service kernel for motion blur (triangles, quads, line segments, flat cubic curves): the combiner traces these calls with the batch kernels
   if (is_instance_kind(A.kind)) return false; // nor for instances (trace_instance.hip)
   if (is_line_kind(A.kind)) return false; // nor for line segments (trace_line.hip)
   if (is_curve_kind(A.kind)) return false; // nor for flat cubic curves (trace_curve.hip)

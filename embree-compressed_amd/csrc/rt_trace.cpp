@@ -69,7 +69,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   const bool poolPays = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER || A.kind == ACCEL_CBVH_GRID;
   p.poolKernel = dev->tunePoolKernel == 2u ? (poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel;
   if (is_mb_mesh_kind(A.kind))
-    p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip, trace_line_mb.hip), under swept and under linear bounds
+    p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip, trace_line_mb.hip, trace_curve_mb.hip), under swept and under linear bounds
   if (is_curve_kind(A.kind)) p.poolKernel = 0u; // the ribbon leaf exists in the lane kernel only (trace_curve.hip)
   const bool instKernel = is_instance_kind(A.kind);
   if (instKernel) p.poolKernel = 0u; // the two-level kernel is a lane-per-ray kernel of its own (trace_instance.hip, trace_instance_subdiv.hip and their linear forms): no pool form, no root cull pre-pass
@@ -146,8 +146,8 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   p.survivors = nullptr;
   // (never on the kinds of mb_bounds=linear: the pre-pass decodes a QNode8 root, and a root of time-dependent boxes would have to be
   // culled per ray time)
-  // (nor on the line accels, static and motion blur, and the curve accel: launch_cull derives the node test from the mesh kinds)
-  if (dev->tuneCull && !p.poolKernel && !instKernel && !is_mb_linear_kind(A.kind) && !is_line_kind(A.kind) && !is_line_mb_kind(A.kind) && !is_curve_kind(A.kind) && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
+  // (nor on the line and curve accels, static and motion blur: launch_cull derives the node test from the mesh kinds)
+  if (dev->tuneCull && !p.poolKernel && !instKernel && !is_mb_linear_kind(A.kind) && !is_line_kind(A.kind) && !is_line_mb_kind(A.kind) && !is_curve_kind(A.kind) && !is_curve_mb_kind(A.kind) && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
     const size_t need = ((size_t)(M + TRACE_QUEUES - 1) / TRACE_QUEUES) * TRACE_QUEUES * 4u;
     if (need > ctx.survivorsBytes) { // first batch of this size on this context (an allocation synchronises the device)
       HIP_CHECK(hipStreamSynchronize(stream));

@@ -830,11 +830,11 @@ API void rtcamdSynchronizeDevice(RTCDevice h)
 API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 
 // the accel the inspection calls describe: the first of the scene's accels that is not empty, in the order subdivision, triangles,
-// motion-blur triangles, quads, motion-blur quads, curves, lines, motion-blur lines, mesh instances, subdivision instances; the (empty)
+// motion-blur triangles, quads, motion-blur quads, curves, motion-blur curves, lines, motion-blur lines, mesh instances, subdivision instances; the (empty)
 // triangle accel when all are empty
 static const Accel& exported_accel(const Scene* s)
 {
-  for (const Accel* a : {&s->subdivAccel, &s->triAccel, &s->triMBAccel, &s->quadAccel, &s->quadMBAccel, &s->curveAccel, &s->lineAccel, &s->lineMBAccel, &s->instAccel, &s->instSubdivAccel})
+  for (const Accel* a : {&s->subdivAccel, &s->triAccel, &s->triMBAccel, &s->quadAccel, &s->quadMBAccel, &s->curveAccel, &s->curveMBAccel, &s->lineAccel, &s->lineMBAccel, &s->instAccel, &s->instSubdivAccel})
     if (a->kind != ACCEL_NONE) return *a;
   return s->triAccel;
 }

@@ -90,7 +90,7 @@ struct ServiceParams
   uint32_t* activity;  // device word: jobs served by any wavefront
 };
 // start the service kernel for base.accel.kind (and base.cbvhLevels); hipErrorInvalidValue: no service kernel for this accel kind / level
-// (the motion-blur triangle, quad and line accels, the line accel, the curve accel and the instance accel have none: rt_service.cpp hands their small calls to the combiner)
+// (the motion-blur triangle, quad and line accels, the line accel, the curve accels and the instance accel have none: rt_service.cpp hands their small calls to the combiner)
 hipError_t launch_service_tri(const ServiceParams& s, hipStream_t stream);       // trace_tri.hip
 hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream);      // trace_quad.hip
 hipError_t launch_service_grid(const ServiceParams& s, hipStream_t stream);      // trace_grid.hip
@@ -136,6 +136,7 @@ hipError_t launch_trace_cbvh_full(const LaunchParams& p, hipStream_t stream); //
 hipError_t launch_trace_line(const LaunchParams& p, hipStream_t stream);      // trace_line.hip (flat linear curves; no service kernel)
 hipError_t launch_trace_line_mb(const LaunchParams& p, hipStream_t stream);   // trace_line_mb.hip (flat linear curves with time steps; lane kernel only)
 hipError_t launch_trace_curve(const LaunchParams& p, hipStream_t stream);     // trace_curve.hip (flat Bezier / B-spline curves; lane kernel only, no service kernel)
+hipError_t launch_trace_curve_mb(const LaunchParams& p, hipStream_t stream);  // trace_curve_mb.hip (flat Bezier / B-spline curves with time steps; lane kernel only)
 hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  // trace_instance.hip
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb.hip
 hipError_t launch_trace_instance_subdiv(const LaunchParams& p, hipStream_t stream);  // trace_instance_subdiv.hip
@@ -186,6 +187,10 @@ inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
   case ACCEL_LINEMB_LINEAR_FAST: return launch_trace_line_mb(p, stream);
   case ACCEL_CURVE_ROBUST:
   case ACCEL_CURVE_FAST: return launch_trace_curve(p, stream);
+  case ACCEL_CURVEMB_ROBUST:
+  case ACCEL_CURVEMB_FAST:
+  case ACCEL_CURVEMB_LINEAR_ROBUST:
+  case ACCEL_CURVEMB_LINEAR_FAST: return launch_trace_curve_mb(p, stream);
   case ACCEL_INST_TRI_PLUECKER:
   case ACCEL_INST_TRI_MOELLER:
   case ACCEL_INST_PLUECKER:

@@ -5,7 +5,7 @@
 //   time segment     as for the motion-blur triangles (trace_mb.hip.h time_segment, geometry.h:28-34); a record is tested only when the
 //                    ray's itime equals the record's segment, checked before any arithmetic
 //   interpolation    lerp(p0, p1, f) = madd(1 - f, p0, f * p1) on Vec4vf (linei.h:276-277, vec4.h:179): ALL FOUR components, so the
-//                    radius is interpolated like a coordinate (lerp_vertex of trace_mb.hip.h zeroes w and cannot serve)
+//                    radius is interpolated like a coordinate: lerp_vertex4 of trace_mb.hip.h (lerp_vertex zeroes w and cannot serve)
 //   test             line_test of the static leaf on the interpolated end points (trace_line.hip.h); the ray space is recomputed per
 //                    leaf visit, as there
 // Blocks are groups of 4 RECORDS from the leaf start with the static leaf's rules: all tested records of a block see the tfar at block
@@ -24,13 +24,6 @@ namespace dev {
 #ifndef LINEMB_FETCH
 #define LINEMB_FETCH 2
 #endif
-
-// lerp of a Vec4vf: the radius in w goes through the same madd as the coordinates
-__device__ __forceinline__ float4 lerp_vertex4(const float4 p0, const float4 p1, float f)
-{
-  const float g = 1.0f - f;
-  return make_float4(madd(g, p0.x, f * p1.x), madd(g, p0.y, f * p1.y), madd(g, p0.z, f * p1.z), madd(g, p0.w, f * p1.w));
-}
 
 struct LineMBLeaf : LeafTraits
 {

@@ -1,4 +1,4 @@
-// What the motion-blur leaves share (trace_tri_mb.hip, trace_quad_mb.hip): the ray's time, the time segment of a record, the
+// What the motion-blur leaves share (trace_tri_mb.hip, trace_quad_mb.hip, trace_line_mb.hip, trace_curve_mb.hip): the ray's time, the time segment of a record, the
 // interpolation of a vertex.  Stateless __forceinline__ helpers, under the rule of trace_leaf.hip.h: a leaf uses a helper only where
 // its kernels stay the same instructions as with the helper in its own unit (tools/kernel_metadata.py --digest).
 #pragma once
@@ -17,6 +17,14 @@ __device__ __forceinline__ float4 lerp_vertex(const float4 p0, const float4 p1, 
 {
   const float g = 1.0f - f;
   return make_float4(madd(g, p0.x, f * p1.x), madd(g, p0.y, f * p1.y), madd(g, p0.z, f * p1.z), 0.0f);
+}
+
+// lerp of a Vec4vf (the line and curve leaves, linei.h:276-277, scene_bezier_curves.h:138-158): the radius in w goes through the same
+// madd as the coordinates
+__device__ __forceinline__ float4 lerp_vertex4(const float4 p0, const float4 p1, float f)
+{
+  const float g = 1.0f - f;
+  return make_float4(madd(g, p0.x, f * p1.x), madd(g, p0.y, f * p1.y), madd(g, p0.z, f * p1.z), madd(g, p0.w, f * p1.w));
 }
 
 // does the record with `segment` of a mesh with `numSegments` serve a ray at `time`?  f = ftime of the ray in that mesh

@@ -75,6 +75,12 @@ ACCEL_LINEMB_LINEAR_FAST = 41
 # flat Bezier / B-spline curves (Scene.add_curves): 80-byte records, one per curve, with the geometry's tessellation rate; robust / fast traversal
 ACCEL_CURVE_ROBUST = 42
 ACCEL_CURVE_FAST = 43
+# flat Bezier / B-spline curves with time steps (Scene.add_curves_mb): 160-byte records, one per curve and time segment; robust / fast
+# traversal, and the same over time-dependent nodes under mb_bounds=linear (144-byte nodes)
+ACCEL_CURVEMB_ROBUST = 44
+ACCEL_CURVEMB_FAST = 45
+ACCEL_CURVEMB_LINEAR_ROBUST = 46
+ACCEL_CURVEMB_LINEAR_FAST = 47
 # Scene.accel_data(kind + ACCEL_DATA_INSTSUBDIV): the arrays of that second instance accel, whatever else the scene holds
 ACCEL_DATA_INSTSUBDIV = 16
 RTC_SCENE_FLAG_NONE = 0
@@ -469,6 +475,42 @@ class Scene:
             gid = geom_id
         L.rtcReleaseGeometry(g)
         self.device.check("add_curves")
+        return gid
+
+    def add_curves_mb(self, verts4_per_step, first_index, basis="bezier", tessellation_rate=None, geom_id=None, flags=None):
+        """Motion-blur flat cubic curves: verts4_per_step is a sequence of N >= 2 float32 [nv,4] arrays = (x, y, z, radius) control points
+        of `basis` per time step (vertex buffer slots 0..N-1 after rtcSetGeometryTimeStepCount); first_index, basis, tessellation_rate and
+        flags as in add_curves; shared buffers padded like add_lines."""
+        L = self.lib
+        types = {"bezier": RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE, "bspline": RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE}
+        if basis not in types:
+            raise ValueError("add_curves_mb: basis must be 'bezier' or 'bspline'")
+        steps = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 4) for v in verts4_per_step]
+        idx = np.ascontiguousarray(first_index, dtype=np.uint32).reshape(-1)
+        g = L.rtcNewGeometry(self.device.handle, types[basis])
+        self.device.check("rtcNewGeometry(FLAT_%s_CURVE)" % basis.upper())
+        L.rtcSetGeometryTimeStepCount(g, len(steps))
+        for slot, v in enumerate(steps):
+            vpad = np.zeros((v.shape[0] + 1, 4), dtype=np.float32)
+            vpad[: v.shape[0]] = v
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_VERTEX, slot, RTC_FORMAT_FLOAT4, vpad.ctypes.data, 0, 16, v.shape[0])
+            self._keep.append(vpad)
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_INDEX, 0, RTC_FORMAT_UINT, idx.ctypes.data, 0, 4, idx.shape[0])
+        self._keep.append(idx)
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_FLAGS, 0, RTC_FORMAT_UCHAR, fl.ctypes.data, 0, 1, fl.shape[0])
+            self._keep.append(fl)
+        if tessellation_rate is not None:
+            L.rtcSetGeometryTessellationRate(g, float(tessellation_rate))
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self.device.check("add_curves_mb")
         return gid
 
     def add_lines_mb(self, verts4_per_step, first_index, geom_id=None, flags=None):

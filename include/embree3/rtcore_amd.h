@@ -83,10 +83,15 @@ struct RTCAMDSceneStats
                                38 / 39 motion blur line segments (robust / fast traversal; 80-byte records, one per segment and time
                                segment), 40 / 41 the same over time-dependent node boxes (mb_bounds=linear; nodeBytes is 144 there),
                                42 / 43 flat Bezier and B-spline curves (robust / fast traversal; 80-byte records: the four Bezier
-                               control points with their radii, geomID, primID and the tessellation rate of the curve's geometry) */
+                               control points with their radii, geomID, primID and the tessellation rate of the curve's geometry),
+                               44 / 45 motion blur flat Bezier and B-spline curves (device config hair_accel_mb=default | bvh4.bezier1imb |
+                               bvh8.bezier1imb, all the one BVH8; robust / fast traversal; 160-byte records, one per curve and time
+                               segment: the four Bezier control points with their radii at both ends of the segment, then geomID,
+                               primID, segment, numSegments and the tessellation rate), 46 / 47 the same over time-dependent node boxes
+                               (mb_bounds=linear; nodeBytes is 144 there) */
   unsigned int branching;   /* 8 */
   size_t nodeCount;         /* quantized BVH8 nodes */
-  size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29 and 40 / 41) */
+  size_t nodeBytes;         /* bytes per node record (96; 144 in the kinds 26..29, 40 / 41 and 46 / 47) */
   size_t primCount;         /* triangles, quads, or cBVH / GridSOA leaves */
   size_t primBytes;         /* bytes per triangle record (48), per quad record (64) or mean bytes per subdiv leaf blob */
   size_t leafCount;         /* BVH8 leaves */

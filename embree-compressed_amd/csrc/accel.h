@@ -510,7 +510,7 @@ enum AccelKind : uint32_t
   ACCEL_INSTSUBDIV_GRID = 24,     // instanced scenes whose subdivision accel is ACCEL_GRIDSOA (eager): GridCells below the instances
   ACCEL_INSTSUBDIV_CBVH_LEAF = 25, // instanced scenes whose subdivision accel is ACCEL_CBVH_LEAF, all at one C: cBVH blobs below the instances
   // mb_bounds=linear: the four motion-blur mesh accels over time-dependent nodes (QNodeMB8[] in `nodes`, 144-byte stride); records,
-  // leaves and the Pluecker / Moeller choice are those of the kinds 10..13.  NOT instance kinds.
+  // leaves and the Pluecker / Moeller choice are those of the kinds 10..13.
   ACCEL_TRIMB_LINEAR_PLUECKER = 26,
   ACCEL_TRIMB_LINEAR_MOELLER = 27,
   ACCEL_QUADMB_LINEAR_PLUECKER = 28,
@@ -528,62 +528,32 @@ enum AccelKind : uint32_t
   ACCEL_INSTSUBDIV_TOP_LINEAR_GRID = 34,
   ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF = 35,
   // flat linear curves (Scene::lineAccel, line_accel=default / bvh8.line4i / bvh4.line4i): LineRecord[] in `blobs`, one leaf arithmetic;
-  // robust traversal for RTC_SCENE_FLAG_ROBUST scenes, fast traversal otherwise.  Neither instance nor motion-blur kinds.
+  // robust traversal for RTC_SCENE_FLAG_ROBUST scenes, fast traversal otherwise.
   ACCEL_LINE_ROBUST = 36,
   ACCEL_LINE_FAST = 37,
   // flat linear curves with time steps (Scene::lineMBAccel, line_accel_mb=default / bvh8.line4imb / bvh4.line4imb): LineMBRecord[] in
-  // `blobs`, the static line leaf's arithmetic on the interpolated end points; robust / fast traversal as for the kinds 36 / 37.
-  // Motion-blur kinds (lane kernel only, no service kernel), NOT line kinds in the sense of is_line_kind (no pool form).
+  // `blobs`, the static line leaf's arithmetic on the interpolated end points; robust / fast traversal as for the kinds 36 / 37.  Lane kernel only.
   ACCEL_LINEMB_ROBUST = 38,
   ACCEL_LINEMB_FAST = 39,
   // the same under mb_bounds=linear: QNodeMB8[] in `nodes`, 144-byte stride, as the kinds 26..29
   ACCEL_LINEMB_LINEAR_ROBUST = 40,
   ACCEL_LINEMB_LINEAR_FAST = 41,
   // flat Bezier and B-spline curves (Scene::curveAccel, hair_accel=default / bvh4.bezier1v / ...): CurveRecord[] in `blobs`, one leaf
-  // arithmetic (the ribbon intersector); robust traversal for RTC_SCENE_FLAG_ROBUST scenes, fast traversal otherwise.  Neither instance nor
-  // motion-blur kinds; lane kernel only (lane and octet form), no pool form and no service kernel.
+  // arithmetic (the ribbon intersector); robust traversal for RTC_SCENE_FLAG_ROBUST scenes, fast traversal otherwise.  Lane
+  // kernel only (lane and octet form), no pool form and no service kernel.
   ACCEL_CURVE_ROBUST = 42,
   ACCEL_CURVE_FAST = 43,
   // flat Bezier and B-spline curves with time steps (Scene::curveMBAccel, hair_accel_mb=default / bvh4.bezier1imb / bvh8.bezier1imb):
   // CurveMBRecord[] in `blobs`, the static curve leaf's arithmetic on the interpolated control points; robust / fast traversal as for the
-  // kinds 42 / 43.  Motion-blur kinds (lane kernel only, no service kernel), NOT curve kinds in the sense of is_curve_kind.
+  // kinds 42 / 43.  Lane kernel only, no service kernel.
   ACCEL_CURVEMB_ROBUST = 44,
   ACCEL_CURVEMB_FAST = 45,
   // the same under mb_bounds=linear: QNodeMB8[] in `nodes`, 144-byte stride, as the kinds 26..29
   ACCEL_CURVEMB_LINEAR_ROBUST = 46,
-  ACCEL_CURVEMB_LINEAR_FAST = 47
+  ACCEL_CURVEMB_LINEAR_FAST = 47,
+  NUM_ACCEL_KINDS // a new kind goes above this line and gets a row in accel_kinds.h
 };
-inline bool is_curve_kind(uint32_t kind) { return kind == ACCEL_CURVE_ROBUST || kind == ACCEL_CURVE_FAST; } // traced by trace_curve.hip: lane kernel only
-inline bool is_line_kind(uint32_t kind) { return kind == ACCEL_LINE_ROBUST || kind == ACCEL_LINE_FAST; } // traced by trace_line.hip: lane and pool kernels, no service kernel
-inline bool is_inst_linear_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_LINEAR_PLUECKER || kind == ACCEL_INSTMESHMB_LINEAR_MOELLER; } // traced by trace_instance_mesh_mb_linear.hip
-inline bool is_inst_top_linear_kind(uint32_t kind) { return kind == ACCEL_INSTTOP_LINEAR_PLUECKER || kind == ACCEL_INSTTOP_LINEAR_MOELLER; } // traced by trace_instance_top_linear.hip
-// the instance kinds whose node buffer has two sections, QNode8s and QNodeMB8s (Accel::nodeImage)
-inline bool is_inst_subdiv_top_linear_kind(uint32_t kind) { return kind == ACCEL_INSTSUBDIV_TOP_LINEAR_GRID || kind == ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF; } // traced by trace_instance_subdiv_top_linear.hip
-inline bool is_inst_two_section_kind(uint32_t kind) { return is_inst_linear_kind(kind) || is_inst_top_linear_kind(kind) || is_inst_subdiv_top_linear_kind(kind); }
-// the instance kinds with the general layout of `blobs` (InstanceSceneRecords)
-inline bool is_inst_general_kind(uint32_t kind) { return kind == ACCEL_INSTMESHMB_PLUECKER || kind == ACCEL_INSTMESHMB_MOELLER || is_inst_linear_kind(kind) || is_inst_top_linear_kind(kind); }
-// traced by trace_instance.hip / trace_instance_mesh_mb.hip / trace_instance_subdiv.hip / trace_instance_mesh_mb_linear.hip / trace_instance_top_linear.hip /
-// trace_instance_subdiv_top_linear.hip
-inline bool is_instance_kind(uint32_t kind) { return (kind >= ACCEL_INST_TRI_PLUECKER && kind <= ACCEL_INSTSUBDIV_CBVH_LEAF) || is_inst_two_section_kind(kind); }
-
-// traced by trace_line_mb.hip: lane kernel only
-inline bool is_line_mb_kind(uint32_t kind) { return kind >= ACCEL_LINEMB_ROBUST && kind <= ACCEL_LINEMB_LINEAR_FAST; }
-// traced by trace_curve_mb.hip: lane kernel only
-inline bool is_curve_mb_kind(uint32_t kind) { return kind >= ACCEL_CURVEMB_ROBUST && kind <= ACCEL_CURVEMB_LINEAR_FAST; }
-// nodes are QNodeMB8: node stride, no root-cull pre-pass.  (The instance builder asks this of the triangle and quad motion-blur accels of
-// an instanced scene only; a scene with a line or curve accel of either kind is refused below an instance before it gets there.)
-inline bool is_mb_linear_kind(uint32_t kind)
-{
-  return (kind >= ACCEL_TRIMB_LINEAR_PLUECKER && kind <= ACCEL_QUADMB_LINEAR_MOELLER) || kind == ACCEL_LINEMB_LINEAR_ROBUST || kind == ACCEL_LINEMB_LINEAR_FAST ||
-         kind == ACCEL_CURVEMB_LINEAR_ROBUST || kind == ACCEL_CURVEMB_LINEAR_FAST;
-}
-// the arithmetic of a motion-blur mesh accel, under swept and under linear bounds
-inline bool is_mb_pluecker_kind(uint32_t kind)
-{
-  return kind == ACCEL_TRIMB_PLUECKER || kind == ACCEL_QUADMB_PLUECKER || kind == ACCEL_TRIMB_LINEAR_PLUECKER || kind == ACCEL_QUADMB_LINEAR_PLUECKER;
-}
-// the motion-blur accels of triangles, quads, line segments and flat cubic curves, under swept and under linear bounds: lane kernel only, no service kernel
-inline bool is_mb_mesh_kind(uint32_t kind) { return (kind >= ACCEL_TRIMB_PLUECKER && kind <= ACCEL_QUADMB_MOELLER) || is_mb_linear_kind(kind) || is_line_mb_kind(kind) || is_curve_mb_kind(kind); }
+// (what the host code asks of a kind - launcher, node test, node array, instance level, kernel forms - is one table: accel_kinds.h)
 
 // What a kernel launch needs to know about one committed scene.
 struct AccelDesc
@@ -609,7 +579,7 @@ struct WaveRecord
   unsigned long long lastGrab, maxRaySteps;
   unsigned long long valid;
 };
-static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel of a scene: triangles, motion-blur triangles, quads, motion-blur quads, subdiv, curves, motion-blur curves, lines, motion-blur lines, instances, subdivision instances)
+static const uint32_t WAVE_LOG_CAPACITY = 16384; // wave records per launch (one slice per accel slot of a scene: SCENE_SLOTS, rt_objects.h)
 
 // Work counters of the instrumented kernels (mirrors RTCAMDTraceCounters).
 struct TraceCounters

@@ -125,14 +125,7 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
   }
   ExclList excl[Scene::NUM_ACCELS];
   for (ExclList& e : excl) e.perRay.resize(M);
-  excl[Scene::QUAD].keyedByT = excl[Scene::QUADMB].keyedByT = excl[Scene::SUBDIV].keyedByT = true;
-  excl[Scene::LINE].keyedByT = true; // the line leaf scans with candidate_excluded(), which compares t as well (one candidate per segment and ray: t adds nothing, and takes nothing away)
-  excl[Scene::LINEMB].keyedByT = true; // the motion-blur line leaf scans the same way: one record per time segment and a ray sees one segment, so (geomID, primID) names the candidate
-  // the ribbon leaf offers up to N candidates per curve and ray, one per ribbon quad, all with the curve's (geomID, primID): t tells them apart,
-  // so a second quad of a rejected curve can still be found (the retry loop of Intersect1EpilogMU, intersector_epilog.h:488-509)
-  excl[Scene::CURVE].keyedByT = true;
-  excl[Scene::CURVEMB].keyedByT = true; // the motion-blur ribbon leaf: a ray sees one time segment's record of a curve, and that record offers up to N candidates told apart by t
-  excl[Scene::INST].keyedByT = excl[Scene::INST].withInst = true; // below a mesh instance: (instance, geomID, primID, bits of t) for every leaf type
+  for (const SlotRow& r : SCENE_SLOTS) { excl[r.slot].keyedByT = r.keyedByT; excl[r.slot].withInst = r.withInst; } // why each list is keyed as it is: SCENE_SLOTS
   std::vector<uint32_t> next;
   void* dExcl = nullptr;
   size_t dExclBytes = 0;
@@ -225,14 +218,7 @@ void trace_filtered(Scene* s, void* rays, uint32_t M, size_t byteStride, bool oc
         } else {
           uint32_t tb;
           memcpy(&tb, &got.ray.tfar, 4);
-          const bool onQuad = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD && geo->timeSteps == 1;
-          const bool onQuadMB = geo && geo->type == RTC_GEOMETRY_TYPE_QUAD && geo->timeSteps > 1; // as onTriMB; the two triangles of the quad are told apart by t
-          const bool onTriMB = geo && geo->type == RTC_GEOMETRY_TYPE_TRIANGLE && geo->timeSteps > 1; // one record per segment, a ray sees one segment: (geomID, primID) names the candidate
-          const bool onLine = geo && geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && geo->timeSteps == 1;
-          const bool onLineMB = geo && geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && geo->timeSteps > 1;
-          const bool onCurve = geo && geo->isFlatCubicCurve() && geo->timeSteps == 1;
-          const bool onCurveMB = geo && geo->isFlatCubicCurve() && geo->timeSteps > 1;
-          const size_t list = belowMeshInstance ? Scene::INST : onCurve ? Scene::CURVE : onCurveMB ? Scene::CURVEMB : onLine ? Scene::LINE : onLineMB ? Scene::LINEMB : onSubdiv ? Scene::SUBDIV : (onQuad ? Scene::QUAD : (onQuadMB ? Scene::QUADMB : (onTriMB ? Scene::TRIMB : Scene::TRI)));
+          const size_t list = belowMeshInstance ? Scene::INST : (geo ? slot_of(geo) : Scene::TRI); // (a hit on no geometry of this scene: the triangles' list, as ever)
           excl[list].perRay[i].push_back(ExclList::Rejected{got.hit.geomID, got.hit.primID, tb, got.hit.instID[0]});
           next.push_back(i);
         }

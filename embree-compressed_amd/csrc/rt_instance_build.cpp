@@ -408,9 +408,9 @@ MeshInstances classify_mesh_instances(const Scene* s)
     if (subdivOk && is_subdivision_scene(o)) continue; // build_instance_subdiv_accel places it
     // without inst_mb_bounds=linear the instanced scenes' trees are copied behind the top-level tree as QNode8s: time-dependent nodes
     // have no place there
-    if (!linearOk && wantTopLinear && (is_mb_linear_kind(o->triMBAccel.kind) || is_mb_linear_kind(o->quadMBAccel.kind)))
+    if (!linearOk && wantTopLinear && (o->triMBAccel.nodesAreMB() || o->quadMBAccel.nodesAreMB()))
       RT_THROW(RTC_ERROR_INVALID_OPERATION, topLinearNeedsLinear);
-    if (!linearOk && (is_mb_linear_kind(o->triMBAccel.kind) || is_mb_linear_kind(o->quadMBAccel.kind)))
+    if (!linearOk && (o->triMBAccel.nodesAreMB() || o->quadMBAccel.nodesAreMB()))
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene with a motion blur accel built under mb_bounds=linear is not supported (instance accels hold swept node boxes: use mb_bounds=swept)");
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
@@ -438,9 +438,9 @@ MeshInstances classify_mesh_instances(const Scene* s)
     if (trisMB || quadsMB) {
       // one arithmetic per top scene, over all four trees of every instanced scene
       struct { bool have, pl; const char* name; } const t[4] = {{tris, o->triAccel.kind == ACCEL_TRI_PLUECKER, "triangle"},
-                                                                {trisMB, is_mb_pluecker_kind(o->triMBAccel.kind), "motion blur triangle"},
+                                                                {trisMB, kind_row(o->triMBAccel.kind).robust, "motion blur triangle"},
                                                                 {quads, o->quadAccel.kind == ACCEL_QUAD_PLUECKER, "quad"},
-                                                                {quadsMB, is_mb_pluecker_kind(o->quadMBAccel.kind), "motion blur quad"}};
+                                                                {quadsMB, kind_row(o->quadMBAccel.kind).robust, "motion blur quad"}};
       std::string pl, mo;
       for (const auto& e : t)
         if (e.have) (e.pl ? pl : mo) += std::string((e.pl ? pl : mo).empty() ? "" : ", ") + e.name;
@@ -450,7 +450,7 @@ MeshInstances classify_mesh_instances(const Scene* s)
       if (haveKind && scenePl != c.pluecker) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(scenePl));
       c.anyMeshMotion = true;
       for (const Accel* m : {trisMB ? &o->triMBAccel : nullptr, quadsMB ? &o->quadMBAccel : nullptr})
-        if (m) (is_mb_linear_kind(m->kind) ? c.anyLinear : anySwept) = true;
+        if (m) (m->nodesAreMB() ? c.anyLinear : anySwept) = true;
     }
     c.pendingMax = std::max(c.pendingMax, (uint32_t)tris + (uint32_t)trisMB + (uint32_t)quads + (uint32_t)quadsMB - 1u);
     // the kernel runs ONE arithmetic on both levels and in both leaves: every accel below this scene is Pluecker / robust, or every one
@@ -460,7 +460,7 @@ MeshInstances classify_mesh_instances(const Scene* s)
                                             "as a robust scene under quad_accel=bvh8.quad4v builds them): instances need one arithmetic");
     const bool pl = tris ? o->triAccel.kind == ACCEL_TRI_PLUECKER
                   : quads ? o->quadAccel.kind == ACCEL_QUAD_PLUECKER
-                  : is_mb_pluecker_kind(trisMB ? o->triMBAccel.kind : o->quadMBAccel.kind);
+                  : kind_row(trisMB ? o->triMBAccel.kind : o->quadMBAccel.kind).robust;
     if (haveKind && pl != c.pluecker) {
       if (!c.anyQuads && !quads && !c.anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
       if (c.anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(pl));

@@ -12,7 +12,7 @@
 #include <thread>
 #include <unordered_map>
 
-#include "accel.h"
+#include "accel_kinds.h"
 #include "rt_common.h"
 
 namespace rtamd {
@@ -411,12 +411,16 @@ struct Accel
   // ACCEL_INSTMESHMB_LINEAR_* / ACCEL_INSTTOP_LINEAR_* / ACCEL_INSTSUBDIV_TOP_LINEAR_* hold both: these three describe their QNode8 section
   // (static trees, and in the kinds 30 / 31 the top-level tree), the QNodeMB8 section is described by the accel's two blobOffsets words
   // (the kinds 34 / 35: its words 2 and 3)
-  size_t nodeCount() const { return is_mb_linear_kind(kind) ? nodesMB.size() : nodes.size(); }
-  size_t nodeStride() const { return is_mb_linear_kind(kind) ? sizeof(QNodeMB8) : sizeof(QNode8); }
-  const void* nodeData() const { return is_mb_linear_kind(kind) ? (const void*)nodesMB.data() : (const void*)nodes.data(); }
+  // (nodesAreMB: the instance builder asks it of the triangle and quad motion-blur accels of an instanced scene only; a scene with a line
+  // or curve accel of either kind is refused below an instance before it gets there)
+  bool nodesAreMB() const { return kind_row(kind).nodes == NODES_MB8; }
+  bool twoSections() const { return kind_row(kind).nodes == NODES_TWO_SECTION; }
+  size_t nodeCount() const { return nodesAreMB() ? nodesMB.size() : nodes.size(); }
+  size_t nodeStride() const { return nodesAreMB() ? sizeof(QNodeMB8) : sizeof(QNode8); }
+  const void* nodeData() const { return nodesAreMB() ? (const void*)nodesMB.data() : (const void*)nodes.data(); }
   // the bytes of the device's node buffer
-  size_t nodeImageBytes() const { return is_inst_two_section_kind(kind) ? nodeImage.size() : nodeCount() * nodeStride(); }
-  const void* nodeImageData() const { return is_inst_two_section_kind(kind) ? (const void*)nodeImage.data() : nodeData(); }
+  size_t nodeImageBytes() const { return twoSections() ? nodeImage.size() : nodeCount() * nodeStride(); }
+  const void* nodeImageData() const { return twoSections() ? (const void*)nodeImage.data() : nodeData(); }
   bool traceable() const { return kind != ACCEL_NONE && root != REF_EMPTY; } // a launch on anything else returns before it touches the GPU
   size_t deviceBytes() const;
   void upload(Device* dev);
@@ -458,9 +462,9 @@ struct Scene : RefCounted
   Accel lineMBAccel; // flat linear curves with several time steps (LineMBRecord[] in `blobs`); traced right after the static lines (scene.cpp: createLineAccel, createLineMBAccel)
   Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle and quad trees behind the top-level tree); traced last (scene.cpp:661-665)
   Accel instSubdivAccel; // instances of scenes that hold subdivision meshes only (InstanceRecord[] and the instanced scenes' leaf blobs in `blobs`, their BVH8s behind the top-level tree); traced after the mesh instances
-  // the accels in trace order; TRI / TRIMB / QUAD / QUADMB / SUBDIV / CURVE / CURVEMB / LINE / LINEMB / INST / INSTSUBDIV index whatever a path keeps per accel
+  // the accel slots in trace order (one row each in SCENE_SLOTS below); they index whatever a path keeps per accel
   enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, CURVE = 5, CURVEMB = 6, LINE = 7, LINEMB = 8, INST = 9, INSTSUBDIV = 10, NUM_ACCELS = 11 };
-  std::array<Accel*, NUM_ACCELS> accels() { return {&triAccel, &triMBAccel, &quadAccel, &quadMBAccel, &subdivAccel, &curveAccel, &curveMBAccel, &lineAccel, &lineMBAccel, &instAccel, &instSubdivAccel}; }
+  std::array<Accel*, NUM_ACCELS> accels();
   bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
   // records the layout of instAccel placed in `blobs` behind the InstanceRecords, as build_instance_accel counted them (host only: the
   // verbose line of commit prints them)
@@ -482,20 +486,70 @@ struct Scene : RefCounted
 bool invert_affine(const float* m, float* out);
 V3 xfm_point(const float* m, V3 q);
 
-// the eight primitive accels of a scene (rt_prim_build.cpp), in Scene::commit's order (build_subdiv_accel, subdiv_build.h, runs between
-// the quads and the curves): where a scene has several faults, the order decides which refusal is reported
-void build_triangle_accel(Scene* s);
-void build_trimb_accel(Scene* s);
-void build_quad_accel(Scene* s);
-void build_quadmb_accel(Scene* s);
-void build_curve_accel(Scene* s);
-void build_curvemb_accel(Scene* s);
-void build_line_accel(Scene* s);
-void build_linemb_accel(Scene* s);
+// the builders of a scene's accels (rt_prim_build.cpp, subdiv_build.cpp, rt_instance_build.cpp); Scene::commit runs them in slot order
+void build_triangle_accel(Scene* s), build_trimb_accel(Scene* s), build_quad_accel(Scene* s), build_quadmb_accel(Scene* s), build_subdiv_accel(Scene* s),
+    build_curve_accel(Scene* s), build_curvemb_accel(Scene* s), build_line_accel(Scene* s), build_linemb_accel(Scene* s), build_instance_accel(Scene* s),
+    build_instance_subdiv_accel(Scene* s);
 
-// the two instance accels of a scene (rt_instance_build.cpp), in Scene::commit's order: the second relies on the first having refused
-// instances without a committed scene
-void build_instance_accel(Scene* s);
-void build_instance_subdiv_accel(Scene* s);
+// One row per accel slot of a scene, in trace order - which is also Scene::commit's build order: where a scene has several faults, the
+// order decides which refusal is reported, and build_instance_subdiv_accel relies on build_instance_accel having refused instances without
+// a committed scene.  Adding a slot: an Accel member, an enum value and a row ("Adding a kind / adding a slot").
+enum SlotSteps : uint8_t { STEPS_ONE, STEPS_SEVERAL, STEPS_ANY };
+struct SlotRow
+{
+  int slot;                  // Scene::TRI .. (checked against the row's place below)
+  Accel Scene::*accel;
+  void (*build)(Scene*);
+  // the verbose=2 line of an accel that keeps fixed-size records in `blobs` (Scene::commit); label nullptr: the slot has a line of its own
+  const char *label, *records;
+  size_t recordBytes;
+  // the geometries that land in the slot: their type is one of `types` (a slot of one type names it twice) and their time step count fits `steps`
+  RTCGeometryType types[2];
+  SlotSteps steps;
+  // the slot's exclusion list in a filter re-trace (rt_excl_list.h): entries carry the bits of t / the instance as well
+  bool keyedByT, withInst;
+  int exportRank;            // place in the order in which the inspection calls look for the first accel that is not empty (exported_accel)
+};
+inline constexpr SlotRow SCENE_SLOTS[] = {
+  // triangles: (geomID, primID) names the candidate.  With time steps: one record per segment, a ray sees one segment, so the pair still does
+  {Scene::TRI, &Scene::triAccel, build_triangle_accel, nullptr, nullptr, 0, {RTC_GEOMETRY_TYPE_TRIANGLE, RTC_GEOMETRY_TYPE_TRIANGLE}, STEPS_ONE, false, false, 1},
+  {Scene::TRIMB, &Scene::triMBAccel, build_trimb_accel, "motion blur triangle", "segment records", sizeof(TriMBRecord), {RTC_GEOMETRY_TYPE_TRIANGLE, RTC_GEOMETRY_TYPE_TRIANGLE}, STEPS_SEVERAL, false, false, 2},
+  // quads, static and (as for the moving triangles) with time steps: the two triangles of the quad are told apart by t
+  {Scene::QUAD, &Scene::quadAccel, build_quad_accel, "quad", "quads", sizeof(QuadRecord), {RTC_GEOMETRY_TYPE_QUAD, RTC_GEOMETRY_TYPE_QUAD}, STEPS_ONE, true, false, 3},
+  {Scene::QUADMB, &Scene::quadMBAccel, build_quadmb_accel, "motion blur quad", "segment records", sizeof(QuadMBRecord), {RTC_GEOMETRY_TYPE_QUAD, RTC_GEOMETRY_TYPE_QUAD}, STEPS_SEVERAL, true, false, 4},
+  // eager grid cells: the triangles of a patch share (geomID, primID), t tells them apart
+  {Scene::SUBDIV, &Scene::subdivAccel, build_subdiv_accel, nullptr, nullptr, 0, {RTC_GEOMETRY_TYPE_SUBDIVISION, RTC_GEOMETRY_TYPE_SUBDIVISION}, STEPS_ANY, true, false, 0},
+  // the ribbon leaf offers up to N candidates per curve and ray, one per ribbon quad, all with the curve's (geomID, primID): t tells them apart,
+  // so a second quad of a rejected curve can still be found (the retry loop of Intersect1EpilogMU, intersector_epilog.h:488-509)
+  {Scene::CURVE, &Scene::curveAccel, build_curve_accel, "curve", "curves", sizeof(CurveRecord), {RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE, RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE}, STEPS_ONE, true, false, 5},
+  // the motion-blur ribbon leaf: a ray sees one time segment's record of a curve, and that record offers up to N candidates told apart by t
+  {Scene::CURVEMB, &Scene::curveMBAccel, build_curvemb_accel, "motion blur curve", "segment records", sizeof(CurveMBRecord), {RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE, RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE}, STEPS_SEVERAL, true, false, 6},
+  // the line leaf scans with candidate_excluded(), which compares t as well (one candidate per segment and ray: t adds nothing, and takes nothing away)
+  {Scene::LINE, &Scene::lineAccel, build_line_accel, "line", "segments", sizeof(LineRecord), {RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE, RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE}, STEPS_ONE, true, false, 7},
+  // the motion-blur line leaf scans the same way: one record per time segment and a ray sees one segment, so (geomID, primID) names the candidate
+  {Scene::LINEMB, &Scene::lineMBAccel, build_linemb_accel, "motion blur line", "segment records", sizeof(LineMBRecord), {RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE, RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE}, STEPS_SEVERAL, true, false, 8},
+  // below a mesh instance: (instance, geomID, primID, bits of t) for every leaf type
+  {Scene::INST, &Scene::instAccel, build_instance_accel, nullptr, nullptr, 0, {RTC_GEOMETRY_TYPE_INSTANCE, RTC_GEOMETRY_TYPE_INSTANCE}, STEPS_ANY, true, true, 9},
+  // (no filter runs below a subdivision instance: the list stays empty)
+  {Scene::INSTSUBDIV, &Scene::instSubdivAccel, build_instance_subdiv_accel, nullptr, nullptr, 0, {RTC_GEOMETRY_TYPE_INSTANCE, RTC_GEOMETRY_TYPE_INSTANCE}, STEPS_ANY, false, false, 10},
+};
+static_assert(sizeof(SCENE_SLOTS) / sizeof(SCENE_SLOTS[0]) == Scene::NUM_ACCELS, "every accel slot needs a row in SCENE_SLOTS");
+constexpr bool scene_slots_in_order(int i = 0) { return i == Scene::NUM_ACCELS || (SCENE_SLOTS[i].slot == i && scene_slots_in_order(i + 1)); }
+static_assert(scene_slots_in_order(), "the rows of SCENE_SLOTS stand in slot order");
+
+inline std::array<Accel*, Scene::NUM_ACCELS> Scene::accels()
+{
+  std::array<Accel*, NUM_ACCELS> a;
+  for (const SlotRow& r : SCENE_SLOTS) a[r.slot] = &(this->*r.accel);
+  return a;
+}
+
+// the slot a geometry's primitives land in (the two instance slots share a type: the first, Scene::INST); -1: no slot takes its type
+inline int slot_of(const Geometry* g)
+{
+  for (const SlotRow& r : SCENE_SLOTS)
+    if ((g->type == r.types[0] || g->type == r.types[1]) && (r.steps == STEPS_ANY || (r.steps == STEPS_SEVERAL) == (g->timeSteps > 1))) return r.slot;
+  return -1;
+}
 
 } // namespace rtamd

@@ -384,31 +384,14 @@ V3 xfm_point(const float* m, V3 q)
   return r;
 }
 
-// the verbose line of an accel that keeps fixed-size records in `blobs`; nothing for an empty accel
-static void print_record_accel(const char* label, const Accel& A, const char* records, size_t recordBytes)
-{
-  if (A.kind == ACCEL_NONE) return;
-  fprintf(stderr, "embree3-amd: %s accel kind %u: %zu nodes (%zu B), %zu %s (%zu B), depth %u\n", label, A.kind, A.nodeCount(), A.nodeCount() * A.nodeStride(),
-          A.blobs.size() / recordBytes, records, A.blobs.size(), A.maxDepth);
-}
-
 void Scene::commit()
 {
   std::lock_guard<std::mutex> g(buildMutex);
   service_quiesce(device); // the upload allocates device memory (see Scene::~Scene)
   for (Geometry* geo : geometries) {
     if (!geo || !geo->enabled) continue;
-    switch (geo->type) {
-    case RTC_GEOMETRY_TYPE_TRIANGLE:
-    case RTC_GEOMETRY_TYPE_QUAD:
-    case RTC_GEOMETRY_TYPE_SUBDIVISION:
-    case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE:
-    case RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE:
-    case RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE:
-    case RTC_GEOMETRY_TYPE_INSTANCE: break;
-    default: // scene.cpp:25-30: geometry types compiled out raise INVALID_OPERATION
+    if (slot_of(geo) < 0) // no slot takes the type (SCENE_SLOTS).  scene.cpp:25-30: geometry types compiled out raise INVALID_OPERATION
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry type not supported by the MI355X traversal path");
-    }
   }
   triIntersectFilter = triOccludedFilter = subdivFilter = false;
   lineIntersectFilter = lineOccludedFilter = false;
@@ -425,42 +408,31 @@ void Scene::commit()
   }
   if (progressFn && !progressFn(progressUser, 0.0)) RT_THROW(RTC_ERROR_CANCELLED, "progress monitor forced termination");
   bounds = Box3();
-  build_triangle_accel(this);
-  build_trimb_accel(this);
-  build_quad_accel(this);
-  build_quadmb_accel(this);
-  build_subdiv_accel(this);
-  build_curve_accel(this);
-  build_curvemb_accel(this);
-  build_line_accel(this);
-  build_linemb_accel(this);
-  build_instance_accel(this);
-  build_instance_subdiv_accel(this);
+  for (const SlotRow& r : SCENE_SLOTS) r.build(this);
   for (Accel* a : accels()) a->upload(device);
   if (progressFn) progressFn(progressUser, 1.0);
   if (device->verbose >= 2) {
     fprintf(stderr, "embree3-amd: tri accel kind %u: %zu nodes (%zu B), %zu tris, depth %u; subdiv accel kind %u: %zu nodes, %zu blobs (%zu B)\n",
             triAccel.kind, triAccel.nodes.size(), triAccel.nodes.size() * sizeof(QNode8), triAccel.prims.size(), triAccel.maxDepth,
             subdivAccel.kind, subdivAccel.nodes.size(), subdivAccel.blobOffsets.size(), subdivAccel.blobs.size());
-    print_record_accel("motion blur triangle", triMBAccel, "segment records", sizeof(TriMBRecord));
-    print_record_accel("quad", quadAccel, "quads", sizeof(QuadRecord));
-    print_record_accel("motion blur quad", quadMBAccel, "segment records", sizeof(QuadMBRecord));
-    print_record_accel("curve", curveAccel, "curves", sizeof(CurveRecord));
-    print_record_accel("motion blur curve", curveMBAccel, "segment records", sizeof(CurveMBRecord));
-    print_record_accel("line", lineAccel, "segments", sizeof(LineRecord));
-    print_record_accel("motion blur line", lineMBAccel, "segment records", sizeof(LineMBRecord));
+    for (const SlotRow& r : SCENE_SLOTS) { // the line of an accel that keeps fixed-size records in `blobs`; nothing for an empty accel
+      const Accel& A = this->*r.accel;
+      if (r.label && A.kind != ACCEL_NONE)
+        fprintf(stderr, "embree3-amd: %s accel kind %u: %zu nodes (%zu B), %zu %s (%zu B), depth %u\n", r.label, A.kind, A.nodeCount(), A.nodeCount() * A.nodeStride(),
+                A.blobs.size() / r.recordBytes, r.records, A.blobs.size(), A.maxDepth);
+    }
   }
   if (instAccel.kind != ACCEL_NONE && device->verbose >= 2)
   {
     // the record counts of the layout (build_instance_accel).  Below the kinds ACCEL_INSTMESHMB_* "instanced quads" has always counted
     // every 64-byte record behind the instance records: quads and InstanceSteps
-    const bool general = is_inst_general_kind(instAccel.kind);
+    const bool general = kind_row(instAccel.kind).instGeneral;
     const size_t nQuads = instCounts.quads + (general ? 0 : instCounts.steps), nTriMB = instCounts.triMB, nQuadMB = instCounts.quadMB;
     fprintf(stderr, "embree3-amd: instance accel kind %u: %zu nodes (%zu B), %zu instances, %zu instanced triangles, %zu instanced quads, %zu instanced motion blur triangle "
                     "segment records, %zu instanced motion blur quad segment records, depth %u\n", instAccel.kind,
             instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),
             nQuads, nTriMB, nQuadMB, instAccel.maxDepth);
-    if (is_inst_two_section_kind(instAccel.kind))
+    if (instAccel.twoSections())
       fprintf(stderr, "embree3-amd: instance accel kind %u: %zu time-dependent nodes (%zu B) from node index %u in 144-byte units, node buffer %zu B\n", instAccel.kind,
               instAccel.nodesMB.size(), instAccel.nodesMB.size() * sizeof(QNodeMB8), instAccel.blobOffsets[1], instAccel.nodeImage.size());
   }
@@ -468,7 +440,7 @@ void Scene::commit()
     fprintf(stderr, "embree3-amd: subdivision instance accel kind %u (C %u): %zu nodes (%zu B), %zu instances, %u instanced leaf blobs of %u B from blob index %u, depth %u\n",
             instSubdivAccel.kind, instSubdivAccel.cbvhLevels, instSubdivAccel.nodes.size(), instSubdivAccel.nodes.size() * sizeof(QNode8), instSubdivAccel.leafCount,
             instSubdivAccel.blobOffsets[0], instSubdivAccel.blobStride, instSubdivAccel.blobOffsets[1], instSubdivAccel.maxDepth);
-  if (is_inst_subdiv_top_linear_kind(instSubdivAccel.kind) && device->verbose >= 2)
+  if (instSubdivAccel.twoSections() && device->verbose >= 2)
     fprintf(stderr, "embree3-amd: subdivision instance accel kind %u: %zu time-dependent nodes (%zu B) from node index %u in 144-byte units, node buffer %zu B\n", instSubdivAccel.kind,
             instSubdivAccel.nodesMB.size(), instSubdivAccel.nodesMB.size() * sizeof(QNodeMB8), instSubdivAccel.blobOffsets[3], instSubdivAccel.nodeImage.size());
   modified = false;

@@ -115,10 +115,8 @@ static bool service_trace(Scene* s, char* rays, uint32_t M, size_t byteStride, b
     if (a->traceable()) { if (only) return false; only = a; } // several accels (AccelN): the general path
   if (!only) return false;
   const Accel& A = *only;
-  if (is_mb_mesh_kind(A.kind)) return false; // no service kernel for motion blur (triangles, quads, line segments, flat cubic curves): the combiner traces these calls with the batch kernels
-  if (is_instance_kind(A.kind)) return false; // nor for instances (trace_instance.hip)
-  if (is_line_kind(A.kind)) return false; // nor for line segments (trace_line.hip)
-  if (is_curve_kind(A.kind)) return false; // nor for flat cubic curves (trace_curve.hip)
+  const KindRow& K = kind_row(A.kind);
+  if (!K.serve) return false; // no service kernel for this kind (accel_kinds.h): the combiner traces these calls with the batch kernels
   const uint32_t worst = 7u * (A.maxDepth + 1u) + 2u;
   const uint32_t need = worst > (uint32_t)TRACE_LDS_STACK ? worst - TRACE_LDS_STACK : 0u;
   if (need > Device::Service::SPILL_DEPTH) return false;
@@ -143,7 +141,7 @@ static bool service_trace(Scene* s, char* rays, uint32_t M, size_t byteStride, b
       p.octMax = dev->tuneOctMax;
       p.walkBatch = dev->tuneWalkBatch;
       p.octSteps = dev->tuneOctSteps;
-      p.octLeaf = dev->tuneOctLeaf != 0xFFFFFFFFu ? dev->tuneOctLeaf : (A.kind == ACCEL_GRIDSOA ? 24u : 16u);
+      p.octLeaf = dev->tuneOctLeaf != 0xFFFFFFFFu ? dev->tuneOctLeaf : (uint32_t)K.octLeaf;
       p.overflow = sh.overflowDev;
       p.spillDepth = Device::Service::SPILL_DEPTH;
       p.gridBlocks = Device::Service::SLOTS / (TRACE_BLOCK / 64);
@@ -169,8 +167,7 @@ static bool service_trace(Scene* s, char* rays, uint32_t M, size_t byteStride, b
     }
     sv = dev->service;
   }
-  const bool levelFree = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER || A.kind == ACCEL_QUAD_PLUECKER || A.kind == ACCEL_QUAD_MOELLER || A.kind == ACCEL_GRIDSOA;
-  if (sv->failed || sv->kind != A.kind || (sv->levels != s->compressionLevel && !levelFree)) return false;
+  if (sv->failed || sv->kind != A.kind || (sv->levels != s->compressionLevel && !K.levelFree)) return false;
 
   // a slot: threads are dealt slots round-robin once; a shared slot is taken in turns
   static thread_local uint32_t mySlot = 0xFFFFFFFFu;

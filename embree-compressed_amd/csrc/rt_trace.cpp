@@ -66,13 +66,8 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   // kernel is the faster one at EVERY size for grid cells and the cBVH box / leaf / full modes (4 M rays, one stream: cbvh.leaf 12.0 vs 10.2 Grays/s,
   // eager 6 M 14.5 vs 10.7); the pool keeps triangles (6 M: 16.8 vs 14.8) and the cBVH grid mode (11.0 vs 8.3).  profiles/r03_lane_pool_ab.txt
   // (quad leaves stay on the lane kernel unless RTAMD_KERNEL=pool: not measured)
-  const bool poolPays = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER || A.kind == ACCEL_CBVH_GRID;
-  p.poolKernel = dev->tunePoolKernel == 2u ? (poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel;
-  if (is_mb_mesh_kind(A.kind))
-    p.poolKernel = 0u; // the motion-blur leaves exist in the lane kernel only (trace_tri_mb.hip, trace_quad_mb.hip, trace_line_mb.hip, trace_curve_mb.hip), under swept and under linear bounds
-  if (is_curve_kind(A.kind)) p.poolKernel = 0u; // the ribbon leaf exists in the lane kernel only (trace_curve.hip)
-  const bool instKernel = is_instance_kind(A.kind);
-  if (instKernel) p.poolKernel = 0u; // the two-level kernel is a lane-per-ray kernel of its own (trace_instance.hip, trace_instance_subdiv.hip and their linear forms): no pool form, no root cull pre-pass
+  const KindRow& K = kind_row(A.kind); // which kinds have a pool form, and why the others have none: accel_kinds.h
+  p.poolKernel = !K.pool ? 0u : (dev->tunePoolKernel == 2u ? (K.poolPays && M >= dev->tunePoolMinRays ? 1u : 0u) : dev->tunePoolKernel);
   // worst-case stack: 7 siblings per level plus the entry being expanded.  The overflow area is sized for it, so a push
   // can only be dropped if the tree is deeper than the builder reported; the kernels then raise `overflow` (below).
   const uint32_t worst = 7u * (A.maxDepth + 1u) + 2u;
@@ -85,7 +80,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
     p.spillDepth = worst > (uint32_t)TRACE_LDS_STACK ? worst - TRACE_LDS_STACK : 0u;
     // development aid (env RTAMD_INST_SPILL_MAX, two-level kernels only): fewer overflow entries than the depth asks for, to exercise the
     // documented failure - a push beyond the area is dropped behind its bounds check, the kernel raises `overflow`, the call RTC_ERROR_UNKNOWN
-    if (instKernel) p.spillDepth = std::min(p.spillDepth, dev->tuneInstSpillMax);
+    if (K.inst != INST_NONE) p.spillDepth = std::min(p.spillDepth, dev->tuneInstSpillMax);
     spillBytes = (size_t)p.gridBlocks * TRACE_BLOCK * (size_t)p.spillDepth * 8u + 16u;
   }
   p.counters = x.counters;
@@ -105,7 +100,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   p.octSteps = dev->tuneOctSteps;
   // waiting rays from which the child-parallel leaf phase runs: triangle leaves 16, grid cells 24 (measured optima), cBVH blobs
   // (quad form, 16 rays per pass) 16
-  p.octLeaf = dev->tuneOctLeaf != 0xFFFFFFFFu ? dev->tuneOctLeaf : (A.kind == ACCEL_GRIDSOA ? 24u : 16u);
+  p.octLeaf = dev->tuneOctLeaf != 0xFFFFFFFFu ? dev->tuneOctLeaf : (uint32_t)K.octLeaf;
   p.exclOffsets = x.exclOffsets;
   p.exclPairs = x.exclPairs;
   p.exclT = x.exclT;
@@ -125,7 +120,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   // instructions (measured: 11.2 -> 12.0 Grays/s with four batches in flight; alone 0.174 -> 0.237 ms, hence adaptive).
   // (The grid-cell kernel, whose leaves are always tested 8 lanes per ray, needs 118 VGPRs: four waves per SIMD fit, and a batch
   // alone on the chip is 10 % faster with four workgroups per CU; 0.169 -> 0.151 ms.)
-  const bool octOnly = A.kind == ACCEL_GRIDSOA || ((A.kind == ACCEL_CBVH_BOX || A.kind == ACCEL_CBVH_LEAF || A.kind == ACCEL_CBVH_FULL) && !p.cbvhLaneForm); // four waves per SIMD
+  const bool octOnly = K.octOnly == OCT_ALWAYS || (K.octOnly == OCT_QUAD_FORM && !p.cbvhLaneForm); // four waves per SIMD
   const uint32_t aloneBlocks = octOnly ? dev->tuneAloneBlocksOct : 2u;
   // with that fourth wave slot two workgroups per CU per batch are also the better grid in flight (eager, 40 steps: random rays
   // 13.3 -> 13.8 Grays/s, shadow rays 9.3 -> 9.8, camera rays 7.1 -> 7.7)
@@ -144,10 +139,8 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   // Root cull pre-pass (trace_cull.hip.h): large batches on the lane kernel whose root is an inner node.  Filter re-traces
   // (exclusion lists) are small and skip it.
   p.survivors = nullptr;
-  // (never on the kinds of mb_bounds=linear: the pre-pass decodes a QNode8 root, and a root of time-dependent boxes would have to be
-  // culled per ray time)
-  // (nor on the line and curve accels, static and motion blur: launch_cull derives the node test from the mesh kinds)
-  if (dev->tuneCull && !p.poolKernel && !instKernel && !is_mb_linear_kind(A.kind) && !is_line_kind(A.kind) && !is_line_mb_kind(A.kind) && !is_curve_kind(A.kind) && !is_curve_mb_kind(A.kind) && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
+  // (only on the kinds whose row allows it, accel_kinds.h)
+  if (dev->tuneCull && K.cull && !p.poolKernel && !x.exclOffsets && M >= dev->tuneCullMinRays && !(A.root & REF_LEAF)) {
     const size_t need = ((size_t)(M + TRACE_QUEUES - 1) / TRACE_QUEUES) * TRACE_QUEUES * 4u;
     if (need > ctx.survivorsBytes) { // first batch of this size on this context (an allocation synchronises the device)
       HIP_CHECK(hipStreamSynchronize(stream));

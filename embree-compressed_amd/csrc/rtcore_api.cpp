@@ -829,13 +829,13 @@ API void rtcamdSynchronizeDevice(RTCDevice h)
 
 API int rtcamdGetDeviceOrdinal(RTCDevice h) { return h ? D(h)->gpu : -1; }
 
-// the accel the inspection calls describe: the first of the scene's accels that is not empty, in the order subdivision, triangles,
-// motion-blur triangles, quads, motion-blur quads, curves, motion-blur curves, lines, motion-blur lines, mesh instances, subdivision instances; the (empty)
-// triangle accel when all are empty
+// the accel the inspection calls describe: the first of the scene's accels that is not empty, in the order of SlotRow::exportRank (the
+// subdivision accel, then the others in trace order); the (empty) triangle accel when all are empty
 static const Accel& exported_accel(const Scene* s)
 {
-  for (const Accel* a : {&s->subdivAccel, &s->triAccel, &s->triMBAccel, &s->quadAccel, &s->quadMBAccel, &s->curveAccel, &s->curveMBAccel, &s->lineAccel, &s->lineMBAccel, &s->instAccel, &s->instSubdivAccel})
-    if (a->kind != ACCEL_NONE) return *a;
+  for (int rank = 0; rank < Scene::NUM_ACCELS; rank++)
+    for (const SlotRow& r : SCENE_SLOTS)
+      if (r.exportRank == rank && (s->*r.accel).kind != ACCEL_NONE) return s->*r.accel;
   return s->triAccel;
 }
 
@@ -851,7 +851,7 @@ API void rtcamdGetSceneStats(RTCScene h, struct RTCAMDSceneStats* st)
   st->branching = 8;
   st->nodeCount = A.nodeCount();
   st->nodeBytes = A.nodeStride(); // QNode8, or QNodeMB8 in the kinds 26..29 (the kinds 30 .. 35: their QNode8s; the QNodeMB8s behind them are counted in blobOffsets)
-  const bool tri = A.kind == ACCEL_TRI_PLUECKER || A.kind == ACCEL_TRI_MOELLER;
+  const bool tri = kind_row(A.kind).primsInPrims;
   st->primCount = tri ? A.prims.size() : (A.blobStride ? A.blobs.size() / A.blobStride : 0);
   st->primBytes = tri ? sizeof(TriRecord) : A.blobStride;
   st->leafCount = A.leafCount;
@@ -883,18 +883,18 @@ API void rtcamdOccluded1MCounted(RTCScene h, struct RTCIntersectContext* ctx, st
   CATCH_END(devOf(h))
 }
 
-API const void* rtcamdGetAccelData(RTCScene h, unsigned int kind, size_t* byteSize)
+API const void* rtcamdGetAccelData(RTCScene h, unsigned int array, size_t* byteSize) // (`array`: the header's data `kind`, not an AccelKind)
 {
   CATCH_BEGIN
   VERIFY(h);
   if (S(h)->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "scene got not committed");
-  // kinds 16..19: the arrays 0..3 of the subdivision instance accel, whatever else the scene holds
-  const bool instSubdiv = kind >= 16 && kind < 20;
+  // 16..19: the arrays 0..3 of the subdivision instance accel, whatever else the scene holds
+  const bool instSubdiv = array >= 16 && array < 20;
   const Accel& A = instSubdiv ? S(h)->instSubdivAccel : exported_accel(S(h));
-  if (instSubdiv) kind -= 16;
+  if (instSubdiv) array -= 16;
   const void* p = nullptr;
   size_t n = 0;
-  switch (kind) {
+  switch (array) {
   case 0: p = A.nodeImageData(); n = A.nodeImageBytes(); break; // (the kinds 30 .. 35: both sections and the padding, as uploaded)
   case 1: p = A.prims.data(); n = A.prims.size() * sizeof(TriRecord); break;
   case 2: p = A.blobs.data(); n = A.blobs.size(); break;
@@ -928,6 +928,20 @@ API void rtcamdDebugHoldCombiner(RTCDevice hdevice, int hold)
 {
   Device* dev = (Device*)hdevice;
   if (dev) dev->combHold.store(hold != 0, std::memory_order_release);
+}
+
+// test hook: the row of ACCEL_KINDS (accel_kinds.h) for `kind` as one word, all ones for a value outside the enum.  Bits 0..5 launcher (the
+// first kind that names the same launch_trace_*), 6 robust, 7..8 node array, 9..10 instance level, 11 general layout, 12 pool form, 13 pool
+// pays, 14 service kernel, 15 level-free, 16 root cull pre-pass, 17..18 octet-only, 19..24 default octLeaf, 25 primitives in `prims`
+// (rtc.accel_kind_row decodes it)
+API unsigned int rtcamdDebugAccelKindRow(unsigned int kind)
+{
+  if (!(kind < NUM_ACCEL_KINDS)) return 0xFFFFFFFFu;
+  const KindRow& K = ACCEL_KINDS[kind];
+  unsigned launcher = 0;
+  while (ACCEL_KINDS[launcher].trace != K.trace) launcher++;
+  return launcher | K.robust << 6 | (unsigned)K.nodes << 7 | (unsigned)K.inst << 9 | K.instGeneral << 11 | K.pool << 12 | K.poolPays << 13 | (K.serve != nullptr) << 14 |
+         K.levelFree << 15 | K.cull << 16 | (unsigned)K.octOnly << 17 | (unsigned)K.octLeaf << 19 | K.primsInPrims << 25;
 }
 
 API void rtcamdDebugCbvhLeafCodec(const float* box, const float* v, float extent, unsigned char* bytesOut, float* extentEstimate)

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 
-#include "accel.h"
+#include "accel_kinds.h"
 
 namespace rtamd {
 
@@ -89,16 +89,6 @@ struct ServiceParams
   uint32_t* stop;      // host-mapped: non-zero = leave now
   uint32_t* activity;  // device word: jobs served by any wavefront
 };
-// start the service kernel for base.accel.kind (and base.cbvhLevels); hipErrorInvalidValue: no service kernel for this accel kind / level
-// (the motion-blur triangle, quad and line accels, the line accel, the curve accels and the instance accel have none: rt_service.cpp hands their small calls to the combiner)
-hipError_t launch_service_tri(const ServiceParams& s, hipStream_t stream);       // trace_tri.hip
-hipError_t launch_service_quad(const ServiceParams& s, hipStream_t stream);      // trace_quad.hip
-hipError_t launch_service_grid(const ServiceParams& s, hipStream_t stream);      // trace_grid.hip
-hipError_t launch_service_cbvh_box(const ServiceParams& s, hipStream_t stream);  // trace_cbvh_box.hip  (one unit per cBVH mode:
-hipError_t launch_service_cbvh_leaf(const ServiceParams& s, hipStream_t stream); // trace_cbvh_leaf.hip  trace_cbvh.hip.h
-hipError_t launch_service_cbvh_grid(const ServiceParams& s, hipStream_t stream); // trace_cbvh_grid.hip  instantiated for
-hipError_t launch_service_cbvh_full(const ServiceParams& s, hipStream_t stream); // trace_cbvh_full.hip  that mode)
-
 static const int TRACE_QUEUES = 64;       // work queues per launch (must equal the wavefront width: one lane scans one head)
 static const int TRACE_QUEUE_STRIDE = 32; // u32 words between two work-queue heads (128 B: one L2 line each)
 #ifndef TRACE_BLOCK_THREADS
@@ -122,107 +112,27 @@ static const int TRACE_LDS_STACK = TRACE_LDS_STACK_ENTRIES; // stack entries per
 // Number of workgroups of the persistent grid for `count` rays on a chip with `numCUs` compute units.
 uint32_t trace_grid_blocks(uint32_t count, int numCUs, uint32_t rayChunk);
 
-// Enqueue traversal of one batch on `stream`.  Asynchronous; errors surface through the returned hipError_t.
-hipError_t launch_trace_tri(const LaunchParams& p, hipStream_t stream);       // trace_tri.hip
+// (the launchers of the kinds, launch_trace_* and launch_service_*, are declared beside the table that names them: accel_kinds.h)
 hipError_t launch_cull(const LaunchParams& p, hipStream_t stream);            // trace_tri.hip (trace_cull.hip.h): root cull pre-pass
-hipError_t launch_trace_quad(const LaunchParams& p, hipStream_t stream);      // trace_quad.hip
-hipError_t launch_trace_trimb(const LaunchParams& p, hipStream_t stream);     // trace_tri_mb.hip (swept and linear-bounds kinds)
-hipError_t launch_trace_quadmb(const LaunchParams& p, hipStream_t stream);    // trace_quad_mb.hip (swept and linear-bounds kinds)
-hipError_t launch_trace_grid(const LaunchParams& p, hipStream_t stream);      // trace_grid.hip
-hipError_t launch_trace_cbvh_box(const LaunchParams& p, hipStream_t stream);  // trace_cbvh_box.hip
-hipError_t launch_trace_cbvh_leaf(const LaunchParams& p, hipStream_t stream); // trace_cbvh_leaf.hip
-hipError_t launch_trace_cbvh_grid(const LaunchParams& p, hipStream_t stream); // trace_cbvh_grid.hip
-hipError_t launch_trace_cbvh_full(const LaunchParams& p, hipStream_t stream); // trace_cbvh_full.hip
-hipError_t launch_trace_line(const LaunchParams& p, hipStream_t stream);      // trace_line.hip (flat linear curves; no service kernel)
-hipError_t launch_trace_line_mb(const LaunchParams& p, hipStream_t stream);   // trace_line_mb.hip (flat linear curves with time steps; lane kernel only)
-hipError_t launch_trace_curve(const LaunchParams& p, hipStream_t stream);     // trace_curve.hip (flat Bezier / B-spline curves; lane kernel only, no service kernel)
-hipError_t launch_trace_curve_mb(const LaunchParams& p, hipStream_t stream);  // trace_curve_mb.hip (flat Bezier / B-spline curves with time steps; lane kernel only)
-hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  // trace_instance.hip
-hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb.hip
-hipError_t launch_trace_instance_subdiv(const LaunchParams& p, hipStream_t stream);  // trace_instance_subdiv.hip
-hipError_t launch_trace_instance_mesh_mb_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb_linear.hip
-hipError_t launch_trace_instance_top_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_top_linear.hip (closest hit, any hit and its own EXCL form)
-hipError_t launch_trace_instance_subdiv_top_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_subdiv_top_linear.hip (no EXCL form: filters stay refused)
 // the mesh-instance launchers of the kinds 14..23, 30, 31 hand a launch with exclOffsets != nullptr (a filter re-trace below an instance, closest hit only) to this one
 hipError_t launch_trace_instance_filter(const LaunchParams& p, hipStream_t stream); // trace_instance_filter.hip
 // Development builds (-DTRACE_DEV_METRIC_ONLY, tools/README.md): of the subdivision accels only the metric's kind is dispatched (the
 // others fail with hipErrorInvalidValue, so that only trace_cbvh_leaf.hip has to be rebuilt), and launch_service serves no other kind.
 inline hipError_t launch_service(const ServiceParams& s, hipStream_t stream)
 {
-  switch (s.base.accel.kind) {
-#ifndef TRACE_DEV_METRIC_ONLY
-  case ACCEL_TRI_PLUECKER:
-  case ACCEL_TRI_MOELLER: return launch_service_tri(s, stream);
-  case ACCEL_QUAD_PLUECKER:
-  case ACCEL_QUAD_MOELLER: return launch_service_quad(s, stream);
-  case ACCEL_GRIDSOA: return launch_service_grid(s, stream);
-  case ACCEL_CBVH_BOX: return launch_service_cbvh_box(s, stream);
-  case ACCEL_CBVH_GRID: return launch_service_cbvh_grid(s, stream);
-  case ACCEL_CBVH_FULL: return launch_service_cbvh_full(s, stream);
+  const auto serve = kind_row(s.base.accel.kind).serve;
+#ifdef TRACE_DEV_METRIC_ONLY
+  if (serve != launch_service_cbvh_leaf) return hipErrorInvalidValue;
 #endif
-  case ACCEL_CBVH_LEAF: return launch_service_cbvh_leaf(s, stream);
-  default: return hipErrorInvalidValue;
-  }
+  return serve ? serve(s, stream) : hipErrorInvalidValue;
 }
 inline hipError_t launch_trace(const LaunchParams& p, hipStream_t stream)
 {
-  switch (p.accel.kind) {
-  case ACCEL_TRI_PLUECKER:
-  case ACCEL_TRI_MOELLER: return launch_trace_tri(p, stream);
-  case ACCEL_QUAD_PLUECKER:
-  case ACCEL_QUAD_MOELLER: return launch_trace_quad(p, stream);
-  case ACCEL_TRIMB_PLUECKER:
-  case ACCEL_TRIMB_MOELLER:
-  case ACCEL_TRIMB_LINEAR_PLUECKER:
-  case ACCEL_TRIMB_LINEAR_MOELLER: return launch_trace_trimb(p, stream);
-  case ACCEL_QUADMB_PLUECKER:
-  case ACCEL_QUADMB_MOELLER:
-  case ACCEL_QUADMB_LINEAR_PLUECKER:
-  case ACCEL_QUADMB_LINEAR_MOELLER: return launch_trace_quadmb(p, stream);
-  case ACCEL_LINE_ROBUST:
-  case ACCEL_LINE_FAST: return launch_trace_line(p, stream);
-  case ACCEL_LINEMB_ROBUST:
-  case ACCEL_LINEMB_FAST:
-  case ACCEL_LINEMB_LINEAR_ROBUST:
-  case ACCEL_LINEMB_LINEAR_FAST: return launch_trace_line_mb(p, stream);
-  case ACCEL_CURVE_ROBUST:
-  case ACCEL_CURVE_FAST: return launch_trace_curve(p, stream);
-  case ACCEL_CURVEMB_ROBUST:
-  case ACCEL_CURVEMB_FAST:
-  case ACCEL_CURVEMB_LINEAR_ROBUST:
-  case ACCEL_CURVEMB_LINEAR_FAST: return launch_trace_curve_mb(p, stream);
-  case ACCEL_INST_TRI_PLUECKER:
-  case ACCEL_INST_TRI_MOELLER:
-  case ACCEL_INST_PLUECKER:
-  case ACCEL_INST_MOELLER:
-  case ACCEL_INSTMB_TRI_PLUECKER:
-  case ACCEL_INSTMB_TRI_MOELLER:
-  case ACCEL_INSTMB_PLUECKER:
-  case ACCEL_INSTMB_MOELLER: return launch_trace_instance(p, stream);
-  case ACCEL_INSTMESHMB_PLUECKER:
-  case ACCEL_INSTMESHMB_MOELLER: return launch_trace_instance_mesh_mb(p, stream);
-  case ACCEL_INSTSUBDIV_GRID:
-  case ACCEL_INSTSUBDIV_CBVH_LEAF: return launch_trace_instance_subdiv(p, stream);
-  case ACCEL_INSTMESHMB_LINEAR_PLUECKER:
-  case ACCEL_INSTMESHMB_LINEAR_MOELLER: return launch_trace_instance_mesh_mb_linear(p, stream);
-  case ACCEL_INSTTOP_LINEAR_PLUECKER:
-  case ACCEL_INSTTOP_LINEAR_MOELLER: return launch_trace_instance_top_linear(p, stream);
-  case ACCEL_INSTSUBDIV_TOP_LINEAR_GRID:
-  case ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF: return launch_trace_instance_subdiv_top_linear(p, stream);
-  case ACCEL_CBVH_LEAF: return launch_trace_cbvh_leaf(p, stream);
+  const auto trace = kind_row(p.accel.kind).trace;
 #ifdef TRACE_DEV_METRIC_ONLY
-  case ACCEL_GRIDSOA:
-  case ACCEL_CBVH_BOX:
-  case ACCEL_CBVH_GRID:
-  case ACCEL_CBVH_FULL: return hipErrorInvalidValue;
-#else
-  case ACCEL_GRIDSOA: return launch_trace_grid(p, stream);
-  case ACCEL_CBVH_BOX: return launch_trace_cbvh_box(p, stream);
-  case ACCEL_CBVH_GRID: return launch_trace_cbvh_grid(p, stream);
-  case ACCEL_CBVH_FULL: return launch_trace_cbvh_full(p, stream);
+  if (trace == launch_trace_grid || trace == launch_trace_cbvh_box || trace == launch_trace_cbvh_grid || trace == launch_trace_cbvh_full) return hipErrorInvalidValue;
 #endif
-  default: return hipSuccess;
-  }
+  return trace ? trace(p, stream) : hipSuccess;
 }
 
 } // namespace rtamd

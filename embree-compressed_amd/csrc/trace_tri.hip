@@ -144,9 +144,8 @@ template <bool PLUECKER> struct TriLeaf : LeafTraits
 hipError_t launch_cull(const LaunchParams& p, hipStream_t stream)
 {
   // every subdivision accel, Triangle4v and the Pluecker quads traverse robustly, Triangle4 and the Moeller quads with the fast test
-  // (same choice as the traversal kernels)
-  const bool robust = p.accel.kind != ACCEL_TRI_MOELLER && p.accel.kind != ACCEL_QUAD_MOELLER && p.accel.kind != ACCEL_TRIMB_MOELLER && p.accel.kind != ACCEL_QUADMB_MOELLER;
-  if (robust) return p.occluded ? dev::launch_cull_vec<true, true>(p, stream) : dev::launch_cull_vec<true, false>(p, stream);
+  // (same choice as the traversal kernels: the kind's row, accel_kinds.h)
+  if (kind_row(p.accel.kind).robust) return p.occluded ? dev::launch_cull_vec<true, true>(p, stream) : dev::launch_cull_vec<true, false>(p, stream);
   return p.occluded ? dev::launch_cull_vec<false, true>(p, stream) : dev::launch_cull_vec<false, false>(p, stream);
 }
 

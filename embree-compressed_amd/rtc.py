@@ -249,6 +249,7 @@ def load_library(path=LIB_PATH):
         "rtcamdDebugHoldCombiner": (None, [vp, C.c_int]),
         "rtcamdDebugCbvhLeafCodec": (None, [vp, vp, C.c_float, vp, C.POINTER(C.c_float)]),
         "rtcamdDebugHostPoolSelfTest": (C.c_ulonglong, [vp, u, u, u, u]),
+        "rtcamdDebugAccelKindRow": (u, [u]),
     }
     for name, (res, args) in sig.items():
         if (name.startswith("rtcamdDebug") or name in ("rtcamdGetGeometryWorld2Local", "rtcamdGetSceneFilterFlags")) and not hasattr(lib, name):
@@ -267,6 +268,24 @@ def lib():
     if _lib is None:
         _lib = load_library()
     return _lib
+
+
+# rtcamdDebugAccelKindRow: the fields of a kind's row in csrc/accel_kinds.h as (name, first bit, bits); the enums in their order there
+_KIND_ROW_FIELDS = (("launcher", 0, 6), ("robust", 6, 1), ("nodes", 7, 2), ("inst", 9, 2), ("instGeneral", 11, 1), ("pool", 12, 1), ("poolPays", 13, 1),
+                    ("service", 14, 1), ("levelFree", 15, 1), ("cull", 16, 1), ("octOnly", 17, 2), ("octLeaf", 19, 6), ("primsInPrims", 25, 1))
+KIND_NODES = ("qnode8", "qnodemb8", "two_section")
+KIND_INST = ("none", "mesh", "subdiv")
+KIND_OCT = ("never", "always", "quad_form")
+
+
+def accel_kind_row(kind):
+    """What the library knows about accel kind `kind` (the row of csrc/accel_kinds.h) as a dict of small integers, None for a value that
+    is no accel kind.  launcher: the first kind traced by the same launch_trace_* (0: none); nodes / inst / octOnly index KIND_NODES /
+    KIND_INST / KIND_OCT."""
+    w = lib().rtcamdDebugAccelKindRow(kind)
+    if w == 0xFFFFFFFF:
+        return None
+    return {name: (w >> lo) & ((1 << n) - 1) for name, lo, n in _KIND_ROW_FIELDS}
 
 
 class RTCError(RuntimeError):

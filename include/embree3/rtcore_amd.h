@@ -153,6 +153,9 @@ RTC_API void rtcamdDebugCbvhLeafCodec(const float* box, const float* v, float ex
  * chunked pipeline of large host-pointer batches; `threads` helpers are started if fewer exist), in `cycles` begin / end cycles,
  * and returns the number of parts that ran exactly once with the right index.  Works on a gpu=none device: CPU-side coverage of the pool. */
 RTC_API unsigned long long rtcamdDebugHostPoolSelfTest(RTCDevice device, unsigned int threads, unsigned int cycles, unsigned int jobs, unsigned int parts);
+/* Test hook: what the library knows about an accel kind (RTCAMDSceneStats::accelKind; the table of csrc/accel_kinds.h) as one word - the
+ * bit layout is documented at the definition - and all ones for a value that is no accel kind. */
+RTC_API unsigned int rtcamdDebugAccelKindRow(unsigned int kind);
 /* Root reference of the BVH8 (encoding documented in DESIGN.md / csrc/accel.h). */
 RTC_API unsigned int rtcamdGetAccelRoot(RTCScene scene);
 /* The geometry filter functions the scene's last commit saw - what routes a batch through the host filter loop: on its own enabled

@@ -1,11 +1,12 @@
 """Development probe: host-side cost of one device-resident rtcIntersect1M call (Python/ctypes + launch-context pick +
 memset + launch + event record), measured by enqueuing many tiny batches without synchronising in between."""
-import importlib, sys, time
-sys.path.insert(0, '/root/repo')
+import importlib, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 rtc = importlib.import_module('embree-compressed_amd').rtc
 raygen = importlib.import_module('embree-compressed_amd.raygen')
-d = np.load('/root/repo/assets/bomberman.mesh.npz'); v, fs, fi = d['verts'], d['face_sizes'], d['face_index']
+d = np.load(os.path.join(ROOT, 'assets', 'bomberman.mesh.npz')); v, fs, fi = d['verts'], d['face_sizes'], d['face_index']
 dev = rtc.Device('gpu=0,tri_accel=bvh8.triangle4v'); sc = rtc.Scene(dev)
 sc.add_triangles(v, rtc.fan_triangulate(fs, fi)); sc.commit()
 buf = torch.from_numpy(raygen.make_random_rays(64, v.min(0), v.max(0), seed=1)).cuda()

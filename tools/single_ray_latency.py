@@ -2,14 +2,15 @@
 Launches of a single ray (count = 1): kernel time = launch floor + the ray's own critical path.  A least-squares fit
 time = a + b*nodes + c*leaves over rays of different depth gives the cost of one dependent node step / leaf visit.
 usage: single_ray_latency.py [workload cbvh.leaf|eager|tri] [n candidate rays]"""
-import importlib, sys, time
-sys.path.insert(0, '/root/repo')
+import importlib, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np, torch
 rtc = importlib.import_module('embree-compressed_amd').rtc
 raygen = importlib.import_module('embree-compressed_amd.raygen')
 wl = sys.argv[1] if len(sys.argv) > 1 else 'cbvh.leaf'
 ncand = int(sys.argv[2]) if len(sys.argv) > 2 else 4000
-d = np.load('/root/repo/assets/bomberman.mesh.npz'); v, fs, fi = d['verts'], d['face_sizes'], d['face_index']
+d = np.load(os.path.join(ROOT, 'assets', 'bomberman.mesh.npz')); v, fs, fi = d['verts'], d['face_sizes'], d['face_index']
 if wl == 'tri':
     dev = rtc.Device('gpu=0,tri_accel=bvh8.triangle4v'); sc = rtc.Scene(dev)
     tris = []

@@ -18,6 +18,7 @@
 // The reference keeps the same information behind 64-bit tagged pointers (kernels/bvh/bvh.h:150-396,
 // AlignedNode :433-594, QuantizedNode :1150-1324, Triangle4v kernels/geometry/trianglev.h:24-162).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
@@ -308,6 +309,15 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // (byte offset of the QuadMBRecord section) / 128 + the scene's base: the kernel indexes `blobs` as ONE array of that record type.
 // Every rebased first record must stay below 2^26.  Inside an instance the trees are traversed one after the other, each against the
 // tfar the previous one left; while a tree is traversed the later ones wait on the stack as markers (REF_INST_TREE).
+// With line segments or flat curves below an instance (device config inst_hair=1; Accel::instHair, LaunchParams::instHair - the kinds stay
+// 22 / 23, also when nothing below the instances moves) a scene has up to six trees, the curve and the line tree last:
+//   nodes : ... | scene 0: triangle, MB triangle, quad, MB quad, curve, line nodes | scene 1: ... | ...
+//   blobs : ... the QuadMBRecords | zero padding to a multiple of 80 bytes | scene 0's CurveRecords | scene 1's | ... |
+//           zero padding to a multiple of 48 bytes | scene 0's LineRecords | scene 1's | ...
+// and every InstanceSceneRecord of the accel holds curveRoot and lineRoot in words 4 and 5 (REF_EMPTY for a missing tree).  A curve leaf is
+// rebased by (byte offset of the CurveRecord section) / 80 + the scene's base, a line leaf by (byte offset of the LineRecord section) / 48 +
+// the scene's base: CurveLeaf::intersect and LineLeaf::intersect index `blobs` as ONE array of their record type.  An accel without such
+// trees ends behind the QuadMBRecords and keeps words 4 and 5 of its scene records zero, byte for byte what it was before the key existed.
 //
 // Kinds ACCEL_INSTMESHMB_LINEAR_PLUECKER / _MOELLER (inst_mb_bounds=linear over scenes built under mb_bounds=linear): `prims` and `blobs`
 // are those of the kinds ACCEL_INSTMESHMB_*; the motion-blur trees keep their time-dependent nodes, so the node array has two sections:
@@ -396,12 +406,17 @@ static const uint32_t REF_INST_QUADS = 0x80000001u;
 static_assert(sizeof(InstanceRecord) == sizeof(QuadRecord), "the instance kernel indexes InstanceRecords and QuadRecords as one array");
 // The roots of one instanced scene (kinds ACCEL_INSTMESHMB_*), 64 bytes, of which the kernel loads the first dwordx4.  INST_TREE_*: the
 // code of a tree = of the leaf kind the lane runs while it is in that tree; roots[] is in visiting order.
-enum : uint32_t { INST_TREE_TRI = 0, INST_TREE_QUAD = 1, INST_TREE_TRIMB = 2, INST_TREE_QUADMB = 3 };
+// inst_hair=1 (an accel with Accel::instHair set): the scene's curve and line tree follow in the second dwordx4, which the kernel's HAIR form
+// loads as well; their codes keep bit 1 clear ("bit 1 = a motion-blur tree").  Visiting order: triangles, motion-blur triangles, quads,
+// motion-blur quads, curves, lines (Scene::commit's).  An accel without hair trees keeps these two words zero and is never read there.
+enum : uint32_t { INST_TREE_TRI = 0, INST_TREE_QUAD = 1, INST_TREE_TRIMB = 2, INST_TREE_QUADMB = 3, INST_TREE_CURVE = 4, INST_TREE_LINE = 5 };
 struct alignas(16) InstanceSceneRecord
 {
   uint32_t triRoot, triMBRoot, quadRoot, quadMBRoot; // rebased root references, REF_EMPTY for a missing tree
-  uint32_t pad[12];                                  // zero
+  uint32_t curveRoot, lineRoot;                      // (words 4 and 5) accels with hair trees: the same for the curve and the line tree; zero otherwise
+  uint32_t pad[10];                                  // zero
 };
+static_assert(offsetof(InstanceSceneRecord, curveRoot) == 16 && offsetof(InstanceSceneRecord, lineRoot) == 20, "the hair roots lead the second dwordx4");
 static_assert(sizeof(InstanceSceneRecord) == sizeof(InstanceRecord), "the instance kernel indexes InstanceRecords and InstanceSceneRecords as one array");
 // Markers of the kernel's MESHMB form, one value per pending tree: REF_INST_TREE(code), stacked above the exit marker in reverse
 // visiting order with the tree's root in the distance word; popping one switches the lane's leaf kind to `code` and continues at that

@@ -347,6 +347,7 @@ struct MeshInstances
   bool anyMotion = false;     // an instance has more than one time step
   bool anyMeshMotion = false; // an instanced scene has a traceable motion-blur accel
   bool anyLinear = false;     // ... built under mb_bounds=linear (kinds 26..29): its nodes are QNodeMB8s
+  bool anyHair = false;       // inst_hair=1: an instanced scene has a traceable curve or line accel (the kinds ACCEL_INSTMESHMB_* with Accel::instHair)
   bool topLinear = false;     // inst_bounds=linear and anyMotion: the top-level tree is made of QNodeMB8s (kinds ACCEL_INSTTOP_LINEAR_*)
   uint32_t pendingMax = 0;    // most trees of one instanced scene, minus one
   bool intersectFilter = false, occludedFilter = false; // inst_filters=1: an enabled geometry of a placed instance's scene has such a filter
@@ -365,6 +366,11 @@ struct MeshInstances
 // placed here gets the kinds ACCEL_INSTTOP_LINEAR_*; one without keeps its kind and bytes.  Moving meshes below the instances of such a
 // top scene must come as QNodeMB8 trees (mb_bounds=linear,inst_mb_bounds=linear), so that one node type serves every motion-blur tree
 // of the kernel's TOPMB form; otherwise the commit is refused with a message that names the three keys.
+// Line segments and flat curves below an instance (inst_hair=1, Device::inst_hair_lines_enabled / inst_hair_curves_enabled): an instanced
+// scene may enable such geometries with one time step, alone or beside its meshes; its curve and line accels join the agreement in
+// arithmetic (their robust / fast traversal).  A top scene with any such tree below it is of the kinds ACCEL_INSTMESHMB_*, over swept
+// boxes only: beside a linear kind, and beside geometry filters below the instances (the hair form of the kernel has no exclusion scan),
+// the commit is refused.  Without the key every refusal is what it was.
 // Subdivision scenes below an instance: an instanced scene that enables a subdivision mesh is left to build_instance_subdiv_accel when
 // the device takes such scenes (Device::inst_subdiv_enabled); otherwise it is refused here with the message of the config, as before.
 MeshInstances classify_mesh_instances(const Scene* s)
@@ -384,6 +390,10 @@ MeshInstances classify_mesh_instances(const Scene* s)
   // inst_filters=1: the meshes of an instanced scene may carry filter functions; what THIS commit sees of them is recorded below, for the
   // scenes of the instances that are placed (as Scene::commit records triIntersectFilter / triOccludedFilter of its own meshes)
   const bool filtersOk = s->device->inst_filters;
+  const bool hairLinesOk = s->device->inst_hair_lines_enabled(), hairCurvesOk = s->device->inst_hair_curves_enabled();
+  auto at_instance = [](const char* text, unsigned gid) { return std::string(text) + " (instance " + std::to_string(gid) + ")"; };
+  unsigned hairGeom = 0, filterGeom = 0; // the first instance whose scene holds hair / a geometry filter: named by the refusals behind the loop
+  bool anyFilter = false;
   // inst_bounds=linear: will this top scene get the time-dependent top level?  Known before the scenes are examined, so that the refusal of
   // moving meshes below it has its own text from the first instance on (a moving instance of an empty scene is not placed and does not count)
   bool wantTopLinear = false;
@@ -414,20 +424,28 @@ MeshInstances classify_mesh_instances(const Scene* s)
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "an instanced scene with a motion blur accel built under mb_bounds=linear is not supported (instance accels hold swept node boxes: use mb_bounds=swept)");
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
+      if (og->isFlatCubicCurve() ? hairCurvesOk : (og->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && hairLinesOk)) { // inst_hair=1
+        if (og->timeSteps != 1)
+          RT_THROW(RTC_ERROR_INVALID_OPERATION, at_instance("motion blur of line segments and flat curves inside an instanced scene is not supported", gid));
+        if (!filtersOk && (og->intersectFilter || og->occludedFilter)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
+        continue;
+      }
       if (og->isFlatCubicCurve()) RT_THROW(RTC_ERROR_INVALID_OPERATION, "flat Bezier and B-spline curves inside an instanced scene are not supported");
       const bool mesh = og->type == RTC_GEOMETRY_TYPE_TRIANGLE || (quadsOk && og->type == RTC_GEOMETRY_TYPE_QUAD);
       if (!mesh || (og->timeSteps != 1 && !meshMotionOk)) RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
       if (!filtersOk && (og->intersectFilter || og->occludedFilter)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
     }
     for (const Accel* oa : o->accels())
-      if (oa != &o->triAccel && !(quadsOk && oa == &o->quadAccel) && !(meshMotionOk && (oa == &o->triMBAccel || oa == &o->quadMBAccel)) && oa->kind != ACCEL_NONE)
+      if (oa != &o->triAccel && !(quadsOk && oa == &o->quadAccel) && !(meshMotionOk && (oa == &o->triMBAccel || oa == &o->quadMBAccel)) &&
+          !(hairCurvesOk && oa == &o->curveAccel) && !(hairLinesOk && oa == &o->lineAccel) && oa->kind != ACCEL_NONE)
         RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
     if (!filtersOk && (o->triIntersectFilter || o->triOccludedFilter)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
     const bool tris = o->triAccel.traceable(), quads = o->quadAccel.traceable();
     const bool trisMB = o->triMBAccel.traceable(), quadsMB = o->quadMBAccel.traceable();
-    if (!tris && !quads && !trisMB && !quadsMB) continue; // empty scene: nothing to hit
+    const bool curves = hairCurvesOk && o->curveAccel.traceable(), lines = hairLinesOk && o->lineAccel.traceable();
+    if (!tris && !quads && !trisMB && !quadsMB && !curves && !lines) continue; // empty scene: nothing to hit
     std::string names; // this scene's traceable accels
-    for (const char* nm : {tris ? "triangle" : "", trisMB ? "motion blur triangle" : "", quads ? "quad" : "", quadsMB ? "motion blur quad" : ""})
+    for (const char* nm : {tris ? "triangle" : "", trisMB ? "motion blur triangle" : "", quads ? "quad" : "", quadsMB ? "motion blur quad" : "", curves ? "curve" : "", lines ? "line" : ""})
       if (*nm) names += std::string(names.empty() ? "" : ", ") + nm;
     // scenes that disagree while a motion-blur accel is involved: the message names the accels on either side
     auto disagree = [&](bool thisPl) {
@@ -435,12 +453,14 @@ MeshInstances classify_mesh_instances(const Scene* s)
       return "the instanced scenes of one scene disagree in accel kind (Pluecker / robust and Moeller / fast): the scene of instance " + std::to_string(gid) + " has " +
              ar[thisPl] + " accels (" + names + "), the scene of instance " + std::to_string(kindGeom) + " " + ar[!thisPl] + " ones (" + kindNames + "): instances need one arithmetic";
     };
-    if (trisMB || quadsMB) {
-      // one arithmetic per top scene, over all four trees of every instanced scene
-      struct { bool have, pl; const char* name; } const t[4] = {{tris, o->triAccel.kind == ACCEL_TRI_PLUECKER, "triangle"},
+    if (trisMB || quadsMB || curves || lines) {
+      // one arithmetic per top scene, over all six trees of every instanced scene
+      struct { bool have, pl; const char* name; } const t[6] = {{tris, o->triAccel.kind == ACCEL_TRI_PLUECKER, "triangle"},
                                                                 {trisMB, kind_row(o->triMBAccel.kind).robust, "motion blur triangle"},
                                                                 {quads, o->quadAccel.kind == ACCEL_QUAD_PLUECKER, "quad"},
-                                                                {quadsMB, kind_row(o->quadMBAccel.kind).robust, "motion blur quad"}};
+                                                                {quadsMB, kind_row(o->quadMBAccel.kind).robust, "motion blur quad"},
+                                                                {curves, kind_row(o->curveAccel.kind).robust, "curve"},
+                                                                {lines, kind_row(o->lineAccel.kind).robust, "line"}};
       std::string pl, mo;
       for (const auto& e : t)
         if (e.have) (e.pl ? pl : mo) += std::string((e.pl ? pl : mo).empty() ? "" : ", ") + e.name;
@@ -448,11 +468,15 @@ MeshInstances classify_mesh_instances(const Scene* s)
         RT_THROW(RTC_ERROR_INVALID_OPERATION, "the accels of an instanced scene disagree in kind (Pluecker / robust: " + pl + "; Moeller / fast: " + mo + "): instances need one arithmetic");
       const bool scenePl = !pl.empty();
       if (haveKind && scenePl != c.pluecker) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(scenePl));
-      c.anyMeshMotion = true;
+      if (curves || lines) {
+        if (!c.anyHair) hairGeom = gid;
+        c.anyHair = true;
+      }
+      c.anyMeshMotion |= trisMB || quadsMB;
       for (const Accel* m : {trisMB ? &o->triMBAccel : nullptr, quadsMB ? &o->quadMBAccel : nullptr})
         if (m) (m->nodesAreMB() ? c.anyLinear : anySwept) = true;
     }
-    c.pendingMax = std::max(c.pendingMax, (uint32_t)tris + (uint32_t)trisMB + (uint32_t)quads + (uint32_t)quadsMB - 1u);
+    c.pendingMax = std::max(c.pendingMax, (uint32_t)tris + (uint32_t)trisMB + (uint32_t)quads + (uint32_t)quadsMB + (uint32_t)curves + (uint32_t)lines - 1u);
     // the kernel runs ONE arithmetic on both levels and in both leaves: every accel below this scene is Pluecker / robust, or every one
     // Moeller / fast
     if (tris && quads && (o->triAccel.kind == ACCEL_TRI_PLUECKER) != (o->quadAccel.kind == ACCEL_QUAD_PLUECKER))
@@ -460,10 +484,10 @@ MeshInstances classify_mesh_instances(const Scene* s)
                                             "as a robust scene under quad_accel=bvh8.quad4v builds them): instances need one arithmetic");
     const bool pl = tris ? o->triAccel.kind == ACCEL_TRI_PLUECKER
                   : quads ? o->quadAccel.kind == ACCEL_QUAD_PLUECKER
-                  : kind_row(trisMB ? o->triMBAccel.kind : o->quadMBAccel.kind).robust;
+                  : kind_row(trisMB ? o->triMBAccel.kind : quadsMB ? o->quadMBAccel.kind : curves ? o->curveAccel.kind : o->lineAccel.kind).robust;
     if (haveKind && pl != c.pluecker) {
-      if (!c.anyQuads && !quads && !c.anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
-      if (c.anyMeshMotion) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(pl));
+      if (!c.anyQuads && !quads && !c.anyMeshMotion && !c.anyHair) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
+      if (c.anyMeshMotion || c.anyHair) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(pl));
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in accel kind (Pluecker / robust and Moeller / fast): instances need one arithmetic");
     }
     if (!haveKind) {
@@ -479,11 +503,20 @@ MeshInstances classify_mesh_instances(const Scene* s)
       if (!og || !og->enabled) continue;
       c.intersectFilter |= og->intersectFilter != nullptr;
       c.occludedFilter |= og->occludedFilter != nullptr;
+      if ((og->intersectFilter || og->occludedFilter) && !anyFilter) {
+        anyFilter = true;
+        filterGeom = gid;
+      }
     }
   }
   if (c.anyLinear && anySwept) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: motion blur accels of both node types below one scene");
   c.topLinear = c.anyMotion && s->device->inst_top_linear_enabled();
   if (c.topLinear && anySwept) RT_THROW(RTC_ERROR_INVALID_OPERATION, topLinearNeedsLinear);
+  if (c.anyHair && (c.topLinear || c.anyLinear))
+    RT_THROW(RTC_ERROR_INVALID_OPERATION, at_instance("inst_hair=1: line segments and flat curves below an instance are traced over swept boxes only (kinds 22 / 23); not beside "
+                                                      "inst_bounds=linear or inst_mb_bounds=linear trees", hairGeom));
+  if (c.anyHair && anyFilter)
+    RT_THROW(RTC_ERROR_INVALID_OPERATION, at_instance("inst_hair=1: geometry filter functions below the instances of a scene with instanced line segments or flat curves are not supported", filterGeom));
   return c;
 }
 
@@ -492,13 +525,14 @@ MeshInstances classify_mesh_instances(const Scene* s)
 // (kinds ACCEL_INST_PLUECKER / ACCEL_INST_MOELLER).  As soon as one enabled instance has more than one time step the kinds are
 // ACCEL_INSTMB_* (chosen otherwise exactly as ACCEL_INST_*); as soon as one instanced scene has a traceable motion-blur accel they are
 // ACCEL_INSTMESHMB_*, and ACCEL_INSTMESHMB_LINEAR_* as soon as one of those accels holds QNodeMB8s.  A top scene without a motion-blur
-// accel below it keeps the kinds 14..21 and their arrays, whatever the config names.  Under inst_bounds=linear a top scene with a moving
+// accel below it keeps the kinds 14..21 and their arrays, whatever the config names.  A top scene with a curve or line tree below it
+// (inst_hair=1) is of the kinds ACCEL_INSTMESHMB_* too, even when nothing below it moves.  Under inst_bounds=linear a top scene with a moving
 // instance is of the kinds ACCEL_INSTTOP_LINEAR_*, whatever lies below its instances.
 uint32_t instance_kind(const MeshInstances& c)
 {
   if (c.topLinear) return c.pluecker ? ACCEL_INSTTOP_LINEAR_PLUECKER : ACCEL_INSTTOP_LINEAR_MOELLER;
   if (c.anyLinear) return c.pluecker ? ACCEL_INSTMESHMB_LINEAR_PLUECKER : ACCEL_INSTMESHMB_LINEAR_MOELLER;
-  if (c.anyMeshMotion) return c.pluecker ? ACCEL_INSTMESHMB_PLUECKER : ACCEL_INSTMESHMB_MOELLER;
+  if (c.anyMeshMotion || c.anyHair) return c.pluecker ? ACCEL_INSTMESHMB_PLUECKER : ACCEL_INSTMESHMB_MOELLER;
   if (c.anyMotion) return c.anyQuads ? (c.pluecker ? ACCEL_INSTMB_PLUECKER : ACCEL_INSTMB_MOELLER) : (c.pluecker ? ACCEL_INSTMB_TRI_PLUECKER : ACCEL_INSTMB_TRI_MOELLER);
   if (c.anyQuads) return c.pluecker ? ACCEL_INST_PLUECKER : ACCEL_INST_MOELLER;
   return c.pluecker ? ACCEL_INST_TRI_PLUECKER : ACCEL_INST_TRI_MOELLER;
@@ -508,6 +542,8 @@ uint32_t instance_kind(const MeshInstances& c)
 // triangle, motion-blur triangle, quad and motion-blur quad tree (Scene::commit's order), whichever it has.
 //   blobs : InstanceRecords | QuadRecords | InstanceSteps, and with anyMeshMotion (the general layout of accel.h InstanceRecord):
 //           | one InstanceSceneRecord per scene, which holds its four roots | TriMBRecords | QuadMBRecords
+//           and with anyHair: | CurveRecords from a multiple of 80 bytes | LineRecords from a multiple of 48 bytes; the scene records then
+//           hold six roots, REF_EMPTY for a missing hair tree too (without anyHair the two words stay zero, the bytes what they were)
 //   nodes : with anyLinear in two sections - `A.nodes` with the top-level tree and the static trees, `A.nodesMB` with the motion-blur
 //           trees, child indices counted in 144-byte units from the start of the uploaded buffer, and `A.nodeImage` the two with the
 //           padding between them.  With topLinear the top-level tree leads `A.nodesMB` instead of `A.nodes`, and the general layout
@@ -515,7 +551,7 @@ uint32_t instance_kind(const MeshInstances& c)
 // maxDepth (launch_on reserves 7 * (maxDepth + 1) + 2 stack entries) =
 //     the top-level depth
 //   + 1 for the exit marker
-//   + the largest number of pending-tree markers any instanced scene can have stacked at once (its tree count - 1, at most 3; in the
+//   + the largest number of pending-tree markers any instanced scene can have stacked at once (its tree count - 1, at most 5; in the
 //     kinds 14..21: 1 as soon as any scene has quads)
 //   + the deepest of all instanced trees (the trees of a scene are never stacked together: a marker is popped only when the entries
 //     of the tree before it are gone).
@@ -527,7 +563,7 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
   std::vector<QNodeMB8> topMB; // topLinear: the top-level tree, references counted from its own first node
   if (c.topLinear) topMB = build_top_level_linear(s, c.placed, A, order);
   else order = build_top_level(s, c.placed, A);
-  const bool general = c.anyMeshMotion || c.topLinear;   // the layout of `blobs` with InstanceSceneRecords
+  const bool general = c.anyMeshMotion || c.topLinear || c.anyHair; // the layout of `blobs` with InstanceSceneRecords
   const bool twoSections = c.anyLinear || c.topLinear;   // QNodeMB8s behind the QNode8s
 
   // what the distinct scenes bring (an accel that is absent or empty is not traceable and brings nothing)
@@ -539,8 +575,12 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
     n.quads += records(o->quadAccel, sizeof(QuadRecord));
     n.triMB += records(o->triMBAccel, sizeof(TriMBRecord));
     n.quadMB += records(o->quadMBAccel, sizeof(QuadMBRecord));
-    for (const Accel* t : {&o->triAccel, &o->triMBAccel, &o->quadAccel, &o->quadMBAccel})
-      if (t->traceable()) { // a motion-blur tree has nodes of one type or of the other
+    if (c.anyHair) {
+      n.curves += records(o->curveAccel, sizeof(CurveRecord));
+      n.lines += records(o->lineAccel, sizeof(LineRecord));
+    }
+    for (const Accel* t : {&o->triAccel, &o->triMBAccel, &o->quadAccel, &o->quadMBAccel, c.anyHair ? &o->curveAccel : nullptr, c.anyHair ? &o->lineAccel : nullptr})
+      if (t && t->traceable()) { // a motion-blur tree has nodes of one type or of the other
         staticNodes += t->nodes.size();
         mbNodes += t->nodesMB.size();
       }
@@ -549,11 +589,15 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
   add_section(blobBytes, c.placed.size(), sizeof(InstanceRecord)); // (the records start the array: write_instance_records)
   Section quadSec = add_section(blobBytes, n.quads, sizeof(QuadRecord)); // quad leaves index `blobs` as one array of 64-byte records
   Section stepSec = add_section(blobBytes, n.steps, sizeof(InstanceStep));
-  Section sceneSec{}, triMBSec{}, quadMBSec{};
+  Section sceneSec{}, triMBSec{}, quadMBSec{}, curveSec{}, lineSec{};
   if (general) {
     sceneSec = add_section(blobBytes, ds.scenes.size(), sizeof(InstanceSceneRecord));
     triMBSec = add_section(blobBytes, n.triMB, sizeof(TriMBRecord));    // motion-blur triangle leaves index `blobs` as one array of 96-byte records
     quadMBSec = add_section(blobBytes, n.quadMB, sizeof(QuadMBRecord)); // motion-blur quad leaves as one of 128-byte records
+    if (c.anyHair) { // (an accel without hair trees ends behind the QuadMBRecords, as it always did)
+      curveSec = add_section(blobBytes, n.curves, sizeof(CurveRecord)); // curve leaves index `blobs` as one array of 80-byte records (CurveLeaf::intersect)
+      lineSec = add_section(blobBytes, n.lines, sizeof(LineRecord));    // line leaves as one of 48-byte records (LineLeaf::intersect)
+    }
   }
   // the node buffer: the QNode8s, and (kinds ACCEL_INSTMESHMB_LINEAR_*, no others have any) zero padding and the QNodeMB8s from the
   // multiple of 144 bytes their references count from
@@ -593,6 +637,12 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
                                                                                                  "the instance records in one array)"));
     sc.quadMBRoot = append_mb(o->quadMBAccel, place_leaf_records(A.blobs, quadMBSec, o->quadMBAccel, "too many instanced motion blur quad segments for the 26-bit leaf reference (their records "
                                                                                                      "follow all other records in one array)"));
+    if (c.anyHair) { // the curve and the line tree behind the scene's four mesh trees; both are QNode8 trees over static records
+      sc.curveRoot = append_static(o->curveAccel, place_leaf_records(A.blobs, curveSec, o->curveAccel, "too many instanced curves for the 26-bit leaf reference (the curve section: their records "
+                                                                                                       "follow all mesh records in one array)"));
+      sc.lineRoot = append_static(o->lineAccel, place_leaf_records(A.blobs, lineSec, o->lineAccel, "too many instanced line segments for the 26-bit leaf reference (the line section: their records "
+                                                                                                   "follow all other records in one array)"));
+    }
     quadRootOf.push_back(sc.quadRoot);
     rootOf.push_back(general ? (uint32_t)(sceneSec.base() + sceneSec.used) : sc.triRoot); // general layout: the scene's InstanceSceneRecord, in 64-byte units
     if (general) memcpy(A.blobs.data() + sceneSec.offset + sceneSec.used++ * sizeof(sc), &sc, sizeof(sc));
@@ -606,6 +656,7 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
     A.blobOffsets = {(uint32_t)A.nodesMB.size(), (uint32_t)mbSec.base()};
   }
   A.kind = instance_kind(c);
+  A.instHair = c.anyHair;
   A.robust = c.pluecker ? 1 : 0;
   A.maxDepth += 1u + (general ? c.pendingMax : c.anyQuads ? 1u : 0u) + deepest;
   return n;

@@ -245,6 +245,7 @@ void Accel::clear()
   maxDepth = 0;
   blobStride = 0;
   cbvhLevels = 0;
+  instHair = false;
   leafCount = 0;
 }
 
@@ -432,6 +433,8 @@ void Scene::commit()
                     "segment records, %zu instanced motion blur quad segment records, depth %u\n", instAccel.kind,
             instAccel.nodes.size(), instAccel.nodes.size() * sizeof(QNode8), instAccel.leafCount, instAccel.prims.size(),
             nQuads, nTriMB, nQuadMB, instAccel.maxDepth);
+    if (instAccel.instHair) // inst_hair=1 and a curve or line tree below an instance
+      fprintf(stderr, "embree3-amd: instance accel kind %u: %zu instanced curves, %zu instanced line segments\n", instAccel.kind, instCounts.curves, instCounts.lines);
     if (instAccel.twoSections())
       fprintf(stderr, "embree3-amd: instance accel kind %u: %zu time-dependent nodes (%zu B) from node index %u in 144-byte units, node buffer %zu B\n", instAccel.kind,
               instAccel.nodesMB.size(), instAccel.nodesMB.size() * sizeof(QNodeMB8), instAccel.blobOffsets[1], instAccel.nodeImage.size());

@@ -84,6 +84,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
     spillBytes = (size_t)p.gridBlocks * TRACE_BLOCK * (size_t)p.spillDepth * 8u + 16u;
   }
   p.counters = x.counters;
+  p.instHair = A.instHair ? 1u : 0u; // line and curve trees below the instances: the HAIR form of the two-level kernel
   p.cbvhLevels = A.cbvhLevels ? A.cbvhLevels : s->compressionLevel; // (instanced cBVH blobs, kinds 25 / 35, carry the level of the scenes they come from)
   // cBVH blob walk: quad form (four lanes per ray, two-stage visits) or one ray per lane.  Coherent batches (RTC_INTERSECT_CONTEXT_FLAG_COHERENT,
   // e.g. the primary rays of viewer_stream_device.cpp:305) keep most lanes at blobs at once; since the two-stage visits the quad form is the faster
@@ -290,6 +291,9 @@ void trace_batch(Scene* s, void* rays, uint32_t M, size_t byteStride, bool occlu
     // inst_filters=1: taken when all instances are mesh instances (the two-level kernel of subdivision instances has no exclusion scan)
     if (ctx && ctx->filter && (!dev->inst_filters || s->instSubdivAccel.traceable()))
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "RTCIntersectContext::filter is not supported on a scene with instances");
+    // inst_hair=1: the hair form of the two-level kernel has no exclusion scan (the commit has refused geometry filters below such a scene)
+    if (ctx && ctx->filter && s->instAccel.instHair)
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "inst_hair=1: RTCIntersectContext::filter is not supported on a scene with instanced line segments or flat curves");
     if (countersOut) RT_THROW(RTC_ERROR_INVALID_OPERATION, "counted batches are not supported on a scene with instances");
   }
   dev->useDevice();

@@ -48,6 +48,8 @@ struct LaunchParams
   const uint2* exclPairs;
   const uint32_t* exclT;
   uint32_t poolKernel;     // 1: ray-pool skeleton (trace_pool.hip.h), 0: lane-per-ray skeleton (trace_loop.hip.h)
+  uint32_t instHair;       // kinds ACCEL_INSTMESHMB_*: 1 = the accel holds curve or line trees below its instances (Accel::instHair): the HAIR form of
+                           // the two-level kernel (trace_instance_hair.hip).  In what was padding in front of `survivors`: no other member moves
   // Root cull pass (trace_cull.hip.h): when `survivors` is set, a streaming pre-pass has tested every ray against the root node's
   // children and appended the indices of the rays that hit at least one of them to per-work-queue lists: queue q's list starts
   // at survivors[q * perQ] (perQ = ceil(count / TRACE_QUEUES), its capacity) and holds queues[q * TRACE_QUEUE_STRIDE + 1] entries;
@@ -60,6 +62,8 @@ struct LaunchParams
   uint32_t* overflow;      // host-mapped word, set to 1 by a kernel that had to drop a traversal-stack entry (never for a tree
                            // whose depth the builder reported correctly: the overflow area is sized for the worst case)
 };
+
+static_assert(offsetof(LaunchParams, instHair) + 4 == offsetof(LaunchParams, survivors), "instHair fills the padding in front of `survivors`");
 
 // ---- persistent consumer for small calls (trace_service.hip.h, rt_service.cpp) ---------------------------------------------
 static const int SERVICE_SLOT_RAYS = 64; // one wavefront, one ray per lane

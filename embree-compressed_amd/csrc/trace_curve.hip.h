@@ -129,5 +129,114 @@ __device__ __forceinline__ void ribbon_hit(TriHit& h, float t, float U, float V,
   h.ngz = bezier_combine(d0, d1, d2, d3, V0.z, V1.z, V2.z, V3.z);
 }
 
+// The static ribbon leaf (described in trace_curve.hip, which holds its launcher): here so that the hair form of the two-level kernel
+// (trace_instance_hair.hip) runs the same leaf below an instance.
+struct CurveLeaf : LeafTraits
+{
+  // Three waves per SIMD, the bound of the line leaves (at most 168 VGPRs): profiles/curve_kernel_resources.txt
+  static constexpr int MIN_WAVES = 3;
+
+  // Child-parallel form (trace_loop.hip.h): one record per pass - lane k of the octet tests segment base + k of the curve, every lane
+  // against the tfar at pass entry; ONE 8-lane minimum, the lowest lane with that t wins and writes the hit into the row (words 0..7 =
+  // t, Ng, u, v, geomID, primID; word 9 = 1).  A curve with N > 8 takes a second pass, which sees the first one's tfar.  Row word 10 is
+  // the ray's index.  The loops are wave-uniform (every octet runs as many passes as the longest one; the others are masked).
+  template <bool OCCLUDED, bool COUNT>
+  static __device__ __forceinline__ void octet_pass(const LaunchParams& P, float* x, bool valid, uint32_t lid, WorkCounters& wc)
+  {
+    const CurveRecord* __restrict__ recs = (const CurveRecord*)P.accel.blobs;
+    const uint32_t k = lid & 7u;
+    const RayState r = row_ray(x);
+    const LineSpace S = line_space(r);
+    const uint32_t ref = __float_as_uint(x[8]);
+    uint32_t first, cnt;
+    leaf_range(ref, first, cnt);
+    cnt = valid ? cnt : 0u;
+    float tfar = r.tfar;
+    for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i++) {
+      const bool present = i < cnt;
+      const float4* lp = (const float4*)(recs + first + (present ? i : 0u));
+      const float4 V0 = lp[0], V1 = lp[1], V2 = lp[2], V3 = lp[3];
+      const uint4 ids = *(const uint4*)(lp + 4); // geomID, primID, N, pad
+      uint32_t N = present ? ids.z : 0u;
+      const float4 w0 = to_ray_space(r, S, V0), w1 = to_ray_space(r, S, V1), w2 = to_ray_space(r, S, V2), w3 = to_ray_space(r, S, V3);
+      for (uint32_t base = 0; __ballot(base < N) != 0ull; base += 8u) {
+        const uint32_t j = base + k;
+        const bool seg = j < N;
+        if (COUNT && seg) wc.prims++;
+        const RibbonEnd a = ribbon_end(w0, w1, w2, w3, j, N), b = ribbon_end(w0, w1, w2, w3, j + 1u, N);
+        float t, U, V;
+        bool ok = ribbon_quad_test(a, b, r.tnear, tfar, S.s, t, U, V) && seg;
+        if (ok && P.exclOffsets) ok = !candidate_excluded(P, __float_as_uint(x[10]), ids.x, ids.y, t);
+        const uint32_t m8 = octet_ballot(ok, lid);
+        if (OCCLUDED) { // Occluded1EpilogMU: any valid segment
+          if (m8 != 0u) {
+            if (k == 0u) x[9] = __uint_as_float(1u);
+            cnt = 0u;
+            N = 0u;
+          }
+          continue;
+        }
+        const float tmin = octet_min8(ok ? t : RT_INF);
+        const uint32_t w = octet_ballot(ok && t == tmin, lid);
+        if (w != 0u && k == (uint32_t)__ffs(w) - 1u) { // select_min, the lowest lane wins an equal t (Intersect1EpilogMU, intersector_epilog.h:455-509)
+          TriHit h;
+          ribbon_hit(h, t, U, V, k, base, N, V0, V1, V2, V3);
+          row_write_hit(x, h, ids.x, ids.y);
+        }
+        tfar = w != 0u ? tmin : tfar;
+      }
+    }
+  }
+
+  // Lane-per-ray form: the records one after the other, the five words of a record requested before the first use; the segments in
+  // passes of 8 against the tfar at pass entry, visited in order and replacing the best one only with a smaller t, so the lowest
+  // segment wins ties.  The end of a segment is carried over as the start of the next (the same bits, see the header).  The world
+  // control points are read again for the Ng of a pass's winner: sixteen registers less across the segment loop.
+  template <bool OCCLUDED, bool COUNT>
+  static __device__ __forceinline__ bool intersect(const LaunchParams& P, uint32_t ref, RayState& r, WorkCounters& wc, uint32_t rayIdx)
+  {
+    const CurveRecord* __restrict__ recs = (const CurveRecord*)P.accel.blobs;
+    const LineSpace S = line_space(r);
+    uint32_t first, count;
+    leaf_range(ref, first, count);
+    for (uint32_t i = 0; i < count; i++) {
+      const float4* lp = (const float4*)(recs + first + i);
+      float4 w0 = lp[0], w1 = lp[1], w2 = lp[2], w3 = lp[3];
+      const uint4 ids = *(const uint4*)(lp + 4); // geomID, primID, N, pad
+      const uint32_t N = ids.z;
+      w0 = to_ray_space(r, S, w0); w1 = to_ray_space(r, S, w1); w2 = to_ray_space(r, S, w2); w3 = to_ray_space(r, S, w3);
+      RibbonEnd a = ribbon_end(w0, w1, w2, w3, 0u, N);
+      for (uint32_t base = 0; base < N; base += 8u) {
+        const float tfarPass = r.tfar; // all segments of a pass see the tfar at pass entry
+        const uint32_t nb = min(8u, N - base);
+        bool found = false;
+        float bt = RT_INF, bU = 0.f, bV = 0.f;
+        uint32_t bk = 0;
+        for (uint32_t k = 0; k < nb; k++) {
+          if (COUNT) wc.prims++;
+          const RibbonEnd b = ribbon_end(w0, w1, w2, w3, base + k + 1u, N);
+          float t, U, V;
+          bool ok = ribbon_quad_test(a, b, r.tnear, tfarPass, S.s, t, U, V);
+          a = b;
+          if (ok && P.exclOffsets) ok = !candidate_excluded(P, rayIdx, ids.x, ids.y, t);
+          if (ok) {
+            if (OCCLUDED) return true; // Occluded1EpilogMU: any valid segment
+            if (!found || t < bt) { // select_min over the pass, lowest segment wins ties
+              bt = t; bU = U; bV = V; bk = k;
+              found = true;
+            }
+          }
+        }
+        if (found) { // Intersect1EpilogMU, intersector_epilog.h:455-509
+          TriHit best;
+          ribbon_hit(best, bt, bU, bV, bk, base, N, lp[0], lp[1], lp[2], lp[3]);
+          commit_hit(r, best, ids.x, ids.y);
+        }
+      }
+    }
+    return false;
+  }
+};
+
 } // namespace dev
 } // namespace rtamd

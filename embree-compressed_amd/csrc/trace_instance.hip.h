@@ -6,6 +6,7 @@
 #include "trace_leaf.hip.h"
 #include "trace_quad_tests.hip.h"
 #include "trace_mb.hip.h"
+#include "trace_curve.hip.h" // (and trace_line.hip.h): the leaves of the HAIR form
 #include "instance_xfm.h"
 
 namespace rtamd {
@@ -57,6 +58,26 @@ constexpr int inst_min_waves(bool pluecker, bool occluded, bool quads, bool xfmb
   return quads && pluecker && !occluded ? TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_MIN_WAVES;
 }
 constexpr int inst_nodemb_min_waves(bool pluecker, bool occluded) { return inst_min_waves(pluecker, occluded, true, true, true); }
+// HAIR (trace_instance_hair.hip): the MESHMB form with the line and the ribbon leaf (trace_line.hip.h, trace_curve.hip.h) beside the four
+// mesh leaves.  Each instantiation is asked for the highest wave count, from its MESHMB twin's bound down to 2, at which it compiles
+// without scratch and without VGPR spills (docs/experiments.md, "Hair below an instance").
+#ifndef TRACE_INST_HAIR_MIN_WAVES_PLUECKER_CLOSEST
+#define TRACE_INST_HAIR_MIN_WAVES_PLUECKER_CLOSEST 2
+#endif
+#ifndef TRACE_INST_HAIR_MIN_WAVES_MOELLER_CLOSEST
+#define TRACE_INST_HAIR_MIN_WAVES_MOELLER_CLOSEST 2
+#endif
+#ifndef TRACE_INST_HAIR_MIN_WAVES_PLUECKER_ANY
+#define TRACE_INST_HAIR_MIN_WAVES_PLUECKER_ANY 3
+#endif
+#ifndef TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY
+#define TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY 4
+#endif
+constexpr int inst_hair_min_waves(bool pluecker, bool occluded)
+{
+  return occluded ? (pluecker ? TRACE_INST_HAIR_MIN_WAVES_PLUECKER_ANY : TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY)
+                  : (pluecker ? TRACE_INST_HAIR_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_HAIR_MIN_WAVES_MOELLER_CLOSEST);
+}
 
 // Filter re-trace below an instance (the EXCL form of the body, trace_instance_filter.hip): a candidate the host filter loop rejected for this
 // ray before stays rejected.  The key is (instance geomID, geomID, primID, bits of t) for every leaf type: the kernels are deterministic,
@@ -78,9 +99,10 @@ __device__ __forceinline__ bool instance_candidate_excluded(const LaunchParams& 
 template <bool PLUECKER, bool OCCLUDED, bool VEC, bool QUADS, bool XFMB>
 __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUADS, XFMB)) void trace_instance_kernel(LaunchParams P)
 {
-  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB, EXCL (it asserts them)
+  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB, EXCL, HAIR (it asserts them)
   constexpr bool MESHMB = false, NODEMB = false, TOPMB = false; // the MESHMB form is trace_instance_mesh_mb.hip's kernel, the NODEMB form trace_instance_mesh_mb_linear.hip's
   constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
+  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 

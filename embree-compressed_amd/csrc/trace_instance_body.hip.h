@@ -1,10 +1,10 @@
 // The body of the two-level traversal kernel (trace_instance.hip, where it is described; trace_instance_mesh_mb.hip;
 // trace_instance_mesh_mb_linear.hip; trace_instance_top_linear.hip), as text: it is
 // included inside the braces of a __global__ function that has the launch parameters `P` and the compile-time constants PLUECKER,
-// OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB and EXCL in scope.  Text and not a function called from the kernels: through a function the compiler
+// OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB, EXCL and HAIR in scope.  Text and not a function called from the kernels: through a function the compiler
 // schedules the loads of the launch parameters differently, and the instruction streams of the instantiations of trace_instance.hip
 // are held to what they were (tools/kernel_metadata.py --digest, docs/experiments.md).  No include guard: one inclusion per kernel.
-// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and nine `bool`
+// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and ten `bool`
 // constants.  Everything else the text uses comes from the headers trace_instance.hip.h includes and from the TRACE_INST_* macros it
 // defines; the text declares only locals of its own and ends with the traversal loop.
 // trace_instance_subdiv.hip restates the refill, node step, ranking, instance entry and pop of this text for subdivision leaves: a fix to
@@ -13,8 +13,8 @@
 #define TRACE_INSTANCE_BODY_BOOL(x) std::is_same<typename std::remove_const<decltype(x)>::type, bool>::value
   static_assert(TRACE_INSTANCE_BODY_BOOL(PLUECKER) && TRACE_INSTANCE_BODY_BOOL(OCCLUDED) && TRACE_INSTANCE_BODY_BOOL(VEC) && TRACE_INSTANCE_BODY_BOOL(QUADS) &&
                     TRACE_INSTANCE_BODY_BOOL(XFMB) && TRACE_INSTANCE_BODY_BOOL(MESHMB) && TRACE_INSTANCE_BODY_BOOL(NODEMB) && TRACE_INSTANCE_BODY_BOOL(TOPMB) &&
-                    TRACE_INSTANCE_BODY_BOOL(EXCL),
-                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB and EXCL must be bool constants in scope");
+                    TRACE_INSTANCE_BODY_BOOL(EXCL) && TRACE_INSTANCE_BODY_BOOL(HAIR),
+                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB, EXCL and HAIR must be bool constants in scope");
 #undef TRACE_INSTANCE_BODY_BOOL
   constexpr uint32_t FETCH = TRACE_INST_FETCH;
   constexpr uint32_t QFETCH = TRACE_INST_QUAD_FETCH;
@@ -27,6 +27,10 @@
   // before the block's minimum selection when the ray's exclusion list names it - (curInst, geomID, primID, bits of t), instance_candidate_excluded
   // in trace_instance.hip.h.  P.exclOffsets is set for every launch of such a kernel and indexed by the ray's index in the batch.
   static_assert(!EXCL || !OCCLUDED, "the filter loop runs closest-hit launches only");
+  // HAIR (trace_instance_hair.hip): an instanced scene may hold a curve and a line tree behind its four mesh trees (accel.h
+  // InstanceSceneRecord); their leaves are CurveLeaf::intersect / LineLeaf::intersect on the local ray.  The swept MESHMB form only, and
+  // no exclusion scan: filters beside instanced hair are refused at commit and at the call.
+  static_assert(!HAIR || (MESHMB && !NODEMB && !TOPMB && !EXCL), "the HAIR form is the MESHMB form over swept boxes, without the exclusion scan");
   constexpr bool ROBUST = PLUECKER; // Pluecker <-> robust traversal, Moeller <-> fast traversal, on both levels
   __shared__ uint2 ldsStack[TRACE_LDS_STACK + 1][TRACE_BLOCK]; // + one scratch row for the branch-free pushes
   const uint32_t tid = threadIdx.x;
@@ -59,12 +63,14 @@
   uint32_t sp = 0, cur = REF_EMPTY, rayIdx = 0;
   uint32_t curInst = 0xFFFFFFFFu, hitInst = 0xFFFFFFFFu; // geomID of the instance being traversed / of the hit's instance
   // lane state bits (vector register, see RayState::hit): the lane owns a ray, its next event is a pop, it is inside an instance,
-  // it is in the instanced scene's quad tree (QUADS only).  MESHMB: two bits, the code of the tree it is in (accel.h INST_TREE_*)
-  enum : uint32_t { ST_ACTIVE = 1u, ST_POP = 2u, ST_INSIDE = 4u, ST_QUADS = 8u, ST_TREE_SHIFT = 3u, ST_TREE = 3u << ST_TREE_SHIFT };
+  // it is in the instanced scene's quad tree (QUADS only).  MESHMB: two bits, the code of the tree it is in (accel.h INST_TREE_*);
+  // HAIR: three, for the codes of the curve and the line tree
+  enum : uint32_t { ST_ACTIVE = 1u, ST_POP = 2u, ST_INSIDE = 4u, ST_QUADS = 8u, ST_TREE_SHIFT = 3u, ST_TREE = (HAIR ? 7u : 3u) << ST_TREE_SHIFT };
   static_assert((INST_TREE_QUAD << ST_TREE_SHIFT) == ST_QUADS, "the quad tree's code is the ST_QUADS bit");
   // NODEMB: bit 1 of the code says that the tree's nodes are QNodeMB8s; the bits are clear outside an instance
   enum : uint32_t { ST_TREE_MB = 2u << ST_TREE_SHIFT };
   static_assert(!(INST_TREE_TRI & 2u) && !(INST_TREE_QUAD & 2u) && (INST_TREE_TRIMB & 2u) && (INST_TREE_QUADMB & 2u), "bit 1 of a tree's code: a motion-blur tree");
+  static_assert(!(INST_TREE_CURVE & 2u) && !(INST_TREE_LINE & 2u) && INST_TREE_CURVE < 8u && INST_TREE_LINE < 8u, "the hair trees' codes: three bits, bit 1 clear");
   uint32_t st = 0u;
   r.hit = 0u;
 
@@ -311,12 +317,19 @@
         // q3.y names the scene's InstanceSceneRecord: its four roots in visiting order (triangles, motion-blur triangles, quads,
         // motion-blur quads).  Walking them backwards, every tree that has one before it is stacked as a marker with its root in the
         // distance word; the lane starts in the first tree the scene has.
+        // HAIR: six roots - the curve and the line root lead the record's second dwordx4 and are visited last, curves before lines
         const uint4 sr = ((const uint4*)(insts + q3.y))[0];
-        const uint32_t roots[4] = {sr.x, sr.y, sr.z, sr.w};
-        const uint32_t codes[4] = {INST_TREE_TRI, INST_TREE_TRIMB, INST_TREE_QUAD, INST_TREE_QUADMB};
+        constexpr int TREES = HAIR ? 6 : 4;
+        uint32_t roots[TREES] = {sr.x, sr.y, sr.z, sr.w};
+        uint32_t codes[TREES] = {INST_TREE_TRI, INST_TREE_TRIMB, INST_TREE_QUAD, INST_TREE_QUADMB};
+        if (HAIR) {
+          const uint4 sh = ((const uint4*)(insts + q3.y))[1];
+          roots[TREES - 2] = sh.x; roots[TREES - 1] = sh.y;
+          codes[TREES - 2] = INST_TREE_CURVE; codes[TREES - 1] = INST_TREE_LINE;
+        }
         uint32_t nextRoot = REF_EMPTY, nextCode = 0u;
 #pragma unroll
-        for (int i = 3; i >= 0; i--) {
+        for (int i = TREES - 1; i >= 0; i--) {
           if (roots[i] != REF_EMPTY) {
             if (nextRoot != REF_EMPTY) {
               push(REF_INST_TREE(nextCode), nextRoot, sp);
@@ -352,7 +365,20 @@
         uint32_t first, count;
         leaf_range(cur, first, count);
         bool occl = false;
-        if (MESHMB && (st & ST_TREE) == (INST_TREE_TRIMB << ST_TREE_SHIFT)) {
+        if (HAIR && ((st & ST_TREE) == (INST_TREE_CURVE << ST_TREE_SHIFT) || (st & ST_TREE) == (INST_TREE_LINE << ST_TREE_SHIFT))) {
+          // the leaves of the top-level curve and line accels (trace_curve.hip.h, trace_line.hip.h) on the LOCAL ray: the ray's own space
+          // depends on the length of the local direction, as in the reference, which hands the local ray to the instanced scene's
+          // intersectors unchanged.  The leaf references are rebased so that `blobs` is ONE array of CurveRecords / LineRecords, which is how
+          // the two leaves index it.  r.hit is cleared around the call: a hit the leaf commits - also one at a t equal to the hit of an
+          // earlier instance - is this instance's
+          WorkCounters wc;
+          const uint32_t had = r.hit;
+          r.hit = 0u;
+          if ((st & ST_TREE) == (INST_TREE_CURVE << ST_TREE_SHIFT)) occl = CurveLeaf::intersect<OCCLUDED, false>(P, cur, r, wc, rayIdx);
+          else occl = LineLeaf::intersect<OCCLUDED, false>(P, cur, r, wc, rayIdx);
+          if (r.hit) hitInst = curInst; // instID: instance_intersector.cpp:57
+          r.hit |= had;
+        } else if (MESHMB && (st & ST_TREE) == (INST_TREE_TRIMB << ST_TREE_SHIFT)) {
           // the block loop of TriMBLeaf::intersect (trace_tri_mb.hip): a record is tested only when its segment is the ray's itime, on the
           // vertices interpolated to the ray's time; Moeller forms its edges from them (e1 = a - b, e2 = c - a)
           const TriMBRecord* __restrict__ mrecs = (const TriMBRecord*)P.accel.blobs; // the leaf references are rebased to the section's start
@@ -572,8 +598,8 @@
           continue;
         }
         if (MESHMB) {
-          if (e.x - REF_INST_TREE(1u) < 3u) { // the tree before is done: on to the pending tree whose marker this is; before the distance cull
-            st = (st & ~ST_TREE) | ((e.x & 3u) << ST_TREE_SHIFT);
+          if (e.x - REF_INST_TREE(1u) < (HAIR ? 5u : 3u)) { // the tree before is done: on to the pending tree whose marker this is; before the distance cull
+            st = (st & ~ST_TREE) | ((e.x & (HAIR ? 7u : 3u)) << ST_TREE_SHIFT);
             cur = e.y;
             break;
           }

@@ -35,6 +35,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, inst_filter_min_waves(PLUECKER, QUADS,
 {
   constexpr bool OCCLUDED = false, EXCL = true;
   constexpr bool TOPMB = false; // the EXCL form over a time-dependent top level is trace_instance_top_linear.hip's filter kernel
+  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 

@@ -28,6 +28,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, tru
 {
   constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = false, TOPMB = false; // always the general layout: quads and instance steps allowed
   constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
+  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 
@@ -42,6 +43,7 @@ inline hipError_t launch_instance_mesh_mb_vec(const LaunchParams& p, hipStream_t
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream)
 {
   if (p.counters) return hipErrorInvalidValue; // no instrumented twin (rt_trace.cpp refuses counted batches on scenes with instances)
+  if (p.instHair) return p.exclOffsets ? hipErrorInvalidValue : launch_trace_instance_hair(p, stream); // line and curve trees below the instances: the HAIR form, which has no EXCL twin
   if (p.exclOffsets) return launch_trace_instance_filter(p, stream); // a re-trace of the host filter loop: the EXCL form (trace_instance_filter.hip)
   switch (p.accel.kind) {
   case ACCEL_INSTMESHMB_PLUECKER: return p.occluded ? dev::launch_instance_mesh_mb_vec<true, true>(p, stream) : dev::launch_instance_mesh_mb_vec<true, false>(p, stream);

@@ -20,6 +20,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, inst_nodemb_min_waves(PLUECKER, OCCLUD
   constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = true;
   constexpr bool TOPMB = false; // the TOPMB form (a top-level tree of time-dependent nodes) is trace_instance_top_linear.hip's kernel
   constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
+  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 

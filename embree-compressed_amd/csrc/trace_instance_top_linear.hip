@@ -21,6 +21,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, inst_nodemb_min_waves(PLUECKER, OCCLUD
 {
   constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = true, TOPMB = true;
   constexpr bool EXCL = false;
+  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 
@@ -30,6 +31,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, inst_nodemb_min_waves(PLUECKER, false)
 {
   constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = true, TOPMB = true;
   constexpr bool OCCLUDED = false, EXCL = true;
+  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
 #include "trace_instance_body.hip.h"
 }
 

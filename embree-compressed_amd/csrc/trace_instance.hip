@@ -1,6 +1,6 @@
 // Single-level instancing (RTC_GEOMETRY_TYPE_INSTANCE, one time step): a two-level traversal kernel of its own, one ray per lane.
-// This file describes the kernel and launches its 32 instantiations; the kernel template is in trace_instance.hip.h and its body, shared with
-// trace_instance_mesh_mb.hip, in trace_instance_body.hip.h.
+// This file describes the kernel and launches its 32 instantiations; the kernel template is in trace_instance.hip.h, beside the list of the
+// other forms' units, and its body, one text for all of them, in trace_instance_body.hip.h.
 // The accel (accel.h InstanceRecord, rt_scene.cpp build_instance_accel) is ONE node array: a top-level BVH8 over the instances' world
 // bounds with one instance per leaf, and behind it the triangle trees of the instanced scenes, rebased, over one TriRecord array.
 // Per ray:

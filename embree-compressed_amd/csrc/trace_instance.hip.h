@@ -1,6 +1,15 @@
-// The two-level traversal kernel of trace_instance.hip (where it is described) as a template, shared with
-// trace_instance_mesh_mb.hip, which instantiates its MESHMB form, trace_instance_mesh_mb_linear.hip (the NODEMB form) and
-// trace_instance_top_linear.hip (the TOPMB form).
+// The two-level traversal kernels, mesh and subdivision instances alike: what a form of the kernel is (InstanceForm), the waves per SIMD
+// each form is asked for, the launcher of a kernel pair, and the kernel template of trace_instance.hip (where the kernel is described).
+// The kernel's text is trace_instance_body.hip.h, included inside the braces of every __global__ function of the family:
+//   trace_instance.hip                     trace_instance_kernel                      PLUECKER x OCCLUDED x QUADS x XFMB
+//   trace_instance_mesh_mb.hip             trace_instance_mesh_mb_kernel              MESHMB
+//   trace_instance_mesh_mb_linear.hip      trace_instance_mesh_mb_linear_kernel       NODEMB
+//   trace_instance_top_linear.hip          trace_instance_top_linear[_filter]_kernel  TOPMB (and its EXCL form)
+//   trace_instance_filter.hip              trace_instance_filter_kernel               EXCL
+//   trace_instance_hair.hip                trace_instance_hair_kernel                 HAIR
+//   trace_instance_subdiv.hip              trace_instance_subdiv_kernel               SUBDIV (through trace_instance_subdiv.hip.h)
+//   trace_instance_subdiv_top_linear.hip   trace_instance_subdiv_top_linear_kernel    SUBDIV, TOPMB
+// One unit per kernel template so that the instantiations compile beside each other.
 #pragma once
 #include <type_traits>
 #include "trace_leaf.hip.h"
@@ -12,8 +21,33 @@
 namespace rtamd {
 namespace dev {
 
+// A form of the two-level kernel: the compile-time constants of trace_instance_body.hip.h, which describes each where it uses it.  A
+// kernel builds its form from its template parameters and names what it turns on; the body, included with `FORM` in scope, unpacks it.
+// A new constant is a member here, with its default, and the kernels that set it.
+struct InstanceForm
+{
+  bool PLUECKER = false; // Pluecker test and robust traversal / Moeller test and fast traversal (mesh family)
+  bool OCCLUDED = false; // any hit / closest hit
+  bool VEC = false;      // ray records are 16-byte aligned
+  bool QUADS = false;    // an instanced scene may hold a quad tree
+  bool XFMB = false;     // an instance may have transform time steps
+  bool MESHMB = false;   // an instanced scene holds up to four trees, two of them of motion-blur meshes
+  bool NODEMB = false;   // some trees are made of time-dependent nodes: the node step interpolates the planes at the ray's time
+  bool TOPMB = false;    // NODEMB, and the top-level tree is one of them
+  bool EXCL = false;     // the exclusion scan of the filter re-traces
+  bool HAIR = false;     // MESHMB, and a curve and a line tree behind the four mesh trees
+  bool SUBDIV = false;   // the subdivision family: an instanced scene is one tree whose leaves are the kernel's `Leaf`
+  bool GRID = false;     // SUBDIV: that leaf is the eager accel's GridCellLeaf (a wave bound depends on it)
+};
+
+// The `Leaf` of the mesh family's kernels: their leaves are the block loops of the body's mesh section, this is never called.
+struct MeshLeaves : LeafTraits
+{
+  template <bool OCCLUDED, bool COUNT> static __device__ __forceinline__ bool intersect(const LaunchParams&, uint32_t, RayState&, WorkCounters&, uint32_t) { return false; }
+};
+
 // Waves per SIMD the register allocator is asked for: 4 (<= 128 VGPRs), as the triangle kernels run; the kernels must compile without
-// scratch at this bound (tools/kernel_resources.sh, docs/experiments.md "Instancing").
+// scratch at their bound (tools/kernel_resources.sh, docs/experiments.md "Instancing").  The exceptions are in instance_min_waves below.
 #ifndef TRACE_INST_MIN_WAVES
 #define TRACE_INST_MIN_WAVES 4
 #endif
@@ -23,44 +57,30 @@ namespace dev {
 #ifndef TRACE_INST_FETCH
 #define TRACE_INST_FETCH 2
 #endif
-// The QUADS instantiations carry the quad block loop (a record is four dwordx4, a block has 8 candidates) next to the triangle loop.
-// Three of the four compile without scratch at 4 waves per SIMD; closest-hit Pluecker does not (76 bytes of scratch with two QuadRecords
-// per round trip, 36 with one), as the static quad lane kernel's does not (trace_quad.hip): it alone is asked for 3 waves (<= 168 VGPRs).
-#ifndef TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST
-#define TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST 3
-#endif
 // QuadRecords requested per memory round trip inside a block of 4 (1 or 2)
 #ifndef TRACE_INST_QUAD_FETCH
 #define TRACE_INST_QUAD_FETCH 2
 #endif
-// MESHMB (trace_instance_mesh_mb.hip): the motion-blur leaves on top of the QUADS and XFMB forms.  Asked for the bound of the QUADS
-// twin; records per memory round trip as in the top-level leaves (trace_tri_mb.hip TRIMB_FETCH, trace_quad_mb.hip QUADMB_FETCH).
+// MESHMB: records per memory round trip as in the top-level leaves (trace_tri_mb.hip TRIMB_FETCH, trace_quad_mb.hip QUADMB_FETCH).
 #ifndef TRACE_INST_TRIMB_FETCH
 #define TRACE_INST_TRIMB_FETCH 2
 #endif
 #ifndef TRACE_INST_QUADMB_FETCH
 #define TRACE_INST_QUADMB_FETCH 1
 #endif
-// The closest-hit MESHMB kernels spill at the bound of their QUADS twins (Pluecker: 20 bytes of scratch at 3 waves, Moeller: 76 at 4;
-// with one record per round trip in every leaf still 12 and 36): they are asked for one wave less, the any-hit kernels keep 4
-// (docs/experiments.md, "Motion-blur meshes below an instance").
+
+#ifndef TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST
+#define TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST 3
+#endif
 #ifndef TRACE_INST_MESHMB_MIN_WAVES_PLUECKER_CLOSEST
 #define TRACE_INST_MESHMB_MIN_WAVES_PLUECKER_CLOSEST 2
 #endif
 #ifndef TRACE_INST_MESHMB_MIN_WAVES_MOELLER_CLOSEST
 #define TRACE_INST_MESHMB_MIN_WAVES_MOELLER_CLOSEST 3
 #endif
-// NODEMB (trace_instance_mesh_mb_linear.hip): the MESHMB form with time-dependent nodes in the motion-blur trees - twelve more node words
-// and the ray's time across the node step.  Each instantiation is asked for the bound of its MESHMB twin.
-constexpr int inst_min_waves(bool pluecker, bool occluded, bool quads, bool xfmb, bool meshmb = false)
-{
-  if (meshmb && !occluded) return pluecker ? TRACE_INST_MESHMB_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_MESHMB_MIN_WAVES_MOELLER_CLOSEST;
-  return quads && pluecker && !occluded ? TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_MIN_WAVES;
-}
-constexpr int inst_nodemb_min_waves(bool pluecker, bool occluded) { return inst_min_waves(pluecker, occluded, true, true, true); }
-// HAIR (trace_instance_hair.hip): the MESHMB form with the line and the ribbon leaf (trace_line.hip.h, trace_curve.hip.h) beside the four
-// mesh leaves.  Each instantiation is asked for the highest wave count, from its MESHMB twin's bound down to 2, at which it compiles
-// without scratch and without VGPR spills (docs/experiments.md, "Hair below an instance").
+#ifndef TRACE_INST_FILTER_MIN_WAVES_TRI_PLUECKER
+#define TRACE_INST_FILTER_MIN_WAVES_TRI_PLUECKER 3
+#endif
 #ifndef TRACE_INST_HAIR_MIN_WAVES_PLUECKER_CLOSEST
 #define TRACE_INST_HAIR_MIN_WAVES_PLUECKER_CLOSEST 2
 #endif
@@ -73,10 +93,32 @@ constexpr int inst_nodemb_min_waves(bool pluecker, bool occluded) { return inst_
 #ifndef TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY
 #define TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY 4
 #endif
-constexpr int inst_hair_min_waves(bool pluecker, bool occluded)
+
+// The wave bound of a form; `leafWaves` is Leaf::MIN_WAVES in the subdivision family.  Every exception, first match wins:
+constexpr int instance_min_waves(InstanceForm f, int leafWaves = TRACE_INST_MIN_WAVES)
 {
-  return occluded ? (pluecker ? TRACE_INST_HAIR_MIN_WAVES_PLUECKER_ANY : TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY)
-                  : (pluecker ? TRACE_INST_HAIR_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_HAIR_MIN_WAVES_MOELLER_CLOSEST);
+  // SUBDIV: the bound of the same leaf's top-level lane kernel (3, cBVH from C = 4 on 2), at which the cBVH kernels compile without
+  // scratch.  The eager closest-hit kernel needs 36 bytes of scratch at 3 waves (168 VGPRs) where its twin has none - the lane kernel
+  // tests cells 8 lanes per ray and does not hold GridCellLeaf::intersect with its 40 cell words at all; the ray-pool kernel, which does,
+  // takes 186 VGPRs: one wave less (docs/experiments.md, "Subdivision meshes below an instance").  TOPMB: the swept twin's bound
+  if (f.SUBDIV) return f.GRID && !f.OCCLUDED ? leafWaves - 1 : leafWaves;
+  // HAIR: the line and the ribbon leaf beside the four mesh leaves.  The highest wave count, from the MESHMB twin's bound down to 2, at
+  // which the kernel compiles without scratch and without VGPR spills (docs/experiments.md, "Hair below an instance")
+  if (f.HAIR)
+    return f.OCCLUDED ? (f.PLUECKER ? TRACE_INST_HAIR_MIN_WAVES_PLUECKER_ANY : TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY)
+                      : (f.PLUECKER ? TRACE_INST_HAIR_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_HAIR_MIN_WAVES_MOELLER_CLOSEST);
+  // EXCL: the bound of the unfiltered closest-hit twin wherever the kernel compiles without scratch there - all forms but one.  The
+  // Pluecker triangle-only forms (kinds 14 and 18) are at 128 VGPRs without the scan and spill 12 bytes with it: one wave less
+  if (f.EXCL && f.PLUECKER && !f.QUADS && !f.MESHMB) return TRACE_INST_FILTER_MIN_WAVES_TRI_PLUECKER;
+  // MESHMB, and with it NODEMB and TOPMB, each at the bound of its MESHMB twin: the closest-hit kernels spill at the bound of their
+  // QUADS twins (Pluecker: 20 bytes of scratch at 3 waves, Moeller: 76 at 4; with one record per round trip in every leaf still 12 and
+  // 36) and are asked for one wave less, the any-hit kernels keep 4 (docs/experiments.md, "Motion-blur meshes below an instance")
+  if (f.MESHMB && !f.OCCLUDED) return f.PLUECKER ? TRACE_INST_MESHMB_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_MESHMB_MIN_WAVES_MOELLER_CLOSEST;
+  // QUADS: the quad block loop (a record is four dwordx4, a block has 8 candidates) next to the triangle loop.  Three of the four
+  // instantiations compile without scratch at 4 waves; closest-hit Pluecker does not (76 bytes of scratch with two QuadRecords per
+  // round trip, 36 with one), as the static quad lane kernel's does not (trace_quad.hip): it alone is asked for 3 waves (<= 168 VGPRs)
+  if (f.QUADS && f.PLUECKER && !f.OCCLUDED) return TRACE_INST_QUADS_MIN_WAVES_PLUECKER_CLOSEST;
+  return TRACE_INST_MIN_WAVES;
 }
 
 // Filter re-trace below an instance (the EXCL form of the body, trace_instance_filter.hip): a candidate the host filter loop rejected for this
@@ -96,13 +138,26 @@ __device__ __forceinline__ bool instance_candidate_excluded(const LaunchParams& 
   return false;
 }
 
-template <bool PLUECKER, bool OCCLUDED, bool VEC, bool QUADS, bool XFMB>
-__global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, QUADS, XFMB)) void trace_instance_kernel(LaunchParams P)
+constexpr InstanceForm instance_form(bool pluecker, bool occluded, bool vec, bool quads, bool xfmb)
 {
-  // the body needs in scope: P, PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB, EXCL, HAIR (it asserts them)
-  constexpr bool MESHMB = false, NODEMB = false, TOPMB = false; // the MESHMB form is trace_instance_mesh_mb.hip's kernel, the NODEMB form trace_instance_mesh_mb_linear.hip's
-  constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
-  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
+  InstanceForm f;
+  f.PLUECKER = pluecker; f.OCCLUDED = occluded; f.VEC = vec; f.QUADS = quads; f.XFMB = xfmb;
+  return f;
+}
+// the MESHMB form, from which the NODEMB, TOPMB and HAIR forms start: always the general layout, quads and instance steps allowed
+constexpr InstanceForm instance_mesh_mb_form(bool pluecker, bool occluded, bool vec)
+{
+  InstanceForm f = instance_form(pluecker, occluded, vec, true, true);
+  f.MESHMB = true;
+  return f;
+}
+
+template <bool Pluecker, bool Occluded, bool Vec, bool Quads, bool Xfmb>
+__global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_form(Pluecker, Occluded, Vec, Quads, Xfmb))) void trace_instance_kernel(LaunchParams P)
+{
+  // the body needs in scope: P, FORM and Leaf
+  constexpr InstanceForm FORM = instance_form(Pluecker, Occluded, Vec, Quads, Xfmb);
+  using Leaf = MeshLeaves;
 #include "trace_instance_body.hip.h"
 }
 

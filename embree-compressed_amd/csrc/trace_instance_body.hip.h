@@ -1,28 +1,27 @@
-// The body of the two-level traversal kernel (trace_instance.hip, where it is described; trace_instance_mesh_mb.hip;
-// trace_instance_mesh_mb_linear.hip; trace_instance_top_linear.hip), as text: it is
-// included inside the braces of a __global__ function that has the launch parameters `P` and the compile-time constants PLUECKER,
-// OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB, EXCL and HAIR in scope.  Text and not a function called from the kernels: through a function the compiler
-// schedules the loads of the launch parameters differently, and the instruction streams of the instantiations of trace_instance.hip
-// are held to what they were (tools/kernel_metadata.py --digest, docs/experiments.md).  No include guard: one inclusion per kernel.
-// What the including function provides, checked right below: `LaunchParams P` (the kernel's by-value parameter) and ten `bool`
-// constants.  Everything else the text uses comes from the headers trace_instance.hip.h includes and from the TRACE_INST_* macros it
-// defines; the text declares only locals of its own and ends with the traversal loop.
-// trace_instance_subdiv.hip restates the refill, node step, ranking, instance entry and pop of this text for subdivision leaves: a fix to
-// the stack, queue or ranking code here belongs there too.
+// The body of the two-level traversal kernels, as text: it is included inside the braces of a __global__ function that has the launch
+// parameters `P`, the kernel's form `FORM` (trace_instance.hip.h InstanceForm) and its leaf type `Leaf` in scope - a subdivision leaf
+// (trace_instance_subdiv.hip.h) or MeshLeaves.  The units that include it are listed in trace_instance.hip.h; trace_instance.hip describes
+// the mesh family, trace_instance_subdiv.hip the subdivision family.  The walk - setup, refill, node step, ranking, push, instance entry,
+// pop, exit marker, store - is one text for both; they part in the leaf section, and in a few places marked SUBDIV.
+// Text and not a function called from the kernels: through a function the compiler schedules the loads of the launch parameters
+// differently, and the instruction streams of the instantiations are held to what they were (tools/kernel_metadata.py --digest,
+// docs/experiments.md).  No include guard: one inclusion per kernel.  Everything else the text uses comes from the headers
+// trace_instance.hip.h includes and from the TRACE_INST_* macros it defines; the text declares only locals of its own and ends with the
+// traversal loop.
   static_assert(std::is_same<decltype(P), LaunchParams>::value, "trace_instance_body.hip.h: `LaunchParams P` must be the kernel's parameter");
-#define TRACE_INSTANCE_BODY_BOOL(x) std::is_same<typename std::remove_const<decltype(x)>::type, bool>::value
-  static_assert(TRACE_INSTANCE_BODY_BOOL(PLUECKER) && TRACE_INSTANCE_BODY_BOOL(OCCLUDED) && TRACE_INSTANCE_BODY_BOOL(VEC) && TRACE_INSTANCE_BODY_BOOL(QUADS) &&
-                    TRACE_INSTANCE_BODY_BOOL(XFMB) && TRACE_INSTANCE_BODY_BOOL(MESHMB) && TRACE_INSTANCE_BODY_BOOL(NODEMB) && TRACE_INSTANCE_BODY_BOOL(TOPMB) &&
-                    TRACE_INSTANCE_BODY_BOOL(EXCL) && TRACE_INSTANCE_BODY_BOOL(HAIR),
-                "trace_instance_body.hip.h: PLUECKER, OCCLUDED, VEC, QUADS, XFMB, MESHMB, NODEMB, TOPMB, EXCL and HAIR must be bool constants in scope");
-#undef TRACE_INSTANCE_BODY_BOOL
+  constexpr bool PLUECKER = FORM.PLUECKER, OCCLUDED = FORM.OCCLUDED, VEC = FORM.VEC, QUADS = FORM.QUADS, XFMB = FORM.XFMB, MESHMB = FORM.MESHMB;
+  constexpr bool NODEMB = FORM.NODEMB, TOPMB = FORM.TOPMB, EXCL = FORM.EXCL, HAIR = FORM.HAIR, SUBDIV = FORM.SUBDIV;
   constexpr uint32_t FETCH = TRACE_INST_FETCH;
   constexpr uint32_t QFETCH = TRACE_INST_QUAD_FETCH;
   constexpr uint32_t TMFETCH = TRACE_INST_TRIMB_FETCH;
   constexpr uint32_t QMFETCH = TRACE_INST_QUADMB_FETCH;
   static_assert(!MESHMB || (QUADS && XFMB), "the MESHMB form carries the general layout: quads and instance steps");
-  static_assert(!NODEMB || MESHMB, "the NODEMB form is the MESHMB form over time-dependent nodes in the motion-blur trees");
+  static_assert(!NODEMB || MESHMB || SUBDIV, "the NODEMB form of the mesh family is the MESHMB form over time-dependent nodes in the motion-blur trees");
   static_assert(!TOPMB || NODEMB, "the TOPMB form is the NODEMB form over a top-level tree of time-dependent nodes");
+  // SUBDIV (trace_instance_subdiv.hip): an instanced scene is one tree - no pending-tree markers, no tree code in the lane state - over
+  // swept boxes, its leaves are Leaf::intersect on the local ray, every instance may have time steps, and the traversal is the robust
+  // one on both levels, as the subdivision accels run at top level.  Time-dependent nodes only at top level: NODEMB with TOPMB.
+  static_assert(!SUBDIV || (XFMB && !PLUECKER && !QUADS && !MESHMB && !EXCL && !HAIR && NODEMB == TOPMB), "the SUBDIV forms: instance steps, one swept tree per scene, TOPMB or not");
   // EXCL (trace_instance_filter.hip, the re-traces of the host filter loop): in every leaf loop a candidate that passed its test is dropped
   // before the block's minimum selection when the ray's exclusion list names it - (curInst, geomID, primID, bits of t), instance_candidate_excluded
   // in trace_instance.hip.h.  P.exclOffsets is set for every launch of such a kernel and indexed by the ray's index in the batch.
@@ -31,8 +30,9 @@
   // InstanceSceneRecord); their leaves are CurveLeaf::intersect / LineLeaf::intersect on the local ray.  The swept MESHMB form only, and
   // no exclusion scan: filters beside instanced hair are refused at commit and at the call.
   static_assert(!HAIR || (MESHMB && !NODEMB && !TOPMB && !EXCL), "the HAIR form is the MESHMB form over swept boxes, without the exclusion scan");
-  constexpr bool ROBUST = PLUECKER; // Pluecker <-> robust traversal, Moeller <-> fast traversal, on both levels
+  constexpr bool ROBUST = SUBDIV || PLUECKER; // Pluecker <-> robust traversal, Moeller <-> fast traversal, on both levels
   __shared__ uint2 ldsStack[TRACE_LDS_STACK + 1][TRACE_BLOCK]; // + one scratch row for the branch-free pushes
+  Leaf::prepare(); // SUBDIV: once per kernel (the cBVH decode tables in LDS); nothing for the others
   const uint32_t tid = threadIdx.x;
   const uint32_t gthread = blockIdx.x * TRACE_BLOCK + tid;
   auto spill_col = [&]() -> uint2* { // see trace_loop.hip.h: formed where it is used, from an opaque copy of the thread index
@@ -64,7 +64,7 @@
   uint32_t curInst = 0xFFFFFFFFu, hitInst = 0xFFFFFFFFu; // geomID of the instance being traversed / of the hit's instance
   // lane state bits (vector register, see RayState::hit): the lane owns a ray, its next event is a pop, it is inside an instance,
   // it is in the instanced scene's quad tree (QUADS only).  MESHMB: two bits, the code of the tree it is in (accel.h INST_TREE_*);
-  // HAIR: three, for the codes of the curve and the line tree
+  // HAIR: three, for the codes of the curve and the line tree.  SUBDIV: the first three bits only
   enum : uint32_t { ST_ACTIVE = 1u, ST_POP = 2u, ST_INSIDE = 4u, ST_QUADS = 8u, ST_TREE_SHIFT = 3u, ST_TREE = (HAIR ? 7u : 3u) << ST_TREE_SHIFT };
   static_assert((INST_TREE_QUAD << ST_TREE_SHIFT) == ST_QUADS, "the quad tree's code is the ST_QUADS bit");
   // NODEMB: bit 1 of the code says that the tree's nodes are QNodeMB8s; the bits are clear outside an instance
@@ -143,8 +143,8 @@
       // NODEMB: the lane's tree says which node type `cur` names - a QNodeMB8 of the buffer indexed in 144-byte units while the lane is in
       // a motion-blur tree of an instanced scene, a QNode8 everywhere else (top level, static trees).  TOPMB (kinds ACCEL_INSTTOP_LINEAR_*):
       // the top-level tree is made of QNodeMB8s too - a lane outside an instance reads one, and enters a moving instance only where its
-      // box is at the ray's time
-      const bool mbNode = NODEMB && ((st & ST_TREE_MB) != 0u || (TOPMB && !(st & ST_INSIDE)));
+      // box is at the ray's time.  SUBDIV has no tree codes: with TOPMB a QNodeMB8 outside an instance, a QNode8 inside one
+      const bool mbNode = NODEMB && ((MESHMB && (st & ST_TREE_MB) != 0u) || (TOPMB && !(st & ST_INSIDE)));
       const uint4* np = mbNode ? (const uint4*)((const QNodeMB8*)nodes + cur) : (const uint4*)(nodes + cur);
       const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3], n4 = np[4], n5 = np[5];
       const float ox = __uint_as_float(n0.x), oy = __uint_as_float(n0.y), oz = __uint_as_float(n0.z);
@@ -352,11 +352,13 @@
             st |= ST_QUADS;
           }
         } else if (cur == REF_EMPTY) st |= ST_POP; // neither tree (the builder leaves such instances out)
+      } else if (SUBDIV) {
+        if (cur == REF_EMPTY) st |= ST_POP; // no tree (the builder leaves such instances out)
       }
       }
     }
 
-    // ---- triangle / quad leaf inside an instance: run when enough lanes wait at one, or when nobody has node work -------
+    // ---- leaf inside an instance: run when enough lanes wait at one, or when nobody has node work ----------------------
     const bool atLeaf = (MESHMB ? st & ~ST_TREE : QUADS ? st & ~ST_QUADS : st) == (ST_ACTIVE | ST_INSIDE) && (cur & REF_LEAF);
     const uint64_t leafMask = __ballot(atLeaf);
     if (leafMask != 0ull) {
@@ -365,7 +367,22 @@
         uint32_t first, count;
         leaf_range(cur, first, count);
         bool occl = false;
-        if (HAIR && ((st & ST_TREE) == (INST_TREE_CURVE << ST_TREE_SHIFT) || (st & ST_TREE) == (INST_TREE_LINE << ST_TREE_SHIFT))) {
+        if (SUBDIV) {
+          // the subdivision family's leaf.  It sets r.hit when IT finds a hit: cleared around the call so that such a hit takes the
+          // instance's id, whatever its t (a hit at the t of the hit so far replaces it, as in the leaf's top-level kernel).  It ends an
+          // occluded ray itself and not through `occl` like the HAIR branch below, whose statement order moves 12 of these kernels' digests
+          WorkCounters wc; // the leaf's counting argument: never counted here.  Declared where it is used, here and below: one declaration
+                           // at function level changes the instruction streams of the mesh family's closest-hit kernels
+          const uint32_t had = r.hit;
+          r.hit = 0u;
+          if (Leaf::template intersect<OCCLUDED, false>(P, cur, r, wc, rayIdx)) {
+            r.tfar = -RT_INF; // bvh_intersector1.cpp:198-201
+            r.hit = 1u;
+            sp = 0;           // any hit found: terminate this ray
+          }
+          if (!OCCLUDED && r.hit) hitInst = curInst; // instID: instance_intersector.cpp:57
+          r.hit |= had;
+        } else if (HAIR && ((st & ST_TREE) == (INST_TREE_CURVE << ST_TREE_SHIFT) || (st & ST_TREE) == (INST_TREE_LINE << ST_TREE_SHIFT))) {
           // the leaves of the top-level curve and line accels (trace_curve.hip.h, trace_line.hip.h) on the LOCAL ray: the ray's own space
           // depends on the length of the local direction, as in the reference, which hands the local ray to the instanced scene's
           // intersectors unchanged.  The leaf references are rebased so that `blobs` is ONE array of CurveRecords / LineRecords, which is how
@@ -617,7 +634,14 @@
         if (r.hit) {
           char* rp = (char*)P.rays + (size_t)rayIdx * P.stride;
           if (OCCLUDED) ((float*)rp)[8] = r.tfar;
-          else store_hit<VEC>(rp, r, hitInst);
+          else {
+            if constexpr (SUBDIV && Leaf::CONST_NG) { // the fork's dummy normal is not kept across the loop (trace_loop.hip.h)
+              float one = 1.f, zero = 0.f;
+              asm volatile("" : "+v"(one), "+v"(zero));
+              r.ngx = one; r.ngy = zero; r.ngz = zero;
+            }
+            store_hit<VEC>(rp, r, hitInst);
+          }
         }
         st = 0u;
       }

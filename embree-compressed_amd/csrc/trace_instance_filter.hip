@@ -12,30 +12,27 @@
 //   kinds 30 / 31  NODEMB (MESHMB over time-dependent nodes)   2 forms
 // each for 16-byte aligned records (VEC) and for any others: 24 instantiations.  They serve latency-bound filter rounds of a few rays,
 // not the metric: each is asked for the waves per SIMD of its unfiltered twin, or for one less where the scan's registers would
-// otherwise spill - none may use scratch (tools/kernel_resources.sh, docs/experiments.md "Filters below an instance").
+// otherwise spill (trace_instance.hip.h instance_min_waves) - none may use scratch (tools/kernel_resources.sh, docs/experiments.md
+// "Filters below an instance").
 #include "trace_instance.hip.h"
 
 namespace rtamd {
 namespace dev {
 
-// Waves per SIMD asked for: the bound of the unfiltered closest-hit twin (inst_min_waves) wherever the kernel compiles without scratch
-// there - all forms but one.  The Pluecker triangle-only forms (kinds 14 and 18) are at 128 VGPRs without the scan and spill 12 bytes
-// with it: they are asked for one wave less.
-#ifndef TRACE_INST_FILTER_MIN_WAVES_TRI_PLUECKER
-#define TRACE_INST_FILTER_MIN_WAVES_TRI_PLUECKER 3
-#endif
-constexpr int inst_filter_min_waves(bool pluecker, bool quads, bool xfmb, bool meshmb)
+// the EXCL twin of a closest-hit form (the one over a time-dependent top level is trace_instance_top_linear.hip's filter kernel)
+constexpr InstanceForm instance_filter_form(bool pluecker, bool vec, bool quads, bool xfmb, bool meshmb, bool nodemb)
 {
-  if (pluecker && !quads && !meshmb) return TRACE_INST_FILTER_MIN_WAVES_TRI_PLUECKER;
-  return inst_min_waves(pluecker, false, quads, xfmb, meshmb);
+  InstanceForm f = instance_form(pluecker, false, vec, quads, xfmb);
+  f.MESHMB = meshmb; f.NODEMB = nodemb;
+  f.EXCL = true;
+  return f;
 }
 
-template <bool PLUECKER, bool VEC, bool QUADS, bool XFMB, bool MESHMB, bool NODEMB>
-__global__ __launch_bounds__(TRACE_BLOCK, inst_filter_min_waves(PLUECKER, QUADS, XFMB, MESHMB)) void trace_instance_filter_kernel(LaunchParams P)
+template <bool Pluecker, bool Vec, bool Quads, bool Xfmb, bool MeshMb, bool NodeMb>
+__global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_filter_form(Pluecker, Vec, Quads, Xfmb, MeshMb, NodeMb))) void trace_instance_filter_kernel(LaunchParams P)
 {
-  constexpr bool OCCLUDED = false, EXCL = true;
-  constexpr bool TOPMB = false; // the EXCL form over a time-dependent top level is trace_instance_top_linear.hip's filter kernel
-  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
+  constexpr InstanceForm FORM = instance_filter_form(Pluecker, Vec, Quads, Xfmb, MeshMb, NodeMb);
+  using Leaf = MeshLeaves;
 #include "trace_instance_body.hip.h"
 }
 

@@ -18,12 +18,19 @@
 namespace rtamd {
 namespace dev {
 
-template <bool PLUECKER, bool OCCLUDED, bool VEC>
-__global__ __launch_bounds__(TRACE_BLOCK, inst_hair_min_waves(PLUECKER, OCCLUDED)) void trace_instance_hair_kernel(LaunchParams P)
+// the general layout over swept boxes; no exclusion scan in the hair leaves: filters beside instanced hair are refused
+constexpr InstanceForm instance_hair_form(bool pluecker, bool occluded, bool vec)
 {
-  constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = false, TOPMB = false; // the general layout over swept boxes
-  constexpr bool EXCL = false; // no exclusion scan in the hair leaves: filters beside instanced hair are refused
-  constexpr bool HAIR = true;
+  InstanceForm f = instance_mesh_mb_form(pluecker, occluded, vec);
+  f.HAIR = true;
+  return f;
+}
+
+template <bool Pluecker, bool Occluded, bool Vec>
+__global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_hair_form(Pluecker, Occluded, Vec))) void trace_instance_hair_kernel(LaunchParams P)
+{
+  constexpr InstanceForm FORM = instance_hair_form(Pluecker, Occluded, Vec);
+  using Leaf = MeshLeaves;
 #include "trace_instance_body.hip.h"
 }
 

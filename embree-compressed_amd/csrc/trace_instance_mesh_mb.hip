@@ -23,12 +23,11 @@
 namespace rtamd {
 namespace dev {
 
-template <bool PLUECKER, bool OCCLUDED, bool VEC>
-__global__ __launch_bounds__(TRACE_BLOCK, inst_min_waves(PLUECKER, OCCLUDED, true, true, true)) void trace_instance_mesh_mb_kernel(LaunchParams P)
+template <bool Pluecker, bool Occluded, bool Vec>
+__global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_mesh_mb_form(Pluecker, Occluded, Vec))) void trace_instance_mesh_mb_kernel(LaunchParams P)
 {
-  constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = false, TOPMB = false; // always the general layout: quads and instance steps allowed
-  constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
-  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
+  constexpr InstanceForm FORM = instance_mesh_mb_form(Pluecker, Occluded, Vec);
+  using Leaf = MeshLeaves;
 #include "trace_instance_body.hip.h"
 }
 

@@ -14,13 +14,19 @@
 namespace rtamd {
 namespace dev {
 
-template <bool PLUECKER, bool OCCLUDED, bool VEC>
-__global__ __launch_bounds__(TRACE_BLOCK, inst_nodemb_min_waves(PLUECKER, OCCLUDED)) void trace_instance_mesh_mb_linear_kernel(LaunchParams P)
+constexpr InstanceForm instance_mesh_mb_linear_form(bool pluecker, bool occluded, bool vec)
 {
-  constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = true;
-  constexpr bool TOPMB = false; // the TOPMB form (a top-level tree of time-dependent nodes) is trace_instance_top_linear.hip's kernel
-  constexpr bool EXCL = false; // the EXCL form of the filter re-traces is trace_instance_filter.hip's kernel
-  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
+  InstanceForm f = instance_mesh_mb_form(pluecker, occluded, vec);
+  f.NODEMB = true;
+  return f;
+}
+
+// each instantiation is asked for the wave bound of its MESHMB twin
+template <bool Pluecker, bool Occluded, bool Vec>
+__global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_mesh_mb_linear_form(Pluecker, Occluded, Vec))) void trace_instance_mesh_mb_linear_kernel(LaunchParams P)
+{
+  constexpr InstanceForm FORM = instance_mesh_mb_linear_form(Pluecker, Occluded, Vec);
+  using Leaf = MeshLeaves;
 #include "trace_instance_body.hip.h"
 }
 

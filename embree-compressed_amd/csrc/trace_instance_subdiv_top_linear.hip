@@ -1,7 +1,7 @@
 // Moving subdivision instances under time-dependent top-level boxes (accel kinds ACCEL_INSTSUBDIV_TOP_LINEAR_GRID / _CBVH_LEAF,
 // inst_subdiv_bounds=linear): the TOPMB form of the subdivision two-level kernel of trace_instance_subdiv.hip - instance entry, the two
 // subdivision leaves, ranking, stacking, the HBM overflow path, the exit marker and the re-read of the world ray are its text
-// (trace_instance_subdiv_body.hip.h) - with one change in which lanes read a time-dependent node.  The node buffer has two sections
+// (trace_instance_body.hip.h) - with one change in which lanes read a time-dependent node.  The node buffer has two sections
 // (accel.h InstanceRecord): the instanced scenes' BVH8s as QNode8s from its start and, from a multiple of 144 bytes on, the top-level
 // tree as QNodeMB8s, referenced in 144-byte units.  A lane outside an instance loads the nine dwordx4 of a QNodeMB8 and interpolates
 // every plane between the node's two blocks at the ray's time, clamped to [0, 1] when the lane took its ray (NaN: 0); a lane inside an
@@ -15,35 +15,17 @@ namespace rtamd {
 namespace dev {
 
 // each instantiation is asked for the wave bound of its swept twin (profiles/instance_subdiv_top_linear_kernel_resources.txt)
-template <typename Leaf, bool OCCLUDED, bool VEC>
-__global__ __launch_bounds__(TRACE_BLOCK, (inst_subdiv_min_waves<Leaf, OCCLUDED>())) void trace_instance_subdiv_top_linear_kernel(LaunchParams P)
+template <typename Leaf, bool Occluded, bool Vec>
+__global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_subdiv_form<Leaf>(Occluded, Vec, true), Leaf::MIN_WAVES)) void trace_instance_subdiv_top_linear_kernel(LaunchParams P)
 {
-  constexpr bool TOPMB = true;
-#include "trace_instance_subdiv_body.hip.h"
-}
-
-template <typename Leaf, bool OCCLUDED>
-inline hipError_t launch_instance_subdiv_top_linear_vec(const LaunchParams& p, hipStream_t stream)
-{
-  const bool vec = (p.stride % 16 == 0) && (((uintptr_t)p.rays) % 16 == 0);
-  // persistent grid = what is resident at once for this instantiation, capped by the host's bound (which sized the spill area)
-  static int occVec = 0, occGen = 0;
-  int& occ = vec ? occVec : occGen;
-  if (occ == 0) {
-    hipError_t e = vec ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_subdiv_top_linear_kernel<Leaf, OCCLUDED, true>, TRACE_BLOCK, 0)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, trace_instance_subdiv_top_linear_kernel<Leaf, OCCLUDED, false>, TRACE_BLOCK, 0);
-    if (e != hipSuccess || occ <= 0) occ = 1;
-  }
-  uint32_t blocks = (p.blocksPerCU ? std::min<uint32_t>(p.blocksPerCU, (uint32_t)occ) : (uint32_t)occ) * p.numCUs;
-  if (blocks > p.gridBlocks) blocks = p.gridBlocks;
-  if (vec) hipLaunchKernelGGL((trace_instance_subdiv_top_linear_kernel<Leaf, OCCLUDED, true>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
-  else hipLaunchKernelGGL((trace_instance_subdiv_top_linear_kernel<Leaf, OCCLUDED, false>), dim3(blocks), dim3(TRACE_BLOCK), 0, stream, p);
-  return hipGetLastError();
+  constexpr InstanceForm FORM = instance_subdiv_form<Leaf>(Occluded, Vec, true);
+#include "trace_instance_body.hip.h"
 }
 
 template <typename Leaf> inline hipError_t launch_instance_subdiv_top_linear(const LaunchParams& p, hipStream_t stream)
 {
-  return p.occluded ? launch_instance_subdiv_top_linear_vec<Leaf, true>(p, stream) : launch_instance_subdiv_top_linear_vec<Leaf, false>(p, stream);
+  return p.occluded ? launch_instance_pair<trace_instance_subdiv_top_linear_kernel<Leaf, true, true>, trace_instance_subdiv_top_linear_kernel<Leaf, true, false>>(p, stream)
+                    : launch_instance_pair<trace_instance_subdiv_top_linear_kernel<Leaf, false, true>, trace_instance_subdiv_top_linear_kernel<Leaf, false, false>>(p, stream);
 }
 
 } // namespace dev

@@ -15,23 +15,29 @@
 namespace rtamd {
 namespace dev {
 
-// each instantiation is asked for the wave bound of its NODEMB twin
-template <bool PLUECKER, bool OCCLUDED, bool VEC>
-__global__ __launch_bounds__(TRACE_BLOCK, inst_nodemb_min_waves(PLUECKER, OCCLUDED)) void trace_instance_top_linear_kernel(LaunchParams P)
+constexpr InstanceForm instance_top_linear_form(bool pluecker, bool occluded, bool vec, bool excl)
 {
-  constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = true, TOPMB = true;
-  constexpr bool EXCL = false;
-  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
+  InstanceForm f = instance_mesh_mb_form(pluecker, occluded, vec);
+  f.NODEMB = f.TOPMB = true;
+  f.EXCL = excl;
+  return f;
+}
+
+// each instantiation is asked for the wave bound of its NODEMB twin
+template <bool Pluecker, bool Occluded, bool Vec>
+__global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_top_linear_form(Pluecker, Occluded, Vec, false))) void trace_instance_top_linear_kernel(LaunchParams P)
+{
+  constexpr InstanceForm FORM = instance_top_linear_form(Pluecker, Occluded, Vec, false);
+  using Leaf = MeshLeaves;
 #include "trace_instance_body.hip.h"
 }
 
 // the filter loop runs closest-hit launches only: the bound of the closest-hit kernel above
-template <bool PLUECKER, bool VEC>
-__global__ __launch_bounds__(TRACE_BLOCK, inst_nodemb_min_waves(PLUECKER, false)) void trace_instance_top_linear_filter_kernel(LaunchParams P)
+template <bool Pluecker, bool Vec>
+__global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_top_linear_form(Pluecker, false, Vec, true))) void trace_instance_top_linear_filter_kernel(LaunchParams P)
 {
-  constexpr bool QUADS = true, XFMB = true, MESHMB = true, NODEMB = true, TOPMB = true;
-  constexpr bool OCCLUDED = false, EXCL = true;
-  constexpr bool HAIR = false; // the HAIR form (line and curve trees below an instance) is trace_instance_hair.hip's kernel
+  constexpr InstanceForm FORM = instance_top_linear_form(Pluecker, false, Vec, true);
+  using Leaf = MeshLeaves;
 #include "trace_instance_body.hip.h"
 }
 

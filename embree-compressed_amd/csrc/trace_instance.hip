@@ -9,8 +9,9 @@
 //      (affinespace.h:110), dir' = xfmVector(world2local, dir) (linearspace3.h:169), tnear and tfar unchanged - t is common to both
 //      spaces; the node-test constants are re-derived from the local ray, an exit marker (REF_INST_EXIT) goes on the stack and the
 //      traversal continues at the instanced scene's root with the same stack;
-//   3. triangle leaves below are the block loop of TriLeaf::intersect (trace_tri.hip) restated: all records of a block of 4 see the tfar
-//      at block entry, the lowest lane wins ties, a later block replaces an equal t.  A hit keeps the instanced scene's geomID / primID and
+//   3. triangle leaves below are TriLeaf::intersect (trace_tri.hip.h), the top-level leaf, on the local ray (written out in the body for
+//      the triangle-only forms, which says why): all records of a block of 4 see the tfar at block entry, the lowest lane wins ties, a
+//      later block replaces an equal t.  A hit the leaf commits is this instance's; it keeps the instanced scene's geomID / primID and
 //      Ng, u, v as computed in LOCAL space (the reference does not transform Ng), and the instance's geomID as instID
 //      (instance_intersector.cpp:57), whatever the context's instID[0] holds;
 //   4. popping the marker restores the world-space ray (read again through the ray's index) and its node-test constants
@@ -26,8 +27,8 @@
 // triangles left (the instanced scene's AccelN, scene.cpp:650-654) - so a quad at a bit-identical t replaces the triangle:
 //   2'. entering an instance whose record has a quad root stacks a second marker (REF_INST_QUADS, the quad root in the entry's
 //       distance word) above the exit marker and continues at the triangle root; without a triangle tree it starts in the quad tree;
-//   3'. popping that marker sets the lane's ST_QUADS bit and continues at the quad root; with the bit set a leaf is the block loop of
-//       QuadLeaf::intersect (trace_quad.hip) restated over pluecker_quad / moeller_quad: 8 candidates per block of 4 records (A =
+//   3'. popping that marker sets the lane's ST_QUADS bit and continues at the quad root; with the bit set a leaf is
+//       QuadLeaf::intersect (trace_quad.hip.h), the top-level leaf: 8 candidates per block of 4 records (A =
 //       (v0, v1, v3) in lanes 0-3, B = (v2, v1, v3) in lanes 4-7), all against the tfar at block entry, one minimum, the lowest lane
 //       wins ties, a later block replaces an equal t.  The QuadRecords lie behind the InstanceRecords in `blobs`, one 64-byte array;
 //   4'. the exit marker clears the bit.

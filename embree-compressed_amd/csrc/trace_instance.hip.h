@@ -13,7 +13,8 @@
 #pragma once
 #include <type_traits>
 #include "trace_leaf.hip.h"
-#include "trace_quad_tests.hip.h"
+#include "trace_tri.hip.h" // the leaves of the mesh family
+#include "trace_quad.hip.h"
 #include "trace_mb.hip.h"
 #include "trace_curve.hip.h" // (and trace_line.hip.h): the leaves of the HAIR form
 #include "instance_xfm.h"
@@ -40,7 +41,8 @@ struct InstanceForm
   bool GRID = false;     // SUBDIV: that leaf is the eager accel's GridCellLeaf (a wave bound depends on it)
 };
 
-// The `Leaf` of the mesh family's kernels: their leaves are the block loops of the body's mesh section, this is never called.
+// The `Leaf` of the mesh family's kernels, kept only as the type the body's SUBDIV text names: the mesh section calls TriLeaf and QuadLeaf
+// (trace_tri.hip.h, trace_quad.hip.h) by the lane's tree and holds the two motion-blur block loops; this is never called.
 struct MeshLeaves : LeafTraits
 {
   template <bool OCCLUDED, bool COUNT> static __device__ __forceinline__ bool intersect(const LaunchParams&, uint32_t, RayState&, WorkCounters&, uint32_t) { return false; }

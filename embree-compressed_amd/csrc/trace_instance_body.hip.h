@@ -396,7 +396,10 @@
           if (r.hit) hitInst = curInst; // instID: instance_intersector.cpp:57
           r.hit |= had;
         } else if (MESHMB && (st & ST_TREE) == (INST_TREE_TRIMB << ST_TREE_SHIFT)) {
-          // the block loop of TriMBLeaf::intersect (trace_tri_mb.hip): a record is tested only when its segment is the ray's itime, on the
+          // the block loop of TriMBLeaf::intersect (trace_tri_mb.hip), written out and not called like the static leaves below: with all four
+          // leaves called, moving two-step triangles below instances trace 3.5 to 3.8 % slower (Pluecker) and 1.2 to 1.5 % (Moeller); with this
+          // loop alone written out the any-hit Moeller HAIR kernels spill 2 VGPRs; with the quad one too nothing spills and the rates are
+          // the parent's (docs/experiments.md, "Mesh leaves below an instance").  A record is tested only when its segment is the ray's itime, on the
           // vertices interpolated to the ray's time; Moeller forms its edges from them (e1 = a - b, e2 = c - a)
           const TriMBRecord* __restrict__ mrecs = (const TriMBRecord*)P.accel.blobs; // the leaf references are rebased to the section's start
           const float time = ray_time(P, rayIdx); // the same value in world and local space
@@ -443,7 +446,7 @@
             }
           }
         } else if (MESHMB && (st & ST_TREE) == (INST_TREE_QUADMB << ST_TREE_SHIFT)) {
-          // the block loop of QuadMBLeaf::intersect (trace_quad_mb.hip): 8 candidates per block of 4 records (A = (v0, v1, v3) in lanes
+          // the block loop of QuadMBLeaf::intersect (trace_quad_mb.hip), written out for the reason given above: 8 candidates per block of 4 records (A = (v0, v1, v3) in lanes
           // 0-3, B = (v2, v1, v3) in lanes 4-7) on the interpolated vertices; records of another segment take no part but keep their lane
           const QuadMBRecord* __restrict__ mrecs = (const QuadMBRecord*)P.accel.blobs; // the leaf references are rebased to the section's start
           const float time = ray_time(P, rayIdx);
@@ -494,56 +497,21 @@
               hitInst = curInst;
             }
           }
-        } else if (MESHMB ? (st & ST_TREE) == ST_QUADS : QUADS && (st & ST_QUADS)) {
-          // the block loop of QuadLeaf::intersect (trace_quad.hip; quad_intersector_pluecker.h:264-299, quad_intersector_moeller.h:251-290)
-          const QuadRecord* __restrict__ quads = (const QuadRecord*)P.accel.blobs; // behind the InstanceRecords: the leaf references are rebased
-          for (uint32_t b = 0; b < count && !occl; b += 4) {
-            const float tfarBlock = r.tfar; // all 8 candidates of a block see the tfar at block entry
-            const uint32_t nb = min(4u, count - b);
-            bool found = false;
-            TriHit best;
-            uint32_t bestLane = 8u, bestPrim = 0, bestGeom = 0;
-            best.t = RT_INF;
-            // QFETCH records are requested before the first one is used; slots past the leaf end re-read the last record and are skipped below
-            for (uint32_t g = 0; g < nb && !occl; g += QFETCH) {
-              float4 V0[QFETCH], V1[QFETCH], V2[QFETCH], V3[QFETCH];
-#pragma unroll
-              for (uint32_t k = 0; k < QFETCH; k++) {
-                const float4* qp = (const float4*)(quads + first + b + min(g + k, nb - 1u));
-                V0[k] = qp[0]; V1[k] = qp[1]; V2[k] = qp[2]; V3[k] = qp[3];
-              }
-#pragma unroll
-              for (uint32_t k = 0; k < QFETCH; k++) {
-                if (g + k >= nb || occl) break;
-                const uint32_t gid = __float_as_uint(V0[k].w), pid = __float_as_uint(V1[k].w);
-#pragma unroll
-                for (uint32_t half = 0; half < 2; half++) { // A then B of this quad (lanes g+k and 4+g+k)
-                  TriHit h;
-                  bool ok = PLUECKER ? pluecker_quad(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h)
-                                     : moeller_quad(r, half ? V2[k] : V0[k], V1[k], V3[k], tfarBlock, half != 0u, h);
-                  if (EXCL) ok = ok && !instance_candidate_excluded(P, rayIdx, curInst, gid, pid, h.t);
-                  if (ok) {
-                    if (OCCLUDED) { occl = true; break; } // Occluded1EpilogM: any valid lane
-                    // select_min over the 8 lanes, lowest lane wins ties
-                    const uint32_t lane = half * 4u + g + k;
-                    if (!found || h.t < best.t || (h.t == best.t && lane < bestLane)) {
-                      best = h;
-                      bestLane = lane;
-                      bestGeom = gid;
-                      bestPrim = pid;
-                      found = true;
-                    }
-                  }
-                }
-              }
-            }
-            if (found) { // Intersect1EpilogM, intersector_epilog.h:293-305; instID: instance_intersector.cpp:57
-              commit_hit(r, best, bestGeom, bestPrim);
-              hitInst = curInst;
-            }
-          }
+        } else if (QUADS) {
+          // the leaves of the top-level static mesh accels (trace_tri.hip.h, trace_quad.hip.h) on the local ray, with this kernel's fetch
+          // widths and, in the EXCL form, its exclusion scan; `blobs` is ONE array of QuadRecords (rebased references).  r.hit as above
+          WorkCounters wc;
+          const uint32_t had = r.hit;
+          r.hit = 0u;
+          const auto excl = [&](uint32_t geomID, uint32_t primID, float t) -> bool { return EXCL && instance_candidate_excluded(P, rayIdx, curInst, geomID, primID, t); };
+          if (MESHMB ? (st & ST_TREE) == ST_QUADS : (st & ST_QUADS) != 0u) occl = QuadLeaf<PLUECKER>::template intersect<OCCLUDED, false, QFETCH>(P, cur, r, wc, rayIdx, excl);
+          else occl = TriLeaf<PLUECKER>::template intersect<OCCLUDED, false, FETCH>(P, cur, r, wc, rayIdx, excl);
+          if (r.hit) hitInst = curInst; // instID: instance_intersector.cpp:57
+          r.hit |= had;
         } else {
-          // the block loop of TriLeaf::intersect (trace_tri.hip; intersector_iterators.h:32-36, epilog intersector_epilog.h:226-307 / :388-450)
+          // QUADS = false: the block loop of TriLeaf::intersect (trace_tri.hip.h; intersector_iterators.h:32-36, epilog intersector_epilog.h:
+          // 226-307 / :388-450) written out.  Through the call above these forms' closest-hit Pluecker kernels, at 128 VGPRs, spill 2 where
+          // they have none, in twelve shapes of the call site; with this loop in the other forms too, Moeller QUADS and HAIR kernels spill
           for (uint32_t b = 0; b < count && !occl; b += 4) {
             const float tfarBlock = r.tfar; // all records of a block see the tfar at block entry
             const uint32_t nb = min(4u, count - b);

@@ -8,8 +8,9 @@
 //       stacks one marker per pending tree, REF_INST_TREE(code) with the tree's root in the distance word, in reverse visiting order,
 //       and continues at the root of the first tree the scene has; two state bits hold the code of the tree it is in;
 //   3". popping such a marker - recognised before the distance cull - sets the two bits to its code and continues at its root.  A
-//       leaf is then, by the code, the block loop of TriLeaf / QuadLeaf (as in the QUADS form) or that of TriMBLeaf::intersect /
-//       QuadMBLeaf::intersect (trace_tri_mb.hip, trace_quad_mb.hip) restated over time_segment, lerp_vertex and the static tests: the
+//       leaf is then, by the code, TriLeaf / QuadLeaf::intersect (as in the QUADS form) or the block loop of TriMBLeaf::intersect /
+//       QuadMBLeaf::intersect (trace_tri_mb.hip, trace_quad_mb.hip) written out in the body over time_segment, lerp_vertex and the static
+//       tests (called, these two cost rate or registers: the body gives the figures): the
 //       ray's time is read from the ray record through the ray's index (the same value in world and local space), a record is tested
 //       only when its segment is the ray's itime, blocks are 4 records, all candidates of a block see the tfar at block entry, the
 //       lowest lane wins ties, a later block replaces an equal t, quads split into A = (v0, v1, v3) and B = (v2, v1, v3).  The

@@ -4,6 +4,7 @@
 // A leaf uses a helper only where its kernels stay the same instructions as with the block written out (tools/kernel_metadata.py
 // --digest); where the compiler schedules the inlined helper differently, the leaf keeps the block, with a comment.
 #pragma once
+#include <type_traits>
 #include "trace_loop.hip.h"
 #include "trace_pool.hip.h"
 
@@ -76,6 +77,11 @@ __device__ __forceinline__ bool candidate_excluded(const LaunchParams& P, uint32
   }
   return false;
 }
+
+// Exclusion policy of the static mesh leaves' lane-per-ray loops: callable as excl(geomID, primID, t) -> bool, true drops a candidate before
+// the block's minimum selection.  This default stands for the top-level scan under P.exclOffsets and is never called: the scan stays
+// written out in the loop, since through any callable 34 of the 42 kernels of trace_tri.hip compile to another schedule
+struct TopLevelExcl {};
 
 // closest-hit epilogue of the lane-per-ray forms (Intersect1EpilogM, intersector_epilog.h:293-305); `best` by value: by reference
 // the leaves compile to another schedule than with the block written out

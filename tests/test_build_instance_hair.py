@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from kernel_metadata import kernel_metadata  # noqa: E402
 
 LIB = os.path.join(ROOT, "embree-compressed_amd", "lib", "libembree3.so")
-# waves per SIMD asked of trace_instance_hair_kernel<PLUECKER, OCCLUDED, *> (trace_instance.hip.h inst_hair_min_waves) and the registers
+# waves per SIMD asked of trace_instance_hair_kernel<PLUECKER, OCCLUDED, *> (trace_instance.hip.h instance_min_waves) and the registers
 # (VGPR + AGPR) a wave may use at that bound on gfx950: 512 / waves, in units of 8
 WAVES = {("true", "false"): 2, ("false", "false"): 2, ("true", "true"): 3, ("false", "true"): 4}
 CAP = {2: 256, 3: 168, 4: 128}

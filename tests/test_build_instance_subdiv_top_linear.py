@@ -1,7 +1,7 @@
 """CPU-side build check (no GPU): the 24 instantiations of the TOPMB form of the subdivision two-level kernel
 (trace_instance_subdiv_top_linear.hip, accel kinds 34 / 35) - the eager leaf and bvh4.compressed.leaf at C = 1..5 x closest hit /
 occluded x aligned / unaligned records - are in the library, none needs scratch or spills vector registers that its swept twin does
-not, and each stays within the registers of the wave bound it is asked for, which is its twin's (inst_subdiv_min_waves).  The library
+not, and each stays within the registers of the wave bound it is asked for, which is its twin's (instance_min_waves).  The library
 exports the new launch symbol, and the 24 kernels of the swept form are still there under their names."""
 import itertools
 import os
@@ -18,7 +18,7 @@ CAP = {2: 256, 3: 168, 4: 128}
 
 
 def _waves(leaf, occluded):
-    """inst_subdiv_min_waves (trace_instance_subdiv.hip.h): the leaf's top-level bound (3; cBVH from C = 4 on 2), one less for the eager
+    """instance_min_waves (trace_instance.hip.h): the leaf's top-level bound (3; cBVH from C = 4 on 2), one less for the eager
     closest-hit kernel"""
     if leaf == "GridCellLeaf":
         return 3 if occluded else 2

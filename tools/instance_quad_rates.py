@@ -3,7 +3,7 @@ bomberman as 727 quads (scaled and snapped as in tests/instance_quads_helpers.py
 against the SAME geometry flattened by the caller into one top-level quad mesh (N x 727 transformed quads, traced by the static quad
 kernel of trace_quad.hip) on the same build.  1 M random rays over the bounds of all instances, device-resident, ONE stream, kernel time
 by HIP events around every step (the batch is restored from a pristine copy before each step, untimed).  Both variants.
-instanced / flattened = price of the two-level traversal with the restated quad block loop (no octet form, 3 waves per SIMD for
+instanced / flattened = price of the two-level traversal with the quad leaf's block loop (no octet form, 3 waves per SIMD for
 closest-hit Pluecker) against a single BVH8 over everything.
 usage: instance_quad_rates.py [steps] [repeats] [N ...]      (default N: 200)"""
 import importlib

@@ -318,6 +318,16 @@ static_assert(sizeof(QuadMBRecord) == 128, "QuadMBRecord must be 128 bytes");
 // rebased by (byte offset of the CurveRecord section) / 80 + the scene's base, a line leaf by (byte offset of the LineRecord section) / 48 +
 // the scene's base: CurveLeaf::intersect and LineLeaf::intersect index `blobs` as ONE array of their record type.  An accel without such
 // trees ends behind the QuadMBRecords and keeps words 4 and 5 of its scene records zero, byte for byte what it was before the key existed.
+// With line segments or flat curves that have time steps below an instance (inst_hair_mb=1 beside inst_hair=1; Accel::instHair and
+// LaunchParams::instHair are 2) a scene has up to eight trees, in the slot order of Scene: triangle, MB triangle, quad, MB quad, curve,
+// MB curve, line, MB line (the visiting order).  The two further trees are QNode8 trees over swept boxes, their nodes placed behind the
+// scene's line tree's, and `blobs` continues behind the LineRecords:
+//   blobs : ... the LineRecords | zero padding to a multiple of 160 bytes | scene 0's CurveMBRecords | scene 1's | ... |
+//           zero padding to a multiple of 80 bytes | scene 0's LineMBRecords | scene 1's | ...
+// Every InstanceSceneRecord of such an accel holds curveMBRoot and lineMBRoot in words 6 and 7 (REF_EMPTY for a missing tree); their leaves
+// are rebased by (byte offset of the section) / 160 or / 80 + the scene's base, so that CurveMBLeaf::intersect and LineMBLeaf::intersect
+// index `blobs` as ONE array of their record type.  An accel without such a tree below it is what it is without the key: words 6 and 7
+// zero, instHair 0 or 1, its end behind the LineRecords or the QuadMBRecords.
 //
 // Kinds ACCEL_INSTMESHMB_LINEAR_PLUECKER / _MOELLER (inst_mb_bounds=linear over scenes built under mb_bounds=linear): `prims` and `blobs`
 // are those of the kinds ACCEL_INSTMESHMB_*; the motion-blur trees keep their time-dependent nodes, so the node array has two sections:
@@ -409,18 +419,26 @@ static_assert(sizeof(InstanceRecord) == sizeof(QuadRecord), "the instance kernel
 // inst_hair=1 (an accel with Accel::instHair set): the scene's curve and line tree follow in the second dwordx4, which the kernel's HAIR form
 // loads as well; their codes keep bit 1 clear ("bit 1 = a motion-blur tree").  Visiting order: triangles, motion-blur triangles, quads,
 // motion-blur quads, curves, lines (Scene::commit's).  An accel without hair trees keeps these two words zero and is never read there.
-enum : uint32_t { INST_TREE_TRI = 0, INST_TREE_QUAD = 1, INST_TREE_TRIMB = 2, INST_TREE_QUADMB = 3, INST_TREE_CURVE = 4, INST_TREE_LINE = 5 };
+// inst_hair_mb=1 (Accel::instHair == 2): the motion-blur curve and line tree fill the rest of the second dwordx4, words 6 and 7, read by the
+// kernel's HAIRMB form; their codes have bit 1 set like the other motion-blur trees' and still fit three bits.  Visiting order: triangles,
+// motion-blur triangles, quads, motion-blur quads, curves, motion-blur curves, lines, motion-blur lines - not the word order.  An accel
+// without such trees keeps the two words zero.
+enum : uint32_t { INST_TREE_TRI = 0, INST_TREE_QUAD = 1, INST_TREE_TRIMB = 2, INST_TREE_QUADMB = 3, INST_TREE_CURVE = 4, INST_TREE_LINE = 5,
+                  INST_TREE_CURVEMB = 6, INST_TREE_LINEMB = 7 };
 struct alignas(16) InstanceSceneRecord
 {
   uint32_t triRoot, triMBRoot, quadRoot, quadMBRoot; // rebased root references, REF_EMPTY for a missing tree
   uint32_t curveRoot, lineRoot;                      // (words 4 and 5) accels with hair trees: the same for the curve and the line tree; zero otherwise
-  uint32_t pad[10];                                  // zero
+  uint32_t curveMBRoot, lineMBRoot;                  // (words 6 and 7) accels with moving-hair trees: the same for the motion-blur curve and line tree; zero otherwise
+  uint32_t pad[8];                                   // zero
 };
 static_assert(offsetof(InstanceSceneRecord, curveRoot) == 16 && offsetof(InstanceSceneRecord, lineRoot) == 20, "the hair roots lead the second dwordx4");
+static_assert(offsetof(InstanceSceneRecord, curveMBRoot) == 24 && offsetof(InstanceSceneRecord, lineMBRoot) == 28, "the moving-hair roots end the second dwordx4");
 static_assert(sizeof(InstanceSceneRecord) == sizeof(InstanceRecord), "the instance kernel indexes InstanceRecords and InstanceSceneRecords as one array");
 // Markers of the kernel's MESHMB form, one value per pending tree: REF_INST_TREE(code), stacked above the exit marker in reverse
 // visiting order with the tree's root in the distance word; popping one switches the lane's leaf kind to `code` and continues at that
-// root.  REF_INST_TREE(INST_TREE_QUAD) is REF_INST_QUADS; the triangle tree is always the first one and never waits.
+// root.  REF_INST_TREE(INST_TREE_QUAD) is REF_INST_QUADS; the triangle tree is always the first one and never waits.  Every marker up to
+// REF_INST_TREE(INST_TREE_LINEMB) = REF_INST_TREE(7) is leaf-flagged with count 0 like the exit marker: codes stay below 2^26, the count field.
 inline constexpr uint32_t REF_INST_TREE(uint32_t code) { return 0x80000000u + code; }
 static_assert(REF_INST_TREE(INST_TREE_QUAD) == REF_INST_QUADS, "the quad tree's marker is the one of the QUADS form");
 

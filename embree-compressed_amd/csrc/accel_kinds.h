@@ -28,6 +28,7 @@ hipError_t launch_trace_curve_mb(const LaunchParams& p, hipStream_t stream);  //
 hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  // trace_instance.hip
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb.hip
 hipError_t launch_trace_instance_hair(const LaunchParams& p, hipStream_t stream);    // trace_instance_hair.hip (launch_trace_instance_mesh_mb diverts to it when LaunchParams::instHair is set)
+hipError_t launch_trace_instance_hair_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_hair_mb.hip (... when LaunchParams::instHair is 2)
 hipError_t launch_trace_instance_subdiv(const LaunchParams& p, hipStream_t stream);  // trace_instance_subdiv.hip
 hipError_t launch_trace_instance_mesh_mb_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb_linear.hip
 hipError_t launch_trace_instance_top_linear(const LaunchParams& p, hipStream_t stream); // trace_instance_top_linear.hip (closest hit, any hit and its own EXCL form)

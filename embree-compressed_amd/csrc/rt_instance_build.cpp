@@ -348,6 +348,7 @@ struct MeshInstances
   bool anyMeshMotion = false; // an instanced scene has a traceable motion-blur accel
   bool anyLinear = false;     // ... built under mb_bounds=linear (kinds 26..29): its nodes are QNodeMB8s
   bool anyHair = false;       // inst_hair=1: an instanced scene has a traceable curve or line accel (the kinds ACCEL_INSTMESHMB_* with Accel::instHair)
+  bool anyHairMB = false;     // inst_hair_mb=1: ... a traceable motion-blur curve or line accel (implies anyHair; Accel::instHair == 2)
   bool topLinear = false;     // inst_bounds=linear and anyMotion: the top-level tree is made of QNodeMB8s (kinds ACCEL_INSTTOP_LINEAR_*)
   uint32_t pendingMax = 0;    // most trees of one instanced scene, minus one
   bool intersectFilter = false, occludedFilter = false; // inst_filters=1: an enabled geometry of a placed instance's scene has such a filter
@@ -371,6 +372,9 @@ struct MeshInstances
 // arithmetic (their robust / fast traversal).  A top scene with any such tree below it is of the kinds ACCEL_INSTMESHMB_*, over swept
 // boxes only: beside a linear kind, and beside geometry filters below the instances (the hair form of the kernel has no exclusion scan),
 // the commit is refused.  Without the key every refusal is what it was.
+// The same with time steps (inst_hair_mb=1 beside inst_hair=1, Device::inst_hair_mb_lines_enabled / inst_hair_mb_curves_enabled): the
+// scene's motion-blur curve and line accels are two further trees under the same rules, swept boxes only - built under mb_bounds=linear
+// they hold QNodeMB8s and the commit is refused.  Without that key moving hair below an instance is refused as before.
 // Subdivision scenes below an instance: an instanced scene that enables a subdivision mesh is left to build_instance_subdiv_accel when
 // the device takes such scenes (Device::inst_subdiv_enabled); otherwise it is refused here with the message of the config, as before.
 MeshInstances classify_mesh_instances(const Scene* s)
@@ -391,9 +395,11 @@ MeshInstances classify_mesh_instances(const Scene* s)
   // scenes of the instances that are placed (as Scene::commit records triIntersectFilter / triOccludedFilter of its own meshes)
   const bool filtersOk = s->device->inst_filters;
   const bool hairLinesOk = s->device->inst_hair_lines_enabled(), hairCurvesOk = s->device->inst_hair_curves_enabled();
+  const bool hairLinesMBOk = s->device->inst_hair_mb_lines_enabled(), hairCurvesMBOk = s->device->inst_hair_mb_curves_enabled(); // inst_hair_mb=1
   auto at_instance = [](const char* text, unsigned gid) { return std::string(text) + " (instance " + std::to_string(gid) + ")"; };
   unsigned hairGeom = 0, filterGeom = 0; // the first instance whose scene holds hair / a geometry filter: named by the refusals behind the loop
-  bool anyFilter = false;
+  unsigned hairLinearGeom = 0;           // ... holds a moving-hair tree of QNodeMB8s
+  bool anyFilter = false, anyHairLinear = false;
   // inst_bounds=linear: will this top scene get the time-dependent top level?  Known before the scenes are examined, so that the refusal of
   // moving meshes below it has its own text from the first instance on (a moving instance of an empty scene is not placed and does not count)
   bool wantTopLinear = false;
@@ -425,7 +431,7 @@ MeshInstances classify_mesh_instances(const Scene* s)
     for (Geometry* og : o->geometries) {
       if (!og || !og->enabled) continue;
       if (og->isFlatCubicCurve() ? hairCurvesOk : (og->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE && hairLinesOk)) { // inst_hair=1
-        if (og->timeSteps != 1)
+        if (og->timeSteps != 1 && !(og->isFlatCubicCurve() ? hairCurvesMBOk : hairLinesMBOk))
           RT_THROW(RTC_ERROR_INVALID_OPERATION, at_instance("motion blur of line segments and flat curves inside an instanced scene is not supported", gid));
         if (!filtersOk && (og->intersectFilter || og->occludedFilter)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
         continue;
@@ -437,15 +443,18 @@ MeshInstances classify_mesh_instances(const Scene* s)
     }
     for (const Accel* oa : o->accels())
       if (oa != &o->triAccel && !(quadsOk && oa == &o->quadAccel) && !(meshMotionOk && (oa == &o->triMBAccel || oa == &o->quadMBAccel)) &&
-          !(hairCurvesOk && oa == &o->curveAccel) && !(hairLinesOk && oa == &o->lineAccel) && oa->kind != ACCEL_NONE)
+          !(hairCurvesOk && oa == &o->curveAccel) && !(hairLinesOk && oa == &o->lineAccel) && !(hairCurvesMBOk && oa == &o->curveMBAccel) &&
+          !(hairLinesMBOk && oa == &o->lineMBAccel) && oa->kind != ACCEL_NONE)
         RT_THROW(RTC_ERROR_INVALID_OPERATION, only);
     if (!filtersOk && (o->triIntersectFilter || o->triOccludedFilter)) RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry filter functions inside an instanced scene are not supported");
     const bool tris = o->triAccel.traceable(), quads = o->quadAccel.traceable();
     const bool trisMB = o->triMBAccel.traceable(), quadsMB = o->quadMBAccel.traceable();
     const bool curves = hairCurvesOk && o->curveAccel.traceable(), lines = hairLinesOk && o->lineAccel.traceable();
-    if (!tris && !quads && !trisMB && !quadsMB && !curves && !lines) continue; // empty scene: nothing to hit
+    const bool curvesMB = hairCurvesMBOk && o->curveMBAccel.traceable(), linesMB = hairLinesMBOk && o->lineMBAccel.traceable();
+    if (!tris && !quads && !trisMB && !quadsMB && !curves && !lines && !curvesMB && !linesMB) continue; // empty scene: nothing to hit
     std::string names; // this scene's traceable accels
-    for (const char* nm : {tris ? "triangle" : "", trisMB ? "motion blur triangle" : "", quads ? "quad" : "", quadsMB ? "motion blur quad" : "", curves ? "curve" : "", lines ? "line" : ""})
+    for (const char* nm : {tris ? "triangle" : "", trisMB ? "motion blur triangle" : "", quads ? "quad" : "", quadsMB ? "motion blur quad" : "", curves ? "curve" : "",
+                           curvesMB ? "motion blur curve" : "", lines ? "line" : "", linesMB ? "motion blur line" : ""})
       if (*nm) names += std::string(names.empty() ? "" : ", ") + nm;
     // scenes that disagree while a motion-blur accel is involved: the message names the accels on either side
     auto disagree = [&](bool thisPl) {
@@ -453,14 +462,16 @@ MeshInstances classify_mesh_instances(const Scene* s)
       return "the instanced scenes of one scene disagree in accel kind (Pluecker / robust and Moeller / fast): the scene of instance " + std::to_string(gid) + " has " +
              ar[thisPl] + " accels (" + names + "), the scene of instance " + std::to_string(kindGeom) + " " + ar[!thisPl] + " ones (" + kindNames + "): instances need one arithmetic";
     };
-    if (trisMB || quadsMB || curves || lines) {
-      // one arithmetic per top scene, over all six trees of every instanced scene
-      struct { bool have, pl; const char* name; } const t[6] = {{tris, o->triAccel.kind == ACCEL_TRI_PLUECKER, "triangle"},
+    if (trisMB || quadsMB || curves || lines || curvesMB || linesMB) {
+      // one arithmetic per top scene, over all eight trees of every instanced scene
+      struct { bool have, pl; const char* name; } const t[8] = {{tris, o->triAccel.kind == ACCEL_TRI_PLUECKER, "triangle"},
                                                                 {trisMB, kind_row(o->triMBAccel.kind).robust, "motion blur triangle"},
                                                                 {quads, o->quadAccel.kind == ACCEL_QUAD_PLUECKER, "quad"},
                                                                 {quadsMB, kind_row(o->quadMBAccel.kind).robust, "motion blur quad"},
                                                                 {curves, kind_row(o->curveAccel.kind).robust, "curve"},
-                                                                {lines, kind_row(o->lineAccel.kind).robust, "line"}};
+                                                                {curvesMB, kind_row(o->curveMBAccel.kind).robust, "motion blur curve"},
+                                                                {lines, kind_row(o->lineAccel.kind).robust, "line"},
+                                                                {linesMB, kind_row(o->lineMBAccel.kind).robust, "motion blur line"}};
       std::string pl, mo;
       for (const auto& e : t)
         if (e.have) (e.pl ? pl : mo) += std::string((e.pl ? pl : mo).empty() ? "" : ", ") + e.name;
@@ -468,15 +479,22 @@ MeshInstances classify_mesh_instances(const Scene* s)
         RT_THROW(RTC_ERROR_INVALID_OPERATION, "the accels of an instanced scene disagree in kind (Pluecker / robust: " + pl + "; Moeller / fast: " + mo + "): instances need one arithmetic");
       const bool scenePl = !pl.empty();
       if (haveKind && scenePl != c.pluecker) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(scenePl));
-      if (curves || lines) {
+      if (curves || lines || curvesMB || linesMB) {
         if (!c.anyHair) hairGeom = gid;
         c.anyHair = true;
+      }
+      if (curvesMB || linesMB) { // their nodes must be swept QNode8s: refused behind the loop otherwise
+        c.anyHairMB = true;
+        if (!anyHairLinear && ((curvesMB && o->curveMBAccel.nodesAreMB()) || (linesMB && o->lineMBAccel.nodesAreMB()))) {
+          anyHairLinear = true;
+          hairLinearGeom = gid;
+        }
       }
       c.anyMeshMotion |= trisMB || quadsMB;
       for (const Accel* m : {trisMB ? &o->triMBAccel : nullptr, quadsMB ? &o->quadMBAccel : nullptr})
         if (m) (m->nodesAreMB() ? c.anyLinear : anySwept) = true;
     }
-    c.pendingMax = std::max(c.pendingMax, (uint32_t)tris + (uint32_t)trisMB + (uint32_t)quads + (uint32_t)quadsMB + (uint32_t)curves + (uint32_t)lines - 1u);
+    c.pendingMax = std::max(c.pendingMax, (uint32_t)tris + (uint32_t)trisMB + (uint32_t)quads + (uint32_t)quadsMB + (uint32_t)curves + (uint32_t)lines + (uint32_t)curvesMB + (uint32_t)linesMB - 1u);
     // the kernel runs ONE arithmetic on both levels and in both leaves: every accel below this scene is Pluecker / robust, or every one
     // Moeller / fast
     if (tris && quads && (o->triAccel.kind == ACCEL_TRI_PLUECKER) != (o->quadAccel.kind == ACCEL_QUAD_PLUECKER))
@@ -484,7 +502,8 @@ MeshInstances classify_mesh_instances(const Scene* s)
                                             "as a robust scene under quad_accel=bvh8.quad4v builds them): instances need one arithmetic");
     const bool pl = tris ? o->triAccel.kind == ACCEL_TRI_PLUECKER
                   : quads ? o->quadAccel.kind == ACCEL_QUAD_PLUECKER
-                  : kind_row(trisMB ? o->triMBAccel.kind : quadsMB ? o->quadMBAccel.kind : curves ? o->curveAccel.kind : o->lineAccel.kind).robust;
+                  : kind_row(trisMB ? o->triMBAccel.kind : quadsMB ? o->quadMBAccel.kind : curves ? o->curveAccel.kind : curvesMB ? o->curveMBAccel.kind
+                             : lines ? o->lineAccel.kind : o->lineMBAccel.kind).robust;
     if (haveKind && pl != c.pluecker) {
       if (!c.anyQuads && !quads && !c.anyMeshMotion && !c.anyHair) RT_THROW(RTC_ERROR_INVALID_OPERATION, "the instanced scenes of one scene disagree in triangle accel kind (robust and not robust)");
       if (c.anyMeshMotion || c.anyHair) RT_THROW(RTC_ERROR_INVALID_OPERATION, disagree(pl));
@@ -512,6 +531,8 @@ MeshInstances classify_mesh_instances(const Scene* s)
   if (c.anyLinear && anySwept) RT_THROW(RTC_ERROR_UNKNOWN, "instance builder: motion blur accels of both node types below one scene");
   c.topLinear = c.anyMotion && s->device->inst_top_linear_enabled();
   if (c.topLinear && anySwept) RT_THROW(RTC_ERROR_INVALID_OPERATION, topLinearNeedsLinear);
+  if (anyHairLinear)
+    RT_THROW(RTC_ERROR_INVALID_OPERATION, at_instance("inst_hair_mb=1: motion blur line segments and flat curves below an instance are traced over swept boxes only; not under mb_bounds=linear", hairLinearGeom));
   if (c.anyHair && (c.topLinear || c.anyLinear))
     RT_THROW(RTC_ERROR_INVALID_OPERATION, at_instance("inst_hair=1: line segments and flat curves below an instance are traced over swept boxes only (kinds 22 / 23); not beside "
                                                       "inst_bounds=linear or inst_mb_bounds=linear trees", hairGeom));
@@ -544,6 +565,8 @@ uint32_t instance_kind(const MeshInstances& c)
 //           | one InstanceSceneRecord per scene, which holds its four roots | TriMBRecords | QuadMBRecords
 //           and with anyHair: | CurveRecords from a multiple of 80 bytes | LineRecords from a multiple of 48 bytes; the scene records then
 //           hold six roots, REF_EMPTY for a missing hair tree too (without anyHair the two words stay zero, the bytes what they were)
+//           and with anyHairMB: | CurveMBRecords from a multiple of 160 bytes | LineMBRecords from a multiple of 80 bytes; the scene records
+//           then hold eight roots (without anyHairMB words 6 and 7 stay zero and the array ends where it did)
 //   nodes : with anyLinear in two sections - `A.nodes` with the top-level tree and the static trees, `A.nodesMB` with the motion-blur
 //           trees, child indices counted in 144-byte units from the start of the uploaded buffer, and `A.nodeImage` the two with the
 //           padding between them.  With topLinear the top-level tree leads `A.nodesMB` instead of `A.nodes`, and the general layout
@@ -551,7 +574,7 @@ uint32_t instance_kind(const MeshInstances& c)
 // maxDepth (launch_on reserves 7 * (maxDepth + 1) + 2 stack entries) =
 //     the top-level depth
 //   + 1 for the exit marker
-//   + the largest number of pending-tree markers any instanced scene can have stacked at once (its tree count - 1, at most 5; in the
+//   + the largest number of pending-tree markers any instanced scene can have stacked at once (its tree count - 1, at most 7; in the
 //     kinds 14..21: 1 as soon as any scene has quads)
 //   + the deepest of all instanced trees (the trees of a scene are never stacked together: a marker is popped only when the entries
 //     of the tree before it are gone).
@@ -579,7 +602,12 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
       n.curves += records(o->curveAccel, sizeof(CurveRecord));
       n.lines += records(o->lineAccel, sizeof(LineRecord));
     }
-    for (const Accel* t : {&o->triAccel, &o->triMBAccel, &o->quadAccel, &o->quadMBAccel, c.anyHair ? &o->curveAccel : nullptr, c.anyHair ? &o->lineAccel : nullptr})
+    if (c.anyHairMB) {
+      n.curveMB += records(o->curveMBAccel, sizeof(CurveMBRecord));
+      n.lineMB += records(o->lineMBAccel, sizeof(LineMBRecord));
+    }
+    for (const Accel* t : {&o->triAccel, &o->triMBAccel, &o->quadAccel, &o->quadMBAccel, c.anyHair ? &o->curveAccel : nullptr, c.anyHair ? &o->lineAccel : nullptr,
+                           c.anyHairMB ? &o->curveMBAccel : nullptr, c.anyHairMB ? &o->lineMBAccel : nullptr})
       if (t && t->traceable()) { // a motion-blur tree has nodes of one type or of the other
         staticNodes += t->nodes.size();
         mbNodes += t->nodesMB.size();
@@ -589,7 +617,7 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
   add_section(blobBytes, c.placed.size(), sizeof(InstanceRecord)); // (the records start the array: write_instance_records)
   Section quadSec = add_section(blobBytes, n.quads, sizeof(QuadRecord)); // quad leaves index `blobs` as one array of 64-byte records
   Section stepSec = add_section(blobBytes, n.steps, sizeof(InstanceStep));
-  Section sceneSec{}, triMBSec{}, quadMBSec{}, curveSec{}, lineSec{};
+  Section sceneSec{}, triMBSec{}, quadMBSec{}, curveSec{}, lineSec{}, curveMBSec{}, lineMBSec{};
   if (general) {
     sceneSec = add_section(blobBytes, ds.scenes.size(), sizeof(InstanceSceneRecord));
     triMBSec = add_section(blobBytes, n.triMB, sizeof(TriMBRecord));    // motion-blur triangle leaves index `blobs` as one array of 96-byte records
@@ -597,6 +625,10 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
     if (c.anyHair) { // (an accel without hair trees ends behind the QuadMBRecords, as it always did)
       curveSec = add_section(blobBytes, n.curves, sizeof(CurveRecord)); // curve leaves index `blobs` as one array of 80-byte records (CurveLeaf::intersect)
       lineSec = add_section(blobBytes, n.lines, sizeof(LineRecord));    // line leaves as one of 48-byte records (LineLeaf::intersect)
+    }
+    if (c.anyHairMB) { // (an accel without moving-hair trees ends behind the LineRecords)
+      curveMBSec = add_section(blobBytes, n.curveMB, sizeof(CurveMBRecord)); // motion-blur curve leaves index `blobs` as one array of 160-byte records (CurveMBLeaf::intersect)
+      lineMBSec = add_section(blobBytes, n.lineMB, sizeof(LineMBRecord));    // motion-blur line leaves as one of 80-byte records (LineMBLeaf::intersect)
     }
   }
   // the node buffer: the QNode8s, and (kinds ACCEL_INSTMESHMB_LINEAR_*, no others have any) zero padding and the QNodeMB8s from the
@@ -643,6 +675,12 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
       sc.lineRoot = append_static(o->lineAccel, place_leaf_records(A.blobs, lineSec, o->lineAccel, "too many instanced line segments for the 26-bit leaf reference (the line section: their records "
                                                                                                    "follow all other records in one array)"));
     }
+    if (c.anyHairMB) { // the two moving-hair trees: swept QNode8s (classify_mesh_instances has refused QNodeMB8s) over motion-blur records
+      sc.curveMBRoot = append_static(o->curveMBAccel, place_leaf_records(A.blobs, curveMBSec, o->curveMBAccel, "too many instanced motion blur curve segments for the 26-bit leaf reference (the motion "
+                                                                                                               "blur curve section: their records follow all static records in one array)"));
+      sc.lineMBRoot = append_static(o->lineMBAccel, place_leaf_records(A.blobs, lineMBSec, o->lineMBAccel, "too many instanced motion blur line segments for the 26-bit leaf reference (the motion blur "
+                                                                                                           "line section: their records follow all other records in one array)"));
+    }
     quadRootOf.push_back(sc.quadRoot);
     rootOf.push_back(general ? (uint32_t)(sceneSec.base() + sceneSec.used) : sc.triRoot); // general layout: the scene's InstanceSceneRecord, in 64-byte units
     if (general) memcpy(A.blobs.data() + sceneSec.offset + sceneSec.used++ * sizeof(sc), &sc, sizeof(sc));
@@ -656,7 +694,7 @@ Scene::InstanceCounts layout_mesh_instances(Scene* s, const MeshInstances& c)
     A.blobOffsets = {(uint32_t)A.nodesMB.size(), (uint32_t)mbSec.base()};
   }
   A.kind = instance_kind(c);
-  A.instHair = c.anyHair;
+  A.instHair = c.anyHairMB ? 2u : c.anyHair ? 1u : 0u;
   A.robust = c.pluecker ? 1 : 0;
   A.maxDepth += 1u + (general ? c.pendingMax : c.anyQuads ? 1u : 0u) + deepest;
   return n;

@@ -36,6 +36,7 @@ struct Device : RefCounted
   std::string inst_subdiv_bounds = "swept"; // top-level boxes of moving subdivision instances (Scene::instSubdivAccel): "swept" (QNode8, kinds 24 / 25) or "linear" (a top-level tree of QNodeMB8s, kinds ACCEL_INSTSUBDIV_TOP_LINEAR_*)
   bool inst_filters = false; // "inst_filters=1": filter functions run on hits below mesh instances (geometry filters inside instanced mesh scenes, RTCIntersectContext::filter on scenes with mesh instances); 0, the default: both are refused as before
   bool inst_hair = false; // "inst_hair=1": an instanced scene may hold static line segments and flat curves, alone or beside its triangle and quad meshes (the HAIR form of the two-level kernel, trace_instance_hair.hip); 0, the default: refused as before
+  bool inst_hair_mb = false; // "inst_hair_mb=1", beside inst_hair=1: the line segments and flat curves of an instanced scene may have time steps (the HAIRMB form of the two-level kernel, trace_instance_hair_mb.hip); 0, the default: refused as before
   std::string line_accel = "default"; // flat linear curves: default / bvh8.line4i / bvh4.line4i, all the one BVH8 over LineRecords (build_line_accel raises for any other at commit)
   std::string line_accel_mb = "default"; // flat linear curves with time steps: default / bvh8.line4imb / bvh4.line4imb, all the one BVH8 over LineMBRecords (build_linemb_accel raises for any other at commit)
   bool lineAccelMBNamed = false; // "line_accel_mb=" given (a host-only device builds the motion-blur line accel only then, lines_mb_enabled())
@@ -256,6 +257,10 @@ struct Device : RefCounted
   // inst_accel=, and for the flat cubic curves hair_accel= as well; under any other config it refuses them as before.
   bool inst_hair_lines_enabled() const { return inst_hair && (gpu >= 0 || instAccelNamed); }
   bool inst_hair_curves_enabled() const { return inst_hair && (gpu >= 0 || (instAccelNamed && hairAccelNamed)); }
+  // The same with time steps (inst_hair_mb=1, which acts only where inst_hair=1 acts): a host-only device honours the key only when its
+  // config also names the motion-blur accel of the type, line_accel_mb= / hair_accel_mb=, as it builds those accels only then.
+  bool inst_hair_mb_lines_enabled() const { return inst_hair_mb && inst_hair_lines_enabled() && lines_mb_enabled(); }
+  bool inst_hair_mb_curves_enabled() const { return inst_hair_mb && inst_hair_curves_enabled() && curves_mb_enabled(); }
   // Time-dependent top-level boxes above moving subdivision instances (inst_subdiv_bounds=linear, independent of inst_bounds): a host-only
   // device honours the key where it takes moving subdivision instances at all.
   bool inst_subdiv_top_linear_enabled() const { return inst_subdiv_bounds == "linear" && inst_subdiv_enabled() && inst_motion_enabled(); }
@@ -399,7 +404,7 @@ struct Accel
   uint32_t robust = 0;
   uint32_t maxDepth = 0;
   uint32_t blobStride = 0;
-  bool instHair = false;   // kinds ACCEL_INSTMESHMB_*: an instanced scene has a curve or a line tree (inst_hair=1; accel.h InstanceSceneRecord) -> LaunchParams::instHair
+  uint32_t instHair = 0;   // kinds ACCEL_INSTMESHMB_*: 1 = an instanced scene has a curve or a line tree (inst_hair=1; accel.h InstanceSceneRecord), 2 = one has a motion-blur curve or line tree as well (inst_hair_mb=1) -> LaunchParams::instHair
   uint32_t cbvhLevels = 0; // ACCEL_INSTSUBDIV_CBVH_LEAF / ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF: the compression level C of the instanced scenes' blobs (0: the scene's own level applies)
   size_t leafCount = 0;
   // device copies, one set per shard of the device (replicated accel)
@@ -418,7 +423,8 @@ struct Accel
   // (static trees, and in the kinds 30 / 31 the top-level tree), the QNodeMB8 section is described by the accel's two blobOffsets words
   // (the kinds 34 / 35: its words 2 and 3)
   // (nodesAreMB: the instance builder asks it of the triangle and quad motion-blur accels of an instanced scene only; a scene with a
-  // motion-blur line or curve accel is refused below an instance before it gets there, and the static ones hold QNode8s)
+  // motion-blur line or curve accel is refused below an instance before it gets there unless inst_hair_mb=1 takes it, which asks the same of
+  // those two and refuses QNodeMB8s; the static ones hold QNode8s)
   bool nodesAreMB() const { return kind_row(kind).nodes == NODES_MB8; }
   bool twoSections() const { return kind_row(kind).nodes == NODES_TWO_SECTION; }
   size_t nodeCount() const { return nodesAreMB() ? nodesMB.size() : nodes.size(); }
@@ -474,7 +480,7 @@ struct Scene : RefCounted
   bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
   // records the layout of instAccel placed in `blobs` behind the InstanceRecords, as build_instance_accel counted them (host only: the
   // verbose line of commit prints them)
-  struct InstanceCounts { size_t quads = 0, steps = 0, triMB = 0, quadMB = 0, curves = 0, lines = 0; };
+  struct InstanceCounts { size_t quads = 0, steps = 0, triMB = 0, quadMB = 0, curves = 0, lines = 0, curveMB = 0, lineMB = 0; };
   InstanceCounts instCounts;
 
   explicit Scene(Device* d);

@@ -245,7 +245,7 @@ void Accel::clear()
   maxDepth = 0;
   blobStride = 0;
   cbvhLevels = 0;
-  instHair = false;
+  instHair = 0;
   leafCount = 0;
 }
 
@@ -435,6 +435,9 @@ void Scene::commit()
             nQuads, nTriMB, nQuadMB, instAccel.maxDepth);
     if (instAccel.instHair) // inst_hair=1 and a curve or line tree below an instance
       fprintf(stderr, "embree3-amd: instance accel kind %u: %zu instanced curves, %zu instanced line segments\n", instAccel.kind, instCounts.curves, instCounts.lines);
+    if (instAccel.instHair == 2) // inst_hair_mb=1 and a motion-blur curve or line tree below an instance (hair level 2: the HAIRMB form of the kernel)
+      fprintf(stderr, "embree3-amd: instance accel kind %u: hair level 2, %zu instanced motion blur curve segment records, %zu instanced motion blur line segment records\n", instAccel.kind,
+              instCounts.curveMB, instCounts.lineMB);
     if (instAccel.twoSections())
       fprintf(stderr, "embree3-amd: instance accel kind %u: %zu time-dependent nodes (%zu B) from node index %u in 144-byte units, node buffer %zu B\n", instAccel.kind,
               instAccel.nodesMB.size(), instAccel.nodesMB.size() * sizeof(QNodeMB8), instAccel.blobOffsets[1], instAccel.nodeImage.size());

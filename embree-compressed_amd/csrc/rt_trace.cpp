@@ -84,7 +84,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
     spillBytes = (size_t)p.gridBlocks * TRACE_BLOCK * (size_t)p.spillDepth * 8u + 16u;
   }
   p.counters = x.counters;
-  p.instHair = A.instHair ? 1u : 0u; // line and curve trees below the instances: the HAIR form of the two-level kernel
+  p.instHair = A.instHair; // line and curve trees below the instances: 1 the HAIR form of the two-level kernel, 2 (moving ones among them) the HAIRMB form
   p.cbvhLevels = A.cbvhLevels ? A.cbvhLevels : s->compressionLevel; // (instanced cBVH blobs, kinds 25 / 35, carry the level of the scenes they come from)
   // cBVH blob walk: quad form (four lanes per ray, two-stage visits) or one ray per lane.  Coherent batches (RTC_INTERSECT_CONTEXT_FLAG_COHERENT,
   // e.g. the primary rays of viewer_stream_device.cpp:305) keep most lanes at blobs at once; since the two-stage visits the quad form is the faster

@@ -49,7 +49,8 @@ struct LaunchParams
   const uint32_t* exclT;
   uint32_t poolKernel;     // 1: ray-pool skeleton (trace_pool.hip.h), 0: lane-per-ray skeleton (trace_loop.hip.h)
   uint32_t instHair;       // kinds ACCEL_INSTMESHMB_*: 1 = the accel holds curve or line trees below its instances (Accel::instHair): the HAIR form of
-                           // the two-level kernel (trace_instance_hair.hip).  In what was padding in front of `survivors`: no other member moves
+                           // the two-level kernel (trace_instance_hair.hip); 2 = motion-blur curve or line trees too: the HAIRMB form
+                           // (trace_instance_hair_mb.hip).  In what was padding in front of `survivors`: no other member moves
   // Root cull pass (trace_cull.hip.h): when `survivors` is set, a streaming pre-pass has tested every ray against the root node's
   // children and appended the indices of the rays that hit at least one of them to per-work-queue lists: queue q's list starts
   // at survivors[q * perQ] (perQ = ceil(count / TRACE_QUEUES), its capacity) and holds queues[q * TRACE_QUEUE_STRIDE + 1] entries;

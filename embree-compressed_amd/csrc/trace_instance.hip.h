@@ -7,6 +7,7 @@
 //   trace_instance_top_linear.hip          trace_instance_top_linear[_filter]_kernel  TOPMB (and its EXCL form)
 //   trace_instance_filter.hip              trace_instance_filter_kernel               EXCL
 //   trace_instance_hair.hip                trace_instance_hair_kernel                 HAIR
+//   trace_instance_hair_mb.hip             trace_instance_hair_mb_kernel              HAIRMB
 //   trace_instance_subdiv.hip              trace_instance_subdiv_kernel               SUBDIV (through trace_instance_subdiv.hip.h)
 //   trace_instance_subdiv_top_linear.hip   trace_instance_subdiv_top_linear_kernel    SUBDIV, TOPMB
 // One unit per kernel template so that the instantiations compile beside each other.
@@ -17,6 +18,8 @@
 #include "trace_quad.hip.h"
 #include "trace_mb.hip.h"
 #include "trace_curve.hip.h" // (and trace_line.hip.h): the leaves of the HAIR form
+#include "trace_curve_mb.hip.h" // the leaves of the HAIRMB form
+#include "trace_line_mb.hip.h"
 #include "instance_xfm.h"
 
 namespace rtamd {
@@ -37,6 +40,7 @@ struct InstanceForm
   bool TOPMB = false;    // NODEMB, and the top-level tree is one of them
   bool EXCL = false;     // the exclusion scan of the filter re-traces
   bool HAIR = false;     // MESHMB, and a curve and a line tree behind the four mesh trees
+  bool HAIRMB = false;   // HAIR, and a motion-blur curve and a motion-blur line tree: eight trees per instanced scene
   bool SUBDIV = false;   // the subdivision family: an instanced scene is one tree whose leaves are the kernel's `Leaf`
   bool GRID = false;     // SUBDIV: that leaf is the eager accel's GridCellLeaf (a wave bound depends on it)
 };
@@ -95,6 +99,18 @@ struct MeshLeaves : LeafTraits
 #ifndef TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY
 #define TRACE_INST_HAIR_MIN_WAVES_MOELLER_ANY 4
 #endif
+#ifndef TRACE_INST_HAIRMB_MIN_WAVES_PLUECKER_CLOSEST
+#define TRACE_INST_HAIRMB_MIN_WAVES_PLUECKER_CLOSEST 2
+#endif
+#ifndef TRACE_INST_HAIRMB_MIN_WAVES_MOELLER_CLOSEST
+#define TRACE_INST_HAIRMB_MIN_WAVES_MOELLER_CLOSEST 2
+#endif
+#ifndef TRACE_INST_HAIRMB_MIN_WAVES_PLUECKER_ANY
+#define TRACE_INST_HAIRMB_MIN_WAVES_PLUECKER_ANY 3
+#endif
+#ifndef TRACE_INST_HAIRMB_MIN_WAVES_MOELLER_ANY
+#define TRACE_INST_HAIRMB_MIN_WAVES_MOELLER_ANY 3
+#endif
 
 // The wave bound of a form; `leafWaves` is Leaf::MIN_WAVES in the subdivision family.  Every exception, first match wins:
 constexpr int instance_min_waves(InstanceForm f, int leafWaves = TRACE_INST_MIN_WAVES)
@@ -104,6 +120,11 @@ constexpr int instance_min_waves(InstanceForm f, int leafWaves = TRACE_INST_MIN_
   // tests cells 8 lanes per ray and does not hold GridCellLeaf::intersect with its 40 cell words at all; the ray-pool kernel, which does,
   // takes 186 VGPRs: one wave less (docs/experiments.md, "Subdivision meshes below an instance").  TOPMB: the swept twin's bound
   if (f.SUBDIV) return f.GRID && !f.OCCLUDED ? leafWaves - 1 : leafWaves;
+  // HAIRMB: the motion-blur line and ribbon leaves beside the six of the HAIR form.  The highest wave count, from the HAIR twin's bound
+  // down to 2, at which the kernel compiles without scratch and without VGPR spills (docs/experiments.md, "Moving hair below an instance")
+  if (f.HAIRMB)
+    return f.OCCLUDED ? (f.PLUECKER ? TRACE_INST_HAIRMB_MIN_WAVES_PLUECKER_ANY : TRACE_INST_HAIRMB_MIN_WAVES_MOELLER_ANY)
+                      : (f.PLUECKER ? TRACE_INST_HAIRMB_MIN_WAVES_PLUECKER_CLOSEST : TRACE_INST_HAIRMB_MIN_WAVES_MOELLER_CLOSEST);
   // HAIR: the line and the ribbon leaf beside the four mesh leaves.  The highest wave count, from the MESHMB twin's bound down to 2, at
   // which the kernel compiles without scratch and without VGPR spills (docs/experiments.md, "Hair below an instance")
   if (f.HAIR)
@@ -146,11 +167,20 @@ constexpr InstanceForm instance_form(bool pluecker, bool occluded, bool vec, boo
   f.PLUECKER = pluecker; f.OCCLUDED = occluded; f.VEC = vec; f.QUADS = quads; f.XFMB = xfmb;
   return f;
 }
-// the MESHMB form, from which the NODEMB, TOPMB and HAIR forms start: always the general layout, quads and instance steps allowed
+// the MESHMB form, from which the NODEMB, TOPMB, HAIR and (through HAIR) HAIRMB forms start: always the general layout, quads and instance steps allowed
 constexpr InstanceForm instance_mesh_mb_form(bool pluecker, bool occluded, bool vec)
 {
   InstanceForm f = instance_form(pluecker, occluded, vec, true, true);
   f.MESHMB = true;
+  return f;
+}
+
+// the HAIR form: the general layout over swept boxes; no exclusion scan in the hair leaves, filters beside instanced hair are refused.
+// Here and not in trace_instance_hair.hip because the HAIRMB form (trace_instance_hair_mb.hip) starts from it.
+constexpr InstanceForm instance_hair_form(bool pluecker, bool occluded, bool vec)
+{
+  InstanceForm f = instance_mesh_mb_form(pluecker, occluded, vec);
+  f.HAIR = true;
   return f;
 }
 

@@ -10,7 +10,7 @@
 // traversal loop.
   static_assert(std::is_same<decltype(P), LaunchParams>::value, "trace_instance_body.hip.h: `LaunchParams P` must be the kernel's parameter");
   constexpr bool PLUECKER = FORM.PLUECKER, OCCLUDED = FORM.OCCLUDED, VEC = FORM.VEC, QUADS = FORM.QUADS, XFMB = FORM.XFMB, MESHMB = FORM.MESHMB;
-  constexpr bool NODEMB = FORM.NODEMB, TOPMB = FORM.TOPMB, EXCL = FORM.EXCL, HAIR = FORM.HAIR, SUBDIV = FORM.SUBDIV;
+  constexpr bool NODEMB = FORM.NODEMB, TOPMB = FORM.TOPMB, EXCL = FORM.EXCL, HAIR = FORM.HAIR, HAIRMB = FORM.HAIRMB, SUBDIV = FORM.SUBDIV;
   constexpr uint32_t FETCH = TRACE_INST_FETCH;
   constexpr uint32_t QFETCH = TRACE_INST_QUAD_FETCH;
   constexpr uint32_t TMFETCH = TRACE_INST_TRIMB_FETCH;
@@ -30,6 +30,10 @@
   // InstanceSceneRecord); their leaves are CurveLeaf::intersect / LineLeaf::intersect on the local ray.  The swept MESHMB form only, and
   // no exclusion scan: filters beside instanced hair are refused at commit and at the call.
   static_assert(!HAIR || (MESHMB && !NODEMB && !TOPMB && !EXCL), "the HAIR form is the MESHMB form over swept boxes, without the exclusion scan");
+  // HAIRMB (trace_instance_hair_mb.hip): the HAIR form with a motion-blur curve and a motion-blur line tree per scene, eight trees in all;
+  // their leaves are CurveMBLeaf::intersect / LineMBLeaf::intersect (trace_curve_mb.hip.h, trace_line_mb.hip.h) on the local ray, their
+  // nodes swept QNode8s like every node of the form
+  static_assert(!HAIRMB || HAIR, "the HAIRMB form is the HAIR form with two more trees");
   constexpr bool ROBUST = SUBDIV || PLUECKER; // Pluecker <-> robust traversal, Moeller <-> fast traversal, on both levels
   __shared__ uint2 ldsStack[TRACE_LDS_STACK + 1][TRACE_BLOCK]; // + one scratch row for the branch-free pushes
   Leaf::prepare(); // SUBDIV: once per kernel (the cBVH decode tables in LDS); nothing for the others
@@ -71,6 +75,7 @@
   enum : uint32_t { ST_TREE_MB = 2u << ST_TREE_SHIFT };
   static_assert(!(INST_TREE_TRI & 2u) && !(INST_TREE_QUAD & 2u) && (INST_TREE_TRIMB & 2u) && (INST_TREE_QUADMB & 2u), "bit 1 of a tree's code: a motion-blur tree");
   static_assert(!(INST_TREE_CURVE & 2u) && !(INST_TREE_LINE & 2u) && INST_TREE_CURVE < 8u && INST_TREE_LINE < 8u, "the hair trees' codes: three bits, bit 1 clear");
+  static_assert((INST_TREE_CURVEMB & 2u) != 0u && (INST_TREE_LINEMB & 2u) != 0u && INST_TREE_CURVEMB < 8u && INST_TREE_LINEMB < 8u, "the moving-hair trees' codes: three bits, bit 1 set");
   uint32_t st = 0u;
   r.hit = 0u;
 
@@ -318,11 +323,17 @@
         // motion-blur quads).  Walking them backwards, every tree that has one before it is stacked as a marker with its root in the
         // distance word; the lane starts in the first tree the scene has.
         // HAIR: six roots - the curve and the line root lead the record's second dwordx4 and are visited last, curves before lines
+        // HAIRMB: eight - all four words of that dwordx4, visited in Scene's slot order (curves, motion-blur curves, lines, motion-blur
+        // lines), which is not the word order (curve, line, motion-blur curve, motion-blur line)
         const uint4 sr = ((const uint4*)(insts + q3.y))[0];
-        constexpr int TREES = HAIR ? 6 : 4;
+        constexpr int TREES = HAIRMB ? 8 : HAIR ? 6 : 4;
         uint32_t roots[TREES] = {sr.x, sr.y, sr.z, sr.w};
         uint32_t codes[TREES] = {INST_TREE_TRI, INST_TREE_TRIMB, INST_TREE_QUAD, INST_TREE_QUADMB};
-        if (HAIR) {
+        if constexpr (HAIRMB) {
+          const uint4 sh = ((const uint4*)(insts + q3.y))[1];
+          roots[4] = sh.x; roots[5] = sh.z; roots[6] = sh.y; roots[7] = sh.w;
+          codes[4] = INST_TREE_CURVE; codes[5] = INST_TREE_CURVEMB; codes[6] = INST_TREE_LINE; codes[7] = INST_TREE_LINEMB;
+        } else if (HAIR) {
           const uint4 sh = ((const uint4*)(insts + q3.y))[1];
           roots[TREES - 2] = sh.x; roots[TREES - 1] = sh.y;
           codes[TREES - 2] = INST_TREE_CURVE; codes[TREES - 1] = INST_TREE_LINE;
@@ -382,16 +393,20 @@
           }
           if (!OCCLUDED && r.hit) hitInst = curInst; // instID: instance_intersector.cpp:57
           r.hit |= had;
-        } else if (HAIR && ((st & ST_TREE) == (INST_TREE_CURVE << ST_TREE_SHIFT) || (st & ST_TREE) == (INST_TREE_LINE << ST_TREE_SHIFT))) {
+        } else if (HAIR && ((st & ST_TREE) == (INST_TREE_CURVE << ST_TREE_SHIFT) || (st & ST_TREE) == (INST_TREE_LINE << ST_TREE_SHIFT) ||
+                            (HAIRMB && ((st & ST_TREE) == (INST_TREE_CURVEMB << ST_TREE_SHIFT) || (st & ST_TREE) == (INST_TREE_LINEMB << ST_TREE_SHIFT))))) {
           // the leaves of the top-level curve and line accels (trace_curve.hip.h, trace_line.hip.h) on the LOCAL ray: the ray's own space
           // depends on the length of the local direction, as in the reference, which hands the local ray to the instanced scene's
           // intersectors unchanged.  The leaf references are rebased so that `blobs` is ONE array of CurveRecords / LineRecords, which is how
           // the two leaves index it.  r.hit is cleared around the call: a hit the leaf commits - also one at a t equal to the hit of an
-          // earlier instance - is this instance's
+          // earlier instance - is this instance's.  HAIRMB: the same for the two motion-blur leaves, which read the ray's time through the
+          // ray's index (ray_time: the same value in world and local space) and index `blobs` as one array of CurveMBRecords / LineMBRecords
           WorkCounters wc;
           const uint32_t had = r.hit;
           r.hit = 0u;
           if ((st & ST_TREE) == (INST_TREE_CURVE << ST_TREE_SHIFT)) occl = CurveLeaf::intersect<OCCLUDED, false>(P, cur, r, wc, rayIdx);
+          else if (HAIRMB && (st & ST_TREE) == (INST_TREE_CURVEMB << ST_TREE_SHIFT)) occl = CurveMBLeaf::intersect<OCCLUDED, false>(P, cur, r, wc, rayIdx);
+          else if (HAIRMB && (st & ST_TREE) == (INST_TREE_LINEMB << ST_TREE_SHIFT)) occl = LineMBLeaf::intersect<OCCLUDED, false>(P, cur, r, wc, rayIdx);
           else occl = LineLeaf::intersect<OCCLUDED, false>(P, cur, r, wc, rayIdx);
           if (r.hit) hitInst = curInst; // instID: instance_intersector.cpp:57
           r.hit |= had;
@@ -583,7 +598,7 @@
           continue;
         }
         if (MESHMB) {
-          if (e.x - REF_INST_TREE(1u) < (HAIR ? 5u : 3u)) { // the tree before is done: on to the pending tree whose marker this is; before the distance cull
+          if (e.x - REF_INST_TREE(1u) < (HAIRMB ? 7u : HAIR ? 5u : 3u)) { // the tree before is done: on to the pending tree whose marker this is; before the distance cull
             st = (st & ~ST_TREE) | ((e.x & (HAIR ? 7u : 3u)) << ST_TREE_SHIFT);
             cur = e.y;
             break;

@@ -18,14 +18,7 @@
 namespace rtamd {
 namespace dev {
 
-// the general layout over swept boxes; no exclusion scan in the hair leaves: filters beside instanced hair are refused
-constexpr InstanceForm instance_hair_form(bool pluecker, bool occluded, bool vec)
-{
-  InstanceForm f = instance_mesh_mb_form(pluecker, occluded, vec);
-  f.HAIR = true;
-  return f;
-}
-
+// (its form, instance_hair_form, is in trace_instance.hip.h: the HAIRMB form starts from it)
 template <bool Pluecker, bool Occluded, bool Vec>
 __global__ __launch_bounds__(TRACE_BLOCK, instance_min_waves(instance_hair_form(Pluecker, Occluded, Vec))) void trace_instance_hair_kernel(LaunchParams P)
 {
@@ -44,7 +37,7 @@ inline hipError_t launch_instance_hair_vec(const LaunchParams& p, hipStream_t st
 
 hipError_t launch_trace_instance_hair(const LaunchParams& p, hipStream_t stream)
 {
-  if (p.counters || p.exclOffsets || !p.instHair) return hipErrorInvalidValue; // no instrumented twin, no EXCL form
+  if (p.counters || p.exclOffsets || p.instHair != 1u) return hipErrorInvalidValue; // no instrumented twin, no EXCL form
   switch (p.accel.kind) {
   case ACCEL_INSTMESHMB_PLUECKER: return p.occluded ? dev::launch_instance_hair_vec<true, true>(p, stream) : dev::launch_instance_hair_vec<true, false>(p, stream);
   case ACCEL_INSTMESHMB_MOELLER: return p.occluded ? dev::launch_instance_hair_vec<false, true>(p, stream) : dev::launch_instance_hair_vec<false, false>(p, stream);

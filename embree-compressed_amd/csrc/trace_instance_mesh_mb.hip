@@ -43,6 +43,7 @@ inline hipError_t launch_instance_mesh_mb_vec(const LaunchParams& p, hipStream_t
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream)
 {
   if (p.counters) return hipErrorInvalidValue; // no instrumented twin (rt_trace.cpp refuses counted batches on scenes with instances)
+  if (p.instHair == 2u) return p.exclOffsets ? hipErrorInvalidValue : launch_trace_instance_hair_mb(p, stream); // moving line or curve trees below the instances: the HAIRMB form, no EXCL twin either
   if (p.instHair) return p.exclOffsets ? hipErrorInvalidValue : launch_trace_instance_hair(p, stream); // line and curve trees below the instances: the HAIR form, which has no EXCL twin
   if (p.exclOffsets) return launch_trace_instance_filter(p, stream); // a re-trace of the host filter loop: the EXCL form (trace_instance_filter.hip)
   switch (p.accel.kind) {

@@ -7,7 +7,10 @@ trace_curve.hip / trace_line.hip).  1 M random rays over the bounds of all insta
 events around every step (the batch is restored from a pristine copy before each step, untimed), closest hit and any hit, both variants
 (robust / fast traversal), instanced and flattened alternating.  Prints the accel bytes of both and instanced / flattened.
 The flattened twin runs on any build (RTAMD_LIB=... selects another build of the library); the instanced one needs inst_hair=1.
-usage: instance_hair_rates.py [steps] [repeats] [N ...] [flattened]      (default N: 64; "flattened": only the flattened twin)"""
+"moving": the moving variant (inst_hair=1,inst_hair_mb=1, the HAIRMB form, csrc/trace_instance_hair_mb.hip) - the tuft of curves with TWO
+time steps (step 1: every point swayed sideways in proportion to its height), then the tuft of line segments with two time steps, each
+alone in the hair scene, rays at random times in [0, 1); the flattened twin is traced by trace_curve_mb.hip / trace_line_mb.hip.
+usage: instance_hair_rates.py [steps] [repeats] [N ...] [flattened] [moving]      (default N: 64; "flattened": only the flattened twin)"""
 import importlib
 import os
 import sys
@@ -18,8 +21,9 @@ import torch  # noqa: E402
 
 rtc = importlib.import_module('embree-compressed_amd').rtc
 raygen = importlib.import_module('embree-compressed_amd.raygen')
-args = [a for a in sys.argv[1:] if a != 'flattened']
-only_flat = len(args) < len(sys.argv) - 1
+args = [a for a in sys.argv[1:] if a not in ('flattened', 'moving')]
+only_flat = 'flattened' in sys.argv[1:]
+moving = 'moving' in sys.argv[1:]
 steps = int(args[0]) if len(args) > 0 else 20
 repeats = int(args[1]) if len(args) > 1 else 5
 counts = [int(a) for a in args[2:]] or [64]
@@ -77,12 +81,33 @@ def moved(v4, m, s):
     return out
 
 
-def measure(kind, variant, xfms, pristine, occluded):
-    dev = rtc.Device('gpu=0' + (',inst_hair=1' if kind == 'instanced' else ''))
+def swayed(v4):
+    """the second time step: every point moved sideways in proportion to its height (the roots stay), radii kept"""
+    out = v4.copy()
+    out[:, 0] += 0.25 * v4[:, 1] / 4.0
+    out[:, 2] += 0.15 * v4[:, 1] / 4.0
+    return out
+
+
+def measure(kind, variant, xfms, pristine, occluded, hair_mb=None):
+    """hair_mb: None (the static tufts), 'curves' or 'lines' (that tuft alone, with two time steps)"""
+    dev = rtc.Device('gpu=0' + (',inst_hair=1' if kind == 'instanced' else '') + (',inst_hair_mb=1' if kind == 'instanced' and hair_mb else ''))
     flags = rtc.RTC_SCENE_FLAG_ROBUST if variant == 'robust' else 0
     sc = rtc.Scene(dev, flags)
     inner = None
-    if kind == 'instanced':
+    if hair_mb:
+        v, idx = (CV, CI) if hair_mb == 'curves' else (LV, LI)
+        add = (lambda s, st, ix: s.add_curves_mb(st, ix, basis='bezier', tessellation_rate=4)) if hair_mb == 'curves' else (lambda s, st, ix: s.add_lines_mb(st, ix))
+        if kind == 'instanced':
+            inner = rtc.Scene(dev, flags)
+            add(inner, [v, swayed(v)], idx)
+            inner.commit()
+            for m, _ in xfms:
+                sc.add_instance(inner, m)
+        else:
+            index = np.concatenate([idx + np.uint32(k * len(v)) for k in range(len(xfms))])
+            add(sc, [np.concatenate([moved(w, m, s) for m, s in xfms]) for w in (v, swayed(v))], index)
+    elif kind == 'instanced':
         inner = rtc.Scene(dev, flags)
         inner.add_curves(CV, CI, basis='bezier', tessellation_rate=4)
         inner.add_lines(LV, LI)
@@ -119,7 +144,7 @@ def measure(kind, variant, xfms, pristine, occluded):
         meds.append(float(np.median(ms)))
     stt = sc.stats()
     med = float(np.median(meds))
-    print(f'{len(xfms):5d} {kind:9s} {variant:6s} {"any hit" if occluded else "closest"}: {stt["totalBytes"]} accel bytes, depth {stt["maxDepth"]}, {hits} hits; '
+    print(f'{len(xfms):5d} {kind:9s} {"moving " + hair_mb + " " if hair_mb else ""}{variant:6s} {"any hit" if occluded else "closest"}: {stt["totalBytes"]} accel bytes, depth {stt["maxDepth"]}, {hits} hits; '
           f'kernel {med:.4f} ms per 1 M-ray batch of {rec}-byte records (median of {repeats} repeats of {steps} steps; repeats {min(meds):.4f}..{max(meds):.4f}) = {n / med / 1e3:.0f} Mrays/s', flush=True)
     sc.release()
     if inner:
@@ -133,11 +158,14 @@ for count in counts:
     xfms = placements(count)
     pts = np.concatenate([np.concatenate([moved(CV, m, s)[:, :3], moved(LV, m, s)[:, :3]]) for m, s in xfms])
     rays = raygen.make_random_rays(n, pts.min(0).astype(np.float32), pts.max(0).astype(np.float32), seed=0)
+    if moving:
+        rays.view(np.float32).reshape(n, 20)[:, 7] = np.random.default_rng(2).random(n, dtype=np.float32)  # ray.time
     pristine = torch.from_numpy(rays.reshape(-1).view(np.uint8).reshape(n, 80).copy()).cuda()
-    for variant in ('robust', 'fast'):
-        for occluded in (False, True):
-            b = measure('flattened', variant, xfms, pristine, occluded)
-            if only_flat:
-                continue
-            a = measure('instanced', variant, xfms, pristine, occluded)
-            print(f'{count:5d} {variant:6s} {"any hit" if occluded else "closest"}: instanced / flattened = {a / b:.2f}', flush=True)
+    for hair_mb in (('curves', 'lines') if moving else (None,)):
+        for variant in ('robust', 'fast'):
+            for occluded in (False, True):
+                b = measure('flattened', variant, xfms, pristine, occluded, hair_mb)
+                if only_flat:
+                    continue
+                a = measure('instanced', variant, xfms, pristine, occluded, hair_mb)
+                print(f'{count:5d} {"moving " + hair_mb + " " if hair_mb else ""}{variant:6s} {"any hit" if occluded else "closest"}: instanced / flattened = {a / b:.2f}', flush=True)

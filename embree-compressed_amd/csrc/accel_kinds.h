@@ -24,6 +24,7 @@ hipError_t launch_trace_cbvh_full(const LaunchParams& p, hipStream_t stream); //
 hipError_t launch_trace_line(const LaunchParams& p, hipStream_t stream);      // trace_line.hip (flat linear curves; no service kernel)
 hipError_t launch_trace_line_mb(const LaunchParams& p, hipStream_t stream);   // trace_line_mb.hip (flat linear curves with time steps; lane kernel only)
 hipError_t launch_trace_curve(const LaunchParams& p, hipStream_t stream);     // trace_curve.hip (flat Bezier / B-spline curves; lane kernel only, no service kernel)
+hipError_t launch_trace_round_curve(const LaunchParams& p, hipStream_t stream); // trace_round_curve.hip (round Bezier / B-spline curves: launch_trace_curve diverts to it when LaunchParams::roundCurves is set)
 hipError_t launch_trace_curve_mb(const LaunchParams& p, hipStream_t stream);  // trace_curve_mb.hip (flat Bezier / B-spline curves with time steps; lane kernel only)
 hipError_t launch_trace_instance(const LaunchParams& p, hipStream_t stream);  // trace_instance.hip
 hipError_t launch_trace_instance_mesh_mb(const LaunchParams& p, hipStream_t stream); // trace_instance_mesh_mb.hip
@@ -119,7 +120,8 @@ inline constexpr KindRow ACCEL_KINDS[] = {
   {ACCEL_LINEMB_FAST,                     launch_trace_line_mb,                    nullptr,                  0, NODES_Q8,          INST_NONE,   0, 0, 0, 0, 0, OCT_NEVER,     16, 0},
   {ACCEL_LINEMB_LINEAR_ROBUST,            launch_trace_line_mb,                    nullptr,                  1, NODES_MB8,         INST_NONE,   0, 0, 0, 0, 0, OCT_NEVER,     16, 0},
   {ACCEL_LINEMB_LINEAR_FAST,              launch_trace_line_mb,                    nullptr,                  0, NODES_MB8,         INST_NONE,   0, 0, 0, 0, 0, OCT_NEVER,     16, 0},
-  // the ribbon leaf exists in the lane kernel only (lane and octet form)
+  // the ribbon leaf exists in the lane kernel only (lane and octet form); so does the tube leaf of the round curves, which shares these two
+  // kinds (Accel::roundCurves, octet form only)
   {ACCEL_CURVE_ROBUST,                    launch_trace_curve,                      nullptr,                  1, NODES_Q8,          INST_NONE,   0, 0, 0, 0, 0, OCT_NEVER,     16, 0},
   {ACCEL_CURVE_FAST,                      launch_trace_curve,                      nullptr,                  0, NODES_Q8,          INST_NONE,   0, 0, 0, 0, 0, OCT_NEVER,     16, 0},
   {ACCEL_CURVEMB_ROBUST,                  launch_trace_curve_mb,                   nullptr,                  1, NODES_Q8,          INST_NONE,   0, 0, 0, 0, 0, OCT_NEVER,     16, 0},

@@ -73,6 +73,10 @@ void Device::parse(const std::string& cfg)
       if (val != "0" && val != "1") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "inst_hair_mb=: unknown value '" + val + "' (0 or 1)");
       inst_hair_mb = val == "1";
     }
+    else if (key == "round_curves") {
+      if (val != "0" && val != "1") RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "round_curves=: unknown value '" + val + "' (0 or 1)");
+      round_curves = val == "1";
+    }
     else if (key == "verbose") verbose = atoi(val.c_str());
     else if (key == "gpu" || key == "device") { gpu = (val == "none") ? -1 : atoi(val.c_str()); gpuList.clear(); }
     else if (key == "gpus") {

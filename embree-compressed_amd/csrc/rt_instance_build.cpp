@@ -421,6 +421,10 @@ MeshInstances classify_mesh_instances(const Scene* s)
     Scene* o = g->instScene;
     if (!o) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instance without an instanced scene");
     if (o->modified) RT_THROW(RTC_ERROR_INVALID_OPERATION, "instanced scene got not committed");
+    // round_curves=1: the tube leaf runs at the top level only, whatever the inst_* keys take (asked before a subdivision scene is passed on)
+    for (const Geometry* og : o->geometries)
+      if (og && og->enabled && og->isRoundCurve())
+        RT_THROW(RTC_ERROR_INVALID_OPERATION, at_instance("round Bezier and B-spline curves inside an instanced scene are not supported", gid));
     if (subdivOk && is_subdivision_scene(o)) continue; // build_instance_subdiv_accel places it
     // without inst_mb_bounds=linear the instanced scenes' trees are copied behind the top-level tree as QNode8s: time-dependent nodes
     // have no place there

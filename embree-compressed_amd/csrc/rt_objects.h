@@ -37,6 +37,7 @@ struct Device : RefCounted
   bool inst_filters = false; // "inst_filters=1": filter functions run on hits below mesh instances (geometry filters inside instanced mesh scenes, RTCIntersectContext::filter on scenes with mesh instances); 0, the default: both are refused as before
   bool inst_hair = false; // "inst_hair=1": an instanced scene may hold static line segments and flat curves, alone or beside its triangle and quad meshes (the HAIR form of the two-level kernel, trace_instance_hair.hip); 0, the default: refused as before
   bool inst_hair_mb = false; // "inst_hair_mb=1", beside inst_hair=1: the line segments and flat curves of an instanced scene may have time steps (the HAIRMB form of the two-level kernel, trace_instance_hair_mb.hip); 0, the default: refused as before
+  bool round_curves = false; // "round_curves=1": RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE / _ROUND_BSPLINE_CURVE are taken (static, top level only) and traced by the tube leaf (trace_round_curve.hip) from Scene::roundCurveAccel; 0, the default: refused at rtcNewGeometry as before
   std::string line_accel = "default"; // flat linear curves: default / bvh8.line4i / bvh4.line4i, all the one BVH8 over LineRecords (build_line_accel raises for any other at commit)
   std::string line_accel_mb = "default"; // flat linear curves with time steps: default / bvh8.line4imb / bvh4.line4imb, all the one BVH8 over LineMBRecords (build_linemb_accel raises for any other at commit)
   bool lineAccelMBNamed = false; // "line_accel_mb=" given (a host-only device builds the motion-blur line accel only then, lines_mb_enabled())
@@ -235,6 +236,10 @@ struct Device : RefCounted
   // Flat Bezier and B-spline curves, the same rule with the key hair_accel=: a host-only device without it refuses the two types at
   // rtcNewGeometry ("RTC_GEOMETRY_TYPE_*_CURVE not supported"), as before the curve accel existed.
   bool curves_enabled() const { return gpu >= 0 || hairAccelNamed; }
+  // Round Bezier and B-spline curves (round_curves=1): every device that has the key, host-only ones included.  With them and the flat
+  // types all five curve types are taken, which is what RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED speaks for.
+  bool round_curves_enabled() const { return round_curves; }
+  bool all_curve_types_enabled() const { return round_curves && curves_enabled(); }
   // Flat cubic curves with time steps, the rule of lines_mb_enabled() with the key hair_accel_mb=: a host-only device without it raises
   // "motion blur of flat Bezier and B-spline curves is not supported" at commit, as before the motion-blur curve accel existed.
   bool curves_mb_enabled() const { return gpu >= 0 || hairAccelMBNamed; }
@@ -380,6 +385,10 @@ struct Geometry : RefCounted
   // flat cubic curve accessors (reference: NativeCurves, kernels/common/scene_bezier_curves.h): curve i uses the vertices index[i] ..
   // index[i] + 3 = (x, y, z, radius), control points of the geometry's own basis
   bool isFlatCubicCurve() const { return type == RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE || type == RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE; }
+  // round cubic curves (round_curves=1): the buffers and the native control points of the flat cubic types, swept tubes instead of ribbons
+  bool isRoundCurve() const { return type == RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE || type == RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE; }
+  bool isCubicCurve() const { return isFlatCubicCurve() || isRoundCurve(); }
+  bool isBSplineCurve() const { return type == RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE || type == RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE; }
   size_t numCurves() const { return numTriangles(); } // index buffer records (UINT)
   bool validCurve(size_t i, unsigned slot = 0) const; // NativeCurves::valid (scene_bezier_curves.h:193-218) at one time step: against the vertex buffer of `slot`
   unsigned curveRate() const;                         // NativeCurves::setTessellationRate: clamp((int)rate, 1, 16)
@@ -405,6 +414,7 @@ struct Accel
   uint32_t maxDepth = 0;
   uint32_t blobStride = 0;
   uint32_t instHair = 0;   // kinds ACCEL_INSTMESHMB_*: 1 = an instanced scene has a curve or a line tree (inst_hair=1; accel.h InstanceSceneRecord), 2 = one has a motion-blur curve or line tree as well (inst_hair_mb=1) -> LaunchParams::instHair
+  uint32_t roundCurves = 0; // kinds ACCEL_CURVE_*: 1 = the records are round curves (Scene::roundCurveAccel): launch_trace_curve diverts to launch_trace_round_curve -> LaunchParams::roundCurves
   uint32_t cbvhLevels = 0; // ACCEL_INSTSUBDIV_CBVH_LEAF / ACCEL_INSTSUBDIV_TOP_LINEAR_CBVH_LEAF: the compression level C of the instanced scenes' blobs (0: the scene's own level applies)
   size_t leafCount = 0;
   // device copies, one set per shard of the device (replicated accel)
@@ -473,9 +483,10 @@ struct Scene : RefCounted
   Accel lineAccel;   // flat linear curves (LineRecord[] in `blobs`); traced after the subdivision patches, before the instances (scene.cpp:650-663)
   Accel lineMBAccel; // flat linear curves with several time steps (LineMBRecord[] in `blobs`); traced right after the static lines (scene.cpp: createLineAccel, createLineMBAccel)
   Accel instAccel;   // instances (InstanceRecord[] in `blobs`, the instanced scenes' triangle and quad trees behind the top-level tree); traced last (scene.cpp:661-665)
+  Accel roundCurveAccel; // round Bezier and B-spline curves (round_curves=1; CurveRecord[] with N = 0 in `blobs`, kinds ACCEL_CURVE_* with Accel::roundCurves); traced last
   Accel instSubdivAccel; // instances of scenes that hold subdivision meshes only (InstanceRecord[] and the instanced scenes' leaf blobs in `blobs`, their BVH8s behind the top-level tree); traced after the mesh instances
   // the accel slots in trace order (one row each in SCENE_SLOTS below); they index whatever a path keeps per accel
-  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, CURVE = 5, CURVEMB = 6, LINE = 7, LINEMB = 8, INST = 9, INSTSUBDIV = 10, NUM_ACCELS = 11 };
+  enum { TRI = 0, TRIMB = 1, QUAD = 2, QUADMB = 3, SUBDIV = 4, CURVE = 5, CURVEMB = 6, LINE = 7, LINEMB = 8, INST = 9, INSTSUBDIV = 10, ROUND = 11, NUM_ACCELS = 12 };
   std::array<Accel*, NUM_ACCELS> accels();
   bool hasInstances() const { return instAccel.kind != ACCEL_NONE || instSubdivAccel.kind != ACCEL_NONE; }
   // records the layout of instAccel placed in `blobs` behind the InstanceRecords, as build_instance_accel counted them (host only: the
@@ -501,7 +512,7 @@ V3 xfm_point(const float* m, V3 q);
 // the builders of a scene's accels (rt_prim_build.cpp, subdiv_build.cpp, rt_instance_build.cpp); Scene::commit runs them in slot order
 void build_triangle_accel(Scene* s), build_trimb_accel(Scene* s), build_quad_accel(Scene* s), build_quadmb_accel(Scene* s), build_subdiv_accel(Scene* s),
     build_curve_accel(Scene* s), build_curvemb_accel(Scene* s), build_line_accel(Scene* s), build_linemb_accel(Scene* s), build_instance_accel(Scene* s),
-    build_instance_subdiv_accel(Scene* s);
+    build_instance_subdiv_accel(Scene* s), build_round_curve_accel(Scene* s);
 
 // One row per accel slot of a scene, in trace order - which is also Scene::commit's build order: where a scene has several faults, the
 // order decides which refusal is reported, and build_instance_subdiv_accel relies on build_instance_accel having refused instances without
@@ -544,6 +555,9 @@ inline constexpr SlotRow SCENE_SLOTS[] = {
   {Scene::INST, &Scene::instAccel, build_instance_accel, nullptr, nullptr, 0, {RTC_GEOMETRY_TYPE_INSTANCE, RTC_GEOMETRY_TYPE_INSTANCE}, STEPS_ANY, true, true, 9},
   // (no filter runs below a subdivision instance: the list stays empty)
   {Scene::INSTSUBDIV, &Scene::instSubdivAccel, build_instance_subdiv_accel, nullptr, nullptr, 0, {RTC_GEOMETRY_TYPE_INSTANCE, RTC_GEOMETRY_TYPE_INSTANCE}, STEPS_ANY, false, false, 10},
+  // the tube leaf offers a front and a back candidate per curve and ray (entry and exit), both with the curve's (geomID, primID): t tells them apart.
+  // Last, so that no older slot number, export rank, exclusion list or wave-log slice moves; a round curve with time steps fits no slot
+  {Scene::ROUND, &Scene::roundCurveAccel, build_round_curve_accel, "round curve", "curves", sizeof(CurveRecord), {RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE, RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE}, STEPS_ONE, true, false, 11},
 };
 static_assert(sizeof(SCENE_SLOTS) / sizeof(SCENE_SLOTS[0]) == Scene::NUM_ACCELS, "every accel slot needs a row in SCENE_SLOTS");
 constexpr bool scene_slots_in_order(int i = 0) { return i == Scene::NUM_ACCELS || (SCENE_SLOTS[i].slot == i && scene_slots_in_order(i + 1)); }

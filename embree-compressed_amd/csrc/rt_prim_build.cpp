@@ -1,4 +1,4 @@
-// The eight primitive accels of a scene - triangles, quads, flat cubic curves and line segments, static and with time steps - built at
+// The nine primitive accels of a scene - triangles, quads, flat cubic curves and line segments, static and with time steps, and the static round cubic curves - built at
 // commit from two frames: build_static_bvh8 and build_mb_bvh8.  A frame gathers the valid primitives of the scene's enabled geometries
 // of one type, builds one BVH8 (block 4, min leaf 4, max leaf 28: bvh_builder_sah.cpp:651-658) over them and stores the leaves' records;
 // where a primitive's box and record come from is the business of a Source.  What a builder keeps is the accel-name check and the kind.
@@ -146,6 +146,49 @@ static Box3 curve_tessellated_bounds(const float cp[16], unsigned N)
   return e;
 }
 
+// BezierBasis::derivative (bezier_curve.h:39-49) in float32, the products in the reference's order
+static void bezier_basis_derivative(float u, float D[4])
+{
+  const float t1 = u, t0 = 1.0f - t1;
+  D[0] = 3.0f * -(t0 * t0);
+  D[1] = 3.0f * fmaf(-2.0f, t0 * t1, t0 * t0);
+  D[2] = 3.0f * fmaf(2.0f, t0 * t1, -(t1 * t1));
+  D[3] = 3.0f * (t1 * t1);
+}
+
+// BezierCurve3fa::accurateBounds() (bezier_curve.h:273-295) in float32, the box of a round curve: at the parameters float(j) / 7.0f,
+// j = 0 .. 7, the point p = eval0(j, 7) and the derivative dp = derivative0(j, 7) - the nested madd over the basis values - and the two
+// neighbours p - dp / 18 (not at j = 0) and p + dp / 18 (not at j = 7): a product and a difference, not fused, with scale = 1 / (3 * 6).
+// Minimum and maximum over all of them in x, y, z and w, the box enlarged on every side by max(|w_min|, |w_max|).
+// Containment.  Between two parameters the curve is a Bezier segment whose inner control points are p_j + dp_j / 21 and p_j+1 - dp_j+1 / 21;
+// they lie on the segments from p to p +- dp / 18, so the core box holds the control polygon of every seventh and with it the axis and -
+// in w - the radius, which the enlargement covers: a surface point lies within r(u) <= max |w| of the axis.  The tube leaf's own float32
+// roundings are a few ulp of the coordinates, inside the quantizer's one-step padding like those of every other leaf.
+static Box3 curve_accurate_bounds(const float cp[16])
+{
+  const int N = 7;
+  const float scale = 1.0f / (3.0f * (float)(N - 1));
+  float lo[4], hi[4];
+  for (int c = 0; c < 4; c++) { lo[c] = INFINITY; hi[c] = -INFINITY; }
+  for (int j = 0; j <= N; j++) {
+    float B[4], D[4];
+    bezier_basis_eval((float)j / (float)N, B);
+    bezier_basis_derivative((float)j / (float)N, D);
+    for (int c = 0; c < 4; c++) {
+      const float p = fmaf(B[0], cp[c], fmaf(B[1], cp[4 + c], fmaf(B[2], cp[8 + c], B[3] * cp[12 + c])));
+      const float dp = fmaf(D[0], cp[c], fmaf(D[1], cp[4 + c], fmaf(D[2], cp[8 + c], D[3] * cp[12 + c])));
+      const float pm = p - scale * (j != 0 ? dp : 0.0f), pp = p + scale * (j != N ? dp : 0.0f);
+      lo[c] = std::min(lo[c], std::min(p, std::min(pm, pp)));
+      hi[c] = std::max(hi[c], std::max(p, std::max(pm, pp)));
+    }
+  }
+  const float r = std::max(fabsf(lo[3]), fabsf(hi[3]));
+  Box3 e;
+  e.extend(V3(lo[0] - r, lo[1] - r, lo[2] - r));
+  e.extend(V3(hi[0] + r, hi[1] + r, hi[2] + r));
+  return e;
+}
+
 // ---- the static frame -------------------------------------------------------------------------------------------------------------------
 // The frame of the static builders (build_mesh_bvh8 of the triangle and quad builders once, now of the lines and curves too): one BVH8
 // over the valid primitives of the scene's enabled geometries the Source takes; a primitive's record is filled from the Source and gets
@@ -268,6 +311,22 @@ struct CurveSource
     g->nativeCurve(i, &r.v0x);
     r.N = g->curveRate();
   }
+};
+
+// The Source of the round Bezier and B-spline curves (round_curves=1): the record of the flat curves - the native control points - with
+// N = 0 (a tube has no tessellation rate), the box the reference's accurateBounds().  One time step only: Scene::commit has refused the rest.
+struct RoundCurveSource
+{
+  bool takes(const Scene*, const Geometry* g) const { return g->isRoundCurve() && g->timeSteps == 1; }
+  size_t count(const Geometry* g) const { return g->numCurves(); }
+  bool valid(const Geometry* g, size_t i) const { return g->validCurve(i); }
+  Box3 box(const Geometry* g, size_t i) const
+  {
+    float cp[16];
+    g->nativeCurve(i, cp);
+    return curve_accurate_bounds(cp);
+  }
+  void fill(CurveRecord& r, const Geometry* g, size_t i) const { g->nativeCurve(i, &r.v0x); }
 };
 
 // ---- the motion-blur frame ----------------------------------------------------------------------------------------------------------------
@@ -656,6 +715,22 @@ void build_linemb_accel(Scene* s)
   const bool robust = s->isRobust();
   build_mb_bvh8<LineMBRecord>(s, A, LineMBSource(), "too many motion blur line segments for the 26-bit leaf reference",
                               robust ? ACCEL_LINEMB_ROBUST : ACCEL_LINEMB_FAST, robust ? ACCEL_LINEMB_LINEAR_ROBUST : ACCEL_LINEMB_LINEAR_FAST, robust);
+}
+
+// Round Bezier and B-spline curves (round_curves=1).  The reference keeps them in the hair accel beside the flat ones (createHairAccel);
+// here they get a BVH8 of their own, under the static frame and with the hair accel's names (oriented-box nodes are not built), over the
+// boxes of accurateBounds().  The accel has the flat curves' kinds - the kind tells the traversal only - and says with Accel::roundCurves
+// that its CurveRecords are tubes: launch_trace_curve hands such a launch to launch_trace_round_curve (trace_round_curve.hip).
+void build_round_curve_accel(Scene* s)
+{
+  Accel& A = s->roundCurveAccel;
+  A.clear();
+  if (!s->device->round_curves_enabled()) return; // (no round curve geometry can exist on such a device)
+  const std::string& name = s->device->hair_accel;
+  if (!one_of(name, {"default", "bvh4.bezier1v", "bvh4.bezier1i", "bvh4obb.bezier1v", "bvh4obb.bezier1i", "bvh8obb.bezier1v", "bvh8obb.bezier1i"}))
+    RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "unknown hair acceleration structure " + name);
+  build_static_bvh8<CurveRecord>(s, A, RoundCurveSource(), "too many round curves for the 26-bit leaf reference", s->isRobust() ? ACCEL_CURVE_ROBUST : ACCEL_CURVE_FAST, s->isRobust());
+  A.roundCurves = A.kind != ACCEL_NONE ? 1u : 0u;
 }
 
 } // namespace rtamd

@@ -12,7 +12,7 @@ namespace rtamd {
 // ---- Geometry -------------------------------------------------------------------------------------------
 Geometry::Geometry(Device* d, RTCGeometryType t) : device(d), type(t)
 {
-  if (isFlatCubicCurve()) tessellationRate = 4.0f; // NativeCurves (scene_bezier_curves.cpp:28)
+  if (isCubicCurve()) tessellationRate = 4.0f; // NativeCurves (scene_bezier_curves.cpp:28); kept and without effect on the round types
   device->retain();
 }
 
@@ -49,7 +49,7 @@ void Geometry::bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size
 {
   // argument checks follow rtcSetGeometryBuffer (rtcore.cpp:1236-1290) and TriangleMesh::setBuffer
   // (scene_triangle_mesh.cpp): 4-byte aligned offset/stride, matching formats per slot type.
-  const bool lineFlags = (type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE || isFlatCubicCurve()) && t == RTC_BUFFER_TYPE_FLAGS; // bytes (scene_line_segments.cpp:63, scene_bezier_curves.cpp:63)
+  const bool lineFlags = (type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE || isCubicCurve()) && t == RTC_BUFFER_TYPE_FLAGS; // bytes (scene_line_segments.cpp:63, scene_bezier_curves.cpp:63)
   if (!lineFlags && ((off & 3) || (stride & 3))) RT_THROW(RTC_ERROR_INVALID_OPERATION, "buffer offset and stride must be 4-byte aligned");
   if (b && off + (count ? (count - 1) * stride + format_bytes(f) : 0) > b->bytes && !b->shared)
     RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "buffer range out of bounds");
@@ -71,6 +71,8 @@ void Geometry::bind(RTCBufferType t, unsigned slot, RTCFormat f, Buffer* b, size
     break;
   case RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE:
   case RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE: // NativeCurves::setBuffer (scene_bezier_curves.cpp:60-110): the same formats and messages
+  case RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE:
+  case RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE: // (the reference's round types are NativeCurves too)
   case RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE: // LineSegments::setBuffer (scene_line_segments.cpp)
     if (t == RTC_BUFFER_TYPE_VERTEX) {
       if (f != RTC_FORMAT_FLOAT4) RT_THROW(RTC_ERROR_INVALID_OPERATION, "invalid vertex buffer format");
@@ -182,7 +184,7 @@ void Geometry::nativeCurve(size_t i, float out[16], unsigned slot) const
   const BufferView* vv = view(RTC_BUFFER_TYPE_VERTEX, slot);
   const size_t i0 = segment(i);
   const float *a = (const float*)vv->at(i0), *b = (const float*)vv->at(i0 + 1), *c = (const float*)vv->at(i0 + 2), *d = (const float*)vv->at(i0 + 3);
-  if (type != RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE) {
+  if (!isBSplineCurve()) {
     memcpy(out, a, 16); memcpy(out + 4, b, 16); memcpy(out + 8, c, 16); memcpy(out + 12, d, 16);
     return;
   }
@@ -246,6 +248,7 @@ void Accel::clear()
   blobStride = 0;
   cbvhLevels = 0;
   instHair = 0;
+  roundCurves = 0;
   leafCount = 0;
 }
 
@@ -391,6 +394,8 @@ void Scene::commit()
   service_quiesce(device); // the upload allocates device memory (see Scene::~Scene)
   for (Geometry* geo : geometries) {
     if (!geo || !geo->enabled) continue;
+    if (geo->isRoundCurve() && geo->timeSteps != 1) // (the slot of the round curves takes one time step only)
+      RT_THROW(RTC_ERROR_INVALID_OPERATION, "motion blur of round Bezier and B-spline curves is not supported");
     if (slot_of(geo) < 0) // no slot takes the type (SCENE_SLOTS).  scene.cpp:25-30: geometry types compiled out raise INVALID_OPERATION
       RT_THROW(RTC_ERROR_INVALID_OPERATION, "geometry type not supported by the MI355X traversal path");
   }
@@ -401,7 +406,7 @@ void Scene::commit()
     if (geo->type == RTC_GEOMETRY_TYPE_TRIANGLE || geo->type == RTC_GEOMETRY_TYPE_QUAD) {
       triIntersectFilter |= geo->intersectFilter != nullptr;
       triOccludedFilter |= geo->occludedFilter != nullptr;
-    } else if (geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE || geo->isFlatCubicCurve()) {
+    } else if (geo->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE || geo->isCubicCurve()) {
       lineIntersectFilter |= geo->intersectFilter != nullptr;
       lineOccludedFilter |= geo->occludedFilter != nullptr;
     } else if (geo->type == RTC_GEOMETRY_TYPE_SUBDIVISION)

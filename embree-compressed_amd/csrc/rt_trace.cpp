@@ -85,6 +85,7 @@ void launch_on(Scene* s, const Accel& A, size_t si, const Batch& b, const Launch
   }
   p.counters = x.counters;
   p.instHair = A.instHair; // line and curve trees below the instances: 1 the HAIR form of the two-level kernel, 2 (moving ones among them) the HAIRMB form
+  p.roundCurves = A.roundCurves; // the kinds 42 / 43 on Scene::roundCurveAccel: the tube leaf
   p.cbvhLevels = A.cbvhLevels ? A.cbvhLevels : s->compressionLevel; // (instanced cBVH blobs, kinds 25 / 35, carry the level of the scenes they come from)
   // cBVH blob walk: quad form (four lanes per ray, two-stage visits) or one ray per lane.  Coherent batches (RTC_INTERSECT_CONTEXT_FLAG_COHERENT,
   // e.g. the primary rays of viewer_stream_device.cpp:305) keep most lanes at blobs at once; since the two-stage visits the quad form is the faster

@@ -87,7 +87,7 @@ API ssize_t rtcGetDeviceProperty(RTCDevice h, enum RTCDeviceProperty prop)
   case RTC_DEVICE_PROPERTY_TRIANGLE_GEOMETRY_SUPPORTED: return 1;
   case RTC_DEVICE_PROPERTY_QUAD_GEOMETRY_SUPPORTED: return D(h)->quads_enabled() ? 1 : 0;
   case RTC_DEVICE_PROPERTY_SUBDIVISION_GEOMETRY_SUPPORTED: return 1;
-  case RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED: return 0; // speaks for all five curve types: the flat ones are taken, the round ones are not
+  case RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED: return D(h)->all_curve_types_enabled() ? 1 : 0; // speaks for all five curve types: 1 only where the round ones (round_curves=1) and the flat ones are both taken
   case RTC_DEVICE_PROPERTY_USER_GEOMETRY_SUPPORTED: return 0;
   case RTC_DEVICE_PROPERTY_TASKING_SYSTEM: return 0; // "internal"
   case RTC_DEVICE_PROPERTY_JOIN_COMMIT_SUPPORTED: return 1;
@@ -166,7 +166,9 @@ API RTCGeometry rtcNewGeometry(RTCDevice h, enum RTCGeometryType type)
     if (!D(h)->curves_enabled()) unsupported("RTC_GEOMETRY_TYPE_*_CURVE");
     return (RTCGeometry) new Geometry(D(h), type);
   case RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE:
-  case RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE: unsupported("RTC_GEOMETRY_TYPE_*_CURVE");
+  case RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE: // tubes (trace_round_curve.hip): only a device whose config says round_curves=1 takes them
+    if (!D(h)->round_curves_enabled()) unsupported("RTC_GEOMETRY_TYPE_*_CURVE");
+    return (RTCGeometry) new Geometry(D(h), type);
   default: RT_THROW(RTC_ERROR_UNKNOWN, "invalid geometry type");
   }
   CATCH_END(D(h))
@@ -437,7 +439,7 @@ API void rtcInterpolate(const struct RTCInterpolateArguments* args)
   if (g->type == RTC_GEOMETRY_TYPE_TRIANGLE) interpolate_triangles(g, args);
   else if (g->type == RTC_GEOMETRY_TYPE_QUAD) interpolate_quads(g, args);
   else if (g->type == RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE) interpolate_lines(g, args);
-  else if (g->isFlatCubicCurve()) interpolate_curves(g, args);
+  else if (g->isCubicCurve()) interpolate_curves(g, args); // (interpolate_helper does not look at the subtype)
   else if (g->type == RTC_GEOMETRY_TYPE_SUBDIVISION) interpolate_subdiv(g, args);
   else unsupported("rtcInterpolate on this geometry type");
   CATCH_END(args && args->geometry ? devOf(args->geometry) : nullptr)

@@ -1031,7 +1031,7 @@ void interpolate_curves(const Geometry* geom, const RTCInterpolateArguments* arg
   if (i0 + 3 >= src->count) RT_THROW(RTC_ERROR_INVALID_ARGUMENT, "rtcInterpolate: curve index out of range");
   const float t = args->u, s = 1.0f - t;
   float b[4], d[4], dd[4];
-  if (geom->type == RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE) {
+  if (geom->isBSplineCurve()) {
     const float n1 = (4.0f * (s * s * s) + (t * t * t)) + (12.0f * ((s * t) * s) + 6.0f * ((t * s) * t));
     const float n2 = (4.0f * (t * t * t) + (s * s * s)) + (12.0f * ((t * s) * t) + 6.0f * ((s * t) * s));
     const float sixth = 1.0f / 6.0f;

@@ -33,6 +33,8 @@ struct LaunchParams
   uint32_t octMax;         // lanes with node work up to which a wave runs the child-parallel node step (0 = never; env RTAMD_OCT_MAX)
   uint32_t wgPool;         // 1: the four waves of a workgroup share the rays of a queue grab (RayPool in trace_loop.hip.h; a grab takes rayChunk per wave
                            // of the workgroup), 0: every wave grabs for itself (env RTAMD_WG_POOL)
+  uint32_t roundCurves;    // kinds ACCEL_CURVE_*: 1 = the CurveRecords are round curves (Accel::roundCurves): launch_trace_curve hands the launch to
+                           // launch_trace_round_curve (trace_round_curve.hip).  Host only, in what was padding in front of `queues`: no other member moves
   uint32_t* queues;        // TRACE_QUEUES work-queue heads, zeroed on the stream before the launch
   // Filter-function re-trace (row f3): ray i skips the triangles (geomID, primID) listed in
   // exclPairs[exclOffsets[i] .. exclOffsets[i+1]) - the candidates a host filter callback rejected in earlier rounds.
@@ -64,6 +66,8 @@ struct LaunchParams
                            // whose depth the builder reported correctly: the overflow area is sized for the worst case)
 };
 
+static_assert(offsetof(LaunchParams, wgPool) + 4 == offsetof(LaunchParams, roundCurves) && offsetof(LaunchParams, roundCurves) + 4 == offsetof(LaunchParams, queues),
+              "roundCurves fills the padding in front of `queues`");
 static_assert(offsetof(LaunchParams, instHair) + 4 == offsetof(LaunchParams, survivors), "instHair fills the padding in front of `survivors`");
 
 // ---- persistent consumer for small calls (trace_service.hip.h, rt_service.cpp) ---------------------------------------------

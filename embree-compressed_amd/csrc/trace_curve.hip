@@ -39,6 +39,7 @@ namespace rtamd {
 
 hipError_t launch_trace_curve(const LaunchParams& p, hipStream_t stream)
 {
+  if (p.roundCurves) return launch_trace_round_curve(p, stream); // the records are tubes (Scene::roundCurveAccel): trace_round_curve.hip
 #ifdef CURVE_BASIS_TABLE
   static bool uploaded = false;
   if (!uploaded) {

@@ -19,7 +19,9 @@ RTC_GEOMETRY_TYPE_TRIANGLE = 0
 RTC_GEOMETRY_TYPE_QUAD = 1
 RTC_GEOMETRY_TYPE_SUBDIVISION = 8
 RTC_GEOMETRY_TYPE_FLAT_LINEAR_CURVE = 17
+RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE = 24  # device config round_curves=1
 RTC_GEOMETRY_TYPE_FLAT_BEZIER_CURVE = 25
+RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE = 32  # device config round_curves=1
 RTC_GEOMETRY_TYPE_FLAT_BSPLINE_CURVE = 33
 RTC_GEOMETRY_TYPE_INSTANCE = 121
 RTC_BUFFER_TYPE_INDEX = 0
@@ -494,6 +496,37 @@ class Scene:
             gid = geom_id
         L.rtcReleaseGeometry(g)
         self.device.check("add_curves")
+        return gid
+
+    def add_round_curves(self, verts4, first_index, basis="bezier", geom_id=None, flags=None):
+        """Round cubic curves, tubes (RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE for basis="bezier", RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE for
+        basis="bspline"; the device config needs round_curves=1): verts4, first_index and flags as in add_curves; there is no
+        tessellation rate; shared buffers padded like add_lines."""
+        L = self.lib
+        types = {"bezier": RTC_GEOMETRY_TYPE_ROUND_BEZIER_CURVE, "bspline": RTC_GEOMETRY_TYPE_ROUND_BSPLINE_CURVE}
+        if basis not in types:
+            raise ValueError("add_round_curves: basis must be 'bezier' or 'bspline'")
+        v = np.ascontiguousarray(verts4, dtype=np.float32).reshape(-1, 4)
+        vpad = np.zeros((v.shape[0] + 1, 4), dtype=np.float32)
+        vpad[: v.shape[0]] = v
+        idx = np.ascontiguousarray(first_index, dtype=np.uint32).reshape(-1)
+        g = L.rtcNewGeometry(self.device.handle, types[basis])
+        self.device.check("rtcNewGeometry(ROUND_%s_CURVE)" % basis.upper())
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_VERTEX, 0, RTC_FORMAT_FLOAT4, vpad.ctypes.data, 0, 16, v.shape[0])
+        L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_INDEX, 0, RTC_FORMAT_UINT, idx.ctypes.data, 0, 4, idx.shape[0])
+        self._keep += [vpad, idx]
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+            L.rtcSetSharedGeometryBuffer(g, RTC_BUFFER_TYPE_FLAGS, 0, RTC_FORMAT_UCHAR, fl.ctypes.data, 0, 1, fl.shape[0])
+            self._keep.append(fl)
+        L.rtcCommitGeometry(g)
+        if geom_id is None:
+            gid = L.rtcAttachGeometry(self.handle, g)
+        else:
+            L.rtcAttachGeometryByID(self.handle, g, geom_id)
+            gid = geom_id
+        L.rtcReleaseGeometry(g)
+        self.device.check("add_round_curves")
         return gid
 
     def add_curves_mb(self, verts4_per_step, first_index, basis="bezier", tessellation_rate=None, geom_id=None, flags=None):

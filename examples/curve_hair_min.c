@@ -7,8 +7,8 @@
  * the ribbon (it faces the ray), u along the curve, v in [-1, 1] across it and Ng = the curve's derivative at u, not normalised.
  * rtcInterpolate evaluates the geometry's own basis on the user's control points.
  *
- * An application should try the geometry type: RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED stays 0, because it speaks for the round
- * curve types as well, which this library refuses.
+ * An application should try the geometry type: RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED speaks for the round
+ * curve types as well, which this library takes only on a device created with round_curves=1 (round_curve_min.c): it is 0 here.
  *
  * C99 on purpose:
  *   gcc -std=c99 -Iinclude examples/curve_hair_min.c -Lembree-compressed_amd/lib -lembree3 -lm \

@@ -5,8 +5,8 @@
  * (the curve is flat: a ribbon that faces the ray), u along the segment, v = 0 and Ng = v1 - v0, not normalised.  rtcInterpolate gives
  * the point on the axis and the interpolated radius.
  *
- * An application should try the geometry type: RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED stays 0, because it speaks for the Bezier
- * and B-spline curve types as well, which this library refuses.
+ * An application should try the geometry type: RTC_DEVICE_PROPERTY_CURVE_GEOMETRY_SUPPORTED speaks for all five curve types, and the
+ * round Bezier and B-spline ones are taken only on a device created with round_curves=1 (round_curve_min.c): it is 0 here.
  *
  * C99 on purpose:
  *   gcc -std=c99 -Iinclude examples/line_segments_min.c -Lembree-compressed_amd/lib -lembree3 -lm \

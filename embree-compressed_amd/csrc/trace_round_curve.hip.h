@@ -21,7 +21,8 @@
 //                   level's per-lane state lives in named registers
 //   Newton          at most five iterations of the 2x2 system in (u, t): f = dot(R, T), g = sqrt(dot(R, R) - f^2) - r(u) with R = Q(t) -
 //                   P(u), T = normalize(P'(u)); from (u of the outer cylinder's hit, tp0.lower) for a front and (..., tp1.upper) for a back
-//                   candidate.  Converged when |f| < 16 ulp max|P'| and |g| < 16 ulp |dir|; accepted when tnear < t + dt < tfar and
+//                   candidate.  Converged when |f| < 16 ulp max|P'| and |g| < 16 ulp max(|dir|, cmax), cmax the largest |component| of the
+//                   relative control points (the reference: 16 ulp |dir|, which a short dir puts below g's own rounding); accepted when tnear < t + dt < tfar and
 //                   0 <= u <= 1.  Hit: t + dt, u, v = 0, Ng = cross(cross(P', Rn), P'.w Rn + P') with Rn = normalize(R), not normalised,
 //                   evaluated at the (u, t) that is reported (the reference: at the iterate before the last update)
 // Order.  The reference walks a level's candidates one at a time, front to back (all tp0, then all tp1), each against the tfar the
@@ -145,7 +146,21 @@ __device__ __forceinline__ float rc_sqr_dist(float px, float py, float pz, float
 // intersect_bezier_iterative_jacobian from (u, t), on this lane alone.  true: converged and accepted, h holds the hit (t with dt added)
 __device__ __forceinline__ bool rc_newton(const RoundCtx& c, float u, float t, TriHit& h)
 {
-  const float lenDir = sqrtf(dot3(c.dx, c.dy, c.dz, c.dx, c.dy, c.dz));
+  // The scale of the bound on g.  The reference has |dir| alone; g is a distance in world units, and its float32 error is a few ulp of
+  // what enters R = Q - P: the control points relative to the ray's reference point.  Under a short unnormalised direction (|dir| below
+  // the curve's extent) 16 ulp |dir| drops below that error, Newton never "converges", and the front hit is lost to the back of the tube,
+  // to another curve or to a miss.  HERE the scale is max(|dir|, cmax) with cmax the largest |x|, |y|, |z|, |w| of the four relative
+  // control points: the same bits as the reference's bound wherever |dir| >= cmax, a bound the arithmetic can meet everywhere else
+  float gScale = sqrtf(dot3(c.dx, c.dy, c.dz, c.dx, c.dy, c.dz));
+  {
+    float4 c0, c1, c2, c3;
+    rc_points(c, c0, c1, c2, c3);
+    const float m0 = fmaxf(fmaxf(fabsf(c0.x), fabsf(c0.y)), fmaxf(fabsf(c0.z), fabsf(c0.w)));
+    const float m1 = fmaxf(fmaxf(fabsf(c1.x), fabsf(c1.y)), fmaxf(fabsf(c1.z), fabsf(c1.w)));
+    const float m2 = fmaxf(fmaxf(fabsf(c2.x), fabsf(c2.y)), fmaxf(fabsf(c2.z), fabsf(c2.w)));
+    const float m3 = fmaxf(fmaxf(fabsf(c3.x), fabsf(c3.y)), fmaxf(fabsf(c3.z), fabsf(c3.w)));
+    gScale = fmaxf(gScale, fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)));
+  }
 #pragma nounroll
   for (int i = 0; i < 5; i++) {
     const float qx = t * c.dx, qy = t * c.dy, qz = t * c.dz; // Q = madd(t, dir, org) with org = 0
@@ -181,7 +196,7 @@ __device__ __forceinline__ bool rc_newton(const RoundCtx& c, float u, float t, T
     u -= (dgdt * f - dfdt * g) * rdet;
     t -= (dfdu * g - dgdu * f) * rdet;
     const bool convU = fabsf(f) < 16.0f * RC_ULP * fmaxf(fmaxf(fabsf(dp.x), fabsf(dp.y)), fabsf(dp.z));
-    const bool convT = fabsf(g) < 16.0f * RC_ULP * lenDir;
+    const bool convT = fabsf(g) < 16.0f * RC_ULP * gScale;
     if (convU && convT) {
       const float th = t + c.dt;
       if (!(th > c.tnear && th < c.tfar)) return false; // rejects NaNs

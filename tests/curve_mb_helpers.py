@@ -116,13 +116,16 @@ def hair_steps(nsteps):
     return steps, idx, org, dirs
 
 
-def moving_truth(nat, N, org, dirs, times, dtype=np.float64, exact=True, geom_id=0):
-    """curve_helpers.closest per distinct ray time on native_at_time(nat, t), gathered into one dict over all rays"""
+def moving_truth(nat, N, org, dirs, times, dtype=np.float64, exact=True, geom_id=0, tnear=None, tfar=None):
+    """curve_helpers.closest per distinct ray time on native_at_time(nat, t), gathered into one dict over all rays; tnear / tfar [m]
+    default to 0 and inf"""
     m = len(org)
     out = None
+    tnear = np.zeros(m, np.float32) if tnear is None else np.asarray(tnear, np.float32)
+    tfar = np.full(m, np.inf, np.float32) if tfar is None else np.asarray(tfar, np.float32)
     for t in np.unique(times):
         sel = np.nonzero(times == t)[0]
-        c = ch.closest([(native_at_time(nat, t, exact), N, geom_id)], org[sel], dirs[sel], np.zeros(len(sel), np.float32), np.full(len(sel), np.inf, np.float32), dtype)
+        c = ch.closest([(native_at_time(nat, t, exact), N, geom_id)], org[sel], dirs[sel], tnear[sel], tfar[sel], dtype)
         if out is None:
             out = {k: np.zeros((m,) + a.shape[1:], a.dtype) for k, a in c.items()}
         for k, a in c.items():

@@ -282,11 +282,17 @@ def ray_space64(dirs):
     return s, dx, dy, n
 
 
-def lines_truth64(v0, v1, org, dirs):
+def _window(m, tnear, tfar):
+    """tnear / tfar [m] in float64, 0 and inf by default"""
+    return (np.zeros(m) if tnear is None else np.asarray(tnear, np.float64)), (np.full(m, np.inf) if tfar is None else np.asarray(tfar, np.float64))
+
+
+def lines_truth64(v0, v1, org, dirs, tnear=None, tfar=None):
     """v0, v1 [n, 4] = (x, y, z, radius), org / dirs [m, 3], all float64 -> dict: hit [m], seg [m] (the nearest valid segment, the lowest
-    index on an equal t), t, u"""
+    index on an equal t), t, u, and near_edge / near_tie [m] as line_helpers.closest has them; tnear / tfar [m] default to 0 and inf"""
     v0, v1, org = np.asarray(v0, np.float64), np.asarray(v1, np.float64), np.asarray(org, np.float64)
     assert v0.dtype == np.float64 and org.dtype == np.float64
+    tn, tf = (x[:, None] for x in _window(len(org), tnear, tfar))
     s, dx, dy, n = ray_space64(dirs)
     rows = np.stack([dx, dy, n], 1)  # [m, 3, 3]
     with np.errstate(all="ignore"):
@@ -299,11 +305,16 @@ def lines_truth64(v0, v1, org, dirs):
         pw = v0[None, :, 3] + u * vw
         t = p[..., 2] * s[:, None]
         nonzero = ((v1[:, :3] - v0[:, :3]) != 0).any(1)[None, :]
-        ok = (p[..., 0] ** 2 + p[..., 1] ** 2 <= pw * pw) & (t > 0) & (t > 2.0 * pw * s[:, None]) & nonzero
+        d2, r2 = p[..., 0] ** 2 + p[..., 1] ** 2, pw * pw
+        ok = (d2 <= r2) & (t > tn) & (t <= tf) & (t > tn + 2.0 * pw * s[:, None]) & nonzero
+        near_edge = (np.where(r2 > 0, np.abs(d2 - r2) / np.where(r2 > 0, r2, 1), np.inf) <= 1e-4).any(1)
     tt = np.where(ok, t, np.inf)
     seg = tt.argmin(1)
     ar = np.arange(len(org))
-    return {"hit": np.isfinite(tt[ar, seg]), "seg": seg, "t": tt[ar, seg], "u": u[ar, seg]}
+    two = np.sort(np.concatenate([tt, np.full((len(org), 1), np.inf)], 1), 1)[:, :2]  # (a single segment has no second candidate)
+    with np.errstate(all="ignore"):
+        near_tie = np.isfinite(two[:, 1]) & (np.abs(two[:, 1] - two[:, 0]) <= 1e-4 * np.abs(two[:, 0]))
+    return {"hit": np.isfinite(tt[ar, seg]), "seg": seg, "t": tt[ar, seg], "u": u[ar, seg], "near_edge": near_edge, "near_tie": near_tie}
 
 
 def _bezier64(u):
@@ -311,11 +322,14 @@ def _bezier64(u):
     return ([t0 ** 3, 3 * t1 * t0 * t0, 3 * t1 * t1 * t0, t1 ** 3], [-3 * t0 * t0, 3 * (t0 * t0 - 2 * t0 * t1), 3 * (2 * t0 * t1 - t1 * t1), 3 * t1 * t1])
 
 
-def curves_truth64(groups, org, dirs):
+def curves_truth64(groups, org, dirs, tnear=None, tfar=None):
     """groups: [(cp [n, 4, 4] native (Bezier) control points in float64, N, geomID)] -> dict: hit [m], geomID, primID (index in its group),
-    t, u, v; on an equal t the first group, lowest curve, lowest segment wins"""
+    t, u, v, and near_edge / near_tie [m] as curve_helpers.closest has them; on an equal t the first group, lowest curve, lowest segment
+    wins; tnear / tfar [m] default to 0 and inf"""
     org = np.asarray(org, np.float64)
     m = len(org)
+    tn, tf = (x[:, None, None] for x in _window(m, tnear, tfar))
+    near_edge, two = np.zeros(m, bool), np.full((m, 2), np.inf)
     s, dx, dy, n = ray_space64(dirs)
     rows = np.stack([dx, dy, n * s[:, None]], 1)  # the z row scaled by s once more: a transformed z is a ray parameter
     best = {"hit": np.zeros(m, bool), "geomID": np.full(m, -1), "primID": np.full(m, -1), "t": np.full(m, np.inf), "u": np.zeros(m), "v": np.zeros(m)}
@@ -350,11 +364,13 @@ def curves_truth64(groups, org, dirs):
             den = e1[0] * e0[1] - e1[1] * e0[0]
             Tn = v0[0] * ngx + v0[1] * ngy + v0[2] * den
             Ts = np.where(den < 0, -Tn, Tn)
-            ok = (np.maximum(Ue, Ve) <= 0) & (Ts > 0) & (den != 0)
+            ok = (np.maximum(Ue, Ve) <= 0) & (Ts > np.abs(den) * tn) & (Ts <= np.abs(den) * tf) & (den != 0)
             t, u, v = Tn / den, Ue / den, Ve / den
             u, v = np.where(first, u, 1.0 - u), np.where(first, v, 1.0 - v)
-            ok &= t > 2.0 * ((1.0 - u) * A[5] + u * B[5]) * s[:, None, None]
+            ok &= t > tn + 2.0 * ((1.0 - u) * A[5] + u * B[5]) * s[:, None, None]
+            near_edge |= (np.abs(np.maximum(Ue, Ve) / den) <= 1e-4).reshape(m, -1).any(1)
         tt = np.where(ok, t, np.inf).reshape(m, -1)
+        two = np.sort(np.concatenate([two, tt], 1), 1)[:, :2]
         k = tt.argmin(1)
         sel = tt[ar, k] < best["t"]
         U = ((np.arange(N)[None, None, :] + u) / float(N)).reshape(m, -1)
@@ -362,4 +378,7 @@ def curves_truth64(groups, org, dirs):
         for key, val in (("geomID", np.full(m, gid)), ("primID", k // N), ("t", tt[ar, k]), ("u", U[ar, k]), ("v", V[ar, k])):
             best[key][sel] = val[sel]
         best["hit"] |= sel
+    with np.errstate(all="ignore"):
+        best["near_tie"] = np.isfinite(two[:, 1]) & (np.abs(two[:, 1] - two[:, 0]) <= 1e-4 * np.abs(two[:, 0]))
+    best["near_edge"] = near_edge
     return best

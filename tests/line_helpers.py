@@ -51,9 +51,10 @@ def ray_space(dirs, dt):
     return s, dx, dy, np.stack([nx, ny, nz], 1).astype(dt)
 
 
-def candidates(v0, v1, org, dirs, tnear, tfar, dtype=np.float64, chunk=256):
+def candidates(v0, v1, org, dirs, tnear, tfar, dtype=np.float64, chunk=256, self_rule=True):
     """LineIntersector1::intersect of all n segments (v0, v1: [n, 4] = x, y, z, radius) against all m rays.
-    Returns valid [m, n] bool, t [m, n], u [m, n], and margin [m, n] = |d2 - r2| / r2 (inf where r2 == 0)."""
+    Returns valid [m, n] bool, t [m, n], u [m, n], and margin [m, n] = |d2 - r2| / r2 (inf where r2 == 0).
+    self_rule=False leaves the self-intersection rule `t > tnear + 2 r s` out: a deliberately wrong side for the tests of the tests."""
     dt = np.float32 if dtype == np.float32 else np.float64
     v0, v1 = np.asarray(v0, np.float32).astype(dt), np.asarray(v1, np.float32).astype(dt)
     org, tnear, tfar = np.asarray(org, np.float32).astype(dt), np.asarray(tnear, np.float32).astype(dt), np.asarray(tfar, np.float32).astype(dt)
@@ -83,16 +84,18 @@ def candidates(v0, v1, org, dirs, tnear, tfar, dtype=np.float64, chunk=256):
             d2 = _fma(px, px, (py * py).astype(dt), dt)
             r2 = (pw * pw).astype(dt)
             tn, tf = tnear[a:b, None], tfar[a:b, None]
-            ok = (d2 <= r2) & (tn < t) & (t <= tf) & (t > (tn + ((dt(2) * pw).astype(dt) * sc).astype(dt)).astype(dt)) & nonzero[None, :]
+            ok = (d2 <= r2) & (tn < t) & (t <= tf) & nonzero[None, :]
+            if self_rule:
+                ok &= t > (tn + ((dt(2) * pw).astype(dt) * sc).astype(dt)).astype(dt)
             valid[a:b], T[a:b], U[a:b] = ok, t, u
             margin[a:b] = np.where(r2 > 0, np.abs(d2 - r2) / np.where(r2 > 0, r2, 1), np.inf)
     return valid, T, U, margin
 
 
-def closest(v0, v1, org, dirs, tnear, tfar, dtype=np.float64):
+def closest(v0, v1, org, dirs, tnear, tfar, dtype=np.float64, self_rule=True):
     """-> dict: hit [m] bool, seg [m] (index of the nearest valid segment, lowest index on equal t), t, u, Ng [m, 3] float32 = v1 - v0 in
     float32, near_edge [m] (some segment has |d2 - r2| <= 1e-4 r2), near_tie [m] (the two nearest candidates within 1e-4 relative in t)"""
-    valid, T, U, margin = candidates(v0, v1, org, dirs, tnear, tfar, dtype)
+    valid, T, U, margin = candidates(v0, v1, org, dirs, tnear, tfar, dtype, self_rule=self_rule)
     tt = np.where(valid, T, np.inf)
     seg = tt.argmin(1)
     m = tt.shape[0]

@@ -125,14 +125,17 @@ def round_robin_times(m, nsteps):
     return ((np.arange(m) % (4 * S + 1)) / (4.0 * S)).astype(np.float32)
 
 
-def moving_truth(steps, idx, org, dirs, times, dtype=np.float64):
-    """line_helpers.closest per distinct ray time on at_time(steps, t), gathered into one dict over all rays"""
+def moving_truth(steps, idx, org, dirs, times, dtype=np.float64, tnear=None, tfar=None):
+    """line_helpers.closest per distinct ray time on at_time(steps, t), gathered into one dict over all rays; tnear / tfar [m] default
+    to 0 and inf"""
     m = len(org)
     out = None
+    tnear = np.zeros(m, np.float32) if tnear is None else np.asarray(tnear, np.float32)
+    tfar = np.full(m, np.inf, np.float32) if tfar is None else np.asarray(tfar, np.float32)
     for t in np.unique(times):
         sel = np.nonzero(times == t)[0]
         v0, v1 = lh.ends(at_time(steps, t), idx)
-        c = lh.closest(v0, v1, org[sel], dirs[sel], np.zeros(len(sel), np.float32), np.full(len(sel), np.inf, np.float32), dtype)
+        c = lh.closest(v0, v1, org[sel], dirs[sel], tnear[sel], tfar[sel], dtype)
         if out is None:
             out = {k: np.zeros((m,) + a.shape[1:], a.dtype) for k, a in c.items()}
         for k, a in c.items():

@@ -394,13 +394,16 @@ def _plane(P, N, d, dt):
     return np.where(eps | (DN < 0), dt(-np.inf), t), np.where(eps | (DN > 0), dt(np.inf), t)
 
 
-def _newton(c, d, tn, tf, dts, u, t, dt):
-    """intersect_bezier_iterative_jacobian on candidates -> ok, t (with dt added), u, Ng"""
+def _newton(c, d, tn, tf, dts, u, t, dt, reference_bound=False):
+    """intersect_bezier_iterative_jacobian on candidates -> ok, t (with dt added), u, Ng.  reference_bound: |g| < 16 ulp |dir| as the
+    reference has it, not the leaf's 16 ulp max(|dir|, cmax)"""
     n = len(u)
     ok, done = np.zeros(n, bool), np.zeros(n, bool)
     T, U, NG = np.full(n, np.inf, dt), np.zeros(n, dt), np.zeros((n, 3), dt)
     ulp = dt(ULP)
     lend = np.sqrt(_dot(d, d, dt)).astype(dt)
+    if not reference_bound:  # rc_newton: max(|dir|, cmax), cmax the largest |component| of the relative control points, radius included
+        lend = np.maximum(lend, np.abs(c).reshape(n, -1).max(1))
     for _ in range(5):
         Q = (t[:, None] * d).astype(dt)
         P, dP = _eval(c, u, dt)
@@ -443,7 +446,7 @@ def _newton(c, d, tn, tf, dts, u, t, dt):
     return ok, T, U, NG
 
 
-def _level(c, d, tn, tf, dts, ray, prim, u0, u1, depth, dt, hits):
+def _level(c, d, tn, tf, dts, ray, prim, u0, u1, depth, dt, hits, reference_bound=False):
     """one level of intersect_bezier_recursive_jacobian for candidates (each: relative control points c, ray d / tn / tf, dt shift, [u0, u1])"""
     if not len(u0):
         return
@@ -505,14 +508,14 @@ def _level(c, d, tn, tf, dts, ray, prim, u0, u1, depth, dt, hits):
         pi, ki = np.nonzero(ready)
         if len(pi):
             with np.errstate(all="ignore"):
-                ok, T, U, NG = _newton(c[pi], d[pi], tn[pi], tf[pi], dts[pi], uo[ph][pi, ki], start[ph][pi, ki], dt)
+                ok, T, U, NG = _newton(c[pi], d[pi], tn[pi], tf[pi], dts[pi], uo[ph][pi, ki], start[ph][pi, ki], dt, reference_bound)
             hits.append((ray[pi][ok], prim[pi][ok], T[ok], U[ok], NG[ok]))
         pi, ki = np.nonzero(val[ph] & ~ready)
         if len(pi) and depth < 3:
-            _level(c[pi], d[pi], tn[pi], tf[pi], dts[pi], ray[pi], prim[pi], vu[pi, ki], vu[pi, ki + 1], depth + 1, dt, hits)
+            _level(c[pi], d[pi], tn[pi], tf[pi], dts[pi], ray[pi], prim[pi], vu[pi, ki], vu[pi, ki + 1], depth + 1, dt, hits, reference_bound)
 
 
-def restate(groups, org, dirs, tnear, tfar, dtype=np.float32):
+def restate(groups, org, dirs, tnear, tfar, dtype=np.float32, reference_bound=False):
     """The leaf on every (ray, curve) pair whose ray meets the curve's bounds.  -> dict hit, geomID, primID, t, u, v, Ng per ray (nearest
     accepted hit; the first group, lowest curve wins an equal t)"""
     dt = np.float32 if dtype == np.float32 else np.float64
@@ -529,7 +532,7 @@ def restate(groups, org, dirs, tnear, tfar, dtype=np.float32):
     c = V.copy()
     c[..., :3] = (V[..., :3] - ref[:, None]).astype(dt)
     hits = []
-    _level(c, d, tn, tf, dts, ri, ci, np.zeros(len(ri), dt), np.ones(len(ri), dt), 1, dt, hits)
+    _level(c, d, tn, tf, dts, ri, ci, np.zeros(len(ri), dt), np.ones(len(ri), dt), 1, dt, hits, reference_bound)
     m = len(org)
     out = {"hit": np.zeros(m, bool), "geomID": np.full(m, -1, np.int64), "primID": np.full(m, -1, np.int64), "t": np.full(m, np.inf, dt), "u": np.zeros(m, dt),
            "v": np.zeros(m, dt), "Ng": np.zeros((m, 3), dt)}
